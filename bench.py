@@ -20,17 +20,28 @@ four whole episodes, i.e. the episode average), otherwise it is centred on the m
 whose tick costs what the episode costs on average (config.episode_window says where; the `episode`
 object carries the whole profile measured in the same run).
 
-The timed region holds the K launches and nothing else (no event records).  The dominant kernel's
-average launch duration (roofline.achieved) is measured with HIP events on the launch stream around
-windows of 25 back-to-back launches, over one whole episode just before and one just after the timed
-region.  `roofline.frac` prices SURVEY's algorithmic bytes; `roofline.frac_moved` the HBM bytes the PMC counters
+The timed region holds the K launches and nothing else (no event records).  A plain run does only what
+`value` and `ms_per_step` need: set up, W warm-up launches, the launches up to the start of the timed window,
+the K timed launches, the outputs (`--dump-outputs`), the line.  The launches up to the window include one whole
+episode after the warm-up, untimed (its launches are the same with and without `--full`, so are the outputs).
+`--full` adds everything else, as follows.  The dominant kernel's average launch duration (roofline.achieved)
+is measured with HIP events on the launch stream around windows of 25 back-to-back launches, over one whole
+episode just before and one just after the timed region.  `roofline.frac` prices SURVEY's algorithmic bytes;
+`roofline.frac_moved` the HBM bytes the PMC counters
 saw (`traffic`), `roofline.frac_full_load` the algorithmic bytes at the cost of a tick with every agent in the
 game (the window of the episode profile that starts at the top of an episode).  `--no-tags` sets the tagging
 distance to 0: nobody ever leaves the game, every tick is a full-load tick (the policy-independent worst case).
 `ms_per_step_spread` = min / median / max of five repeats of the timed region at the same place of the
-episode (`value` is the first).
+episode (`value` is the first).  Also only with `--full`: the CPU baseline (N = 1), the per-rank times and the
+all-reduce time (N > 1) and, by default at N > 1, the configs[3] trainer iteration.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
+`--dump-outputs DIR` writes, after the timed region, what its last step left for a caller of the tick: the
+observations, sampled actions, rewards and done flags (and the [T, E, ...] batch tensors of a multi-tick launch)
+as DIR/<name>.npy (DIR/<name>_rank<r>.npy at N > 1), float32 as float32 and integers as float64.  Above
+64 MB in all, every array keeps the same seeded sample of replicas.  The inputs are seeded: the same
+arguments give the same outputs.
+
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
         (N > 1 without a launcher: bench.py starts its own N ranks through torch.distributed.run)
         python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 Prints ONE JSON line on rank 0.
@@ -65,6 +76,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 VALU_CYCLES = {"ADD_F32": 1.2, "MUL_F32": 1.2, "FMA_F32": 2.0, "INT32": 2.9, "CVT": 2.9, "INT64": 4.0,
                "ADD_F64": 4.0, "MUL_F64": 4.0, "FMA_F64": 4.0, "TRANS_F32": 6.0, "OTHER": 2.5}
 SIMDS = 256 * 4
+DUMP_BYTES = 64 * 1000 * 1000  # --dump-outputs: at most this much in all
 
 BENCH_CFG = dict(num_taggers=5, num_runners=100, grid_length=20.0, episode_length=500, max_acceleration=0.1,
                  min_acceleration=-0.1, max_turn=2.356, min_turn=-2.356, num_acceleration_levels=20,
@@ -172,6 +184,19 @@ def cpu_baseline(cfg, target_seconds=12.0):
                       "Orientation: the reference's own Python step() does ~49 env-steps/s per core (BASELINE.md section 3)"}
 
 
+def dump_outputs(dirname, arrays, num_envs, suffix=""):
+    """--dump-outputs: `arrays` maps a name to (host array, its replica axis).  Writes dirname/<name><suffix>.npy,
+    float32 kept, everything else as float64; over DUMP_BYTES in all, the same seeded sample of replicas of every array."""
+    arrays = {k: (a.astype(np.float32 if a.dtype == np.float32 else np.float64), ax) for k, (a, ax) in arrays.items()}
+    total = sum(a.nbytes for a, _ in arrays.values())
+    if total > DUMP_BYTES:
+        keep = np.sort(np.random.RandomState(0).choice(num_envs, max(1, num_envs * DUMP_BYTES // total), replace=False))
+        arrays = {k: (np.take(a, keep, axis=ax), ax) for k, (a, ax) in arrays.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for k, (a, _) in arrays.items():
+        np.save(os.path.join(dirname, f"{k}{suffix}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -198,11 +223,18 @@ def main():
     ap.add_argument("--no-spread", action="store_true", help="skip the four extra repeats of the timed region")
     ap.add_argument("--profile-episodes", type=int, default=0,
                     help="profiler helper: run this many whole episodes of ticks and exit (no timing, no JSON)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline value does not need: the episode profile and rooflines, the spread "
+                         "of five repeats, the CPU baseline, per-rank and all-reduce times, the trainer leg (auto)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left for a caller (observations, actions, rewards, done) as "
+                         "DIR/<name>.npy, at most 64 MB in all")
     ap.add_argument("--trainer-leg", choices=("auto", "on", "off"), default="auto",
                     help="add a `trainer` object to the line: ONE timed PPO training iteration of BASELINE configs[3] per rank "
                          "(2000 replicas x 250 ticks, both policies, the real one-bucket gradient all-reduce) after one warm-up "
                          "iteration -- rollout_ms, update_ms, allreduce_us measured inside the iteration, end-to-end env-steps/s, "
-                         "collectives per iteration, parameter checksum per rank.  auto = when --gpus > 1 (tag_continuous only)")
+                         "collectives per iteration, parameter checksum per rank.  auto = with --full when --gpus > 1 "
+                         "(tag_continuous only)")
     ap.add_argument("--trainer-timeout", type=float, default=300.0,
                     help="seconds after which the trainer leg is abandoned (the kernel line is printed without it)")
     ap.add_argument("--trainer-num-envs", type=int, default=2000, help="replicas per rank of the trainer leg")
@@ -210,6 +242,8 @@ def main():
     ap.add_argument("--unfused", action="store_true",
                     help="tick = 4 launches (sample x2, step, fused reset) instead of the single tick kernel")
     args = ap.parse_args()
+    if args.steps < 1 or (args.mode == "graph" and args.steps % 10):
+        ap.error("--steps is the number of timed steps: a positive number (--mode graph: a multiple of 10, the graph's ticks)")
 
     from warp_drive_amd import distributed as wdd
 
@@ -292,7 +326,6 @@ def main():
                            rollout_batch=rollout_batch)
     steps, warmup = args.steps, args.warmup
     if args.mode == "graph":
-        steps = max(10, steps // 10 * 10)
         warmup = max(10, warmup // 10 * 10)
 
     def run(n):
@@ -343,8 +376,13 @@ def main():
         return [e0.elapsed_time(e1) * 1e3 / WIN for e0, e1 in evs]
 
     P = (max(T, 500) + WIN - 1) // WIN * WIN if args.mode == "plan" else 500
+    # one whole episode before the timed window: it leaves the clocks where a long run has them (without it, a window of
+    # 100 launches after 10 warm-up launches measured 1.6 - 3 % slower); --full times it (the episode profile)
     first_pass_tick = ticks_done % T
-    win_us = time_episode(P)   # one whole episode; also leaves the clocks where a long run has them
+    if args.full:
+        win_us = time_episode(P)
+    else:
+        run(P)
     ticks_done += P
     # the timed window: on an episode boundary when it covers whole episodes, else centred mid-episode
     t0 = 0 if steps >= T else (T - steps) // 2
@@ -364,24 +402,31 @@ def main():
 
     window_first_tick = ticks_done % T
     live_first = None
-    if is_tc:
+    if is_tc and args.full:
         torch.cuda.synchronize()
         live_first = float(w.cuda_data_manager.pull_data_from_device("still_in_the_game").sum(axis=1).mean())
     elapsed, elapsed_local = timed_region()
     ticks_done += steps
-    repeats = [elapsed]
-    for _ in range(0 if args.no_spread else 4):  # the same K launches at the same place of the episode
-        pre = (window_first_tick - ticks_done) % T if is_tc else 0
-        run(pre)
-        ticks_done += pre
-        repeats.append(timed_region()[0])
-        ticks_done += steps
-    per_rank_ms = wdd.gather_floats(elapsed_local / steps * 1e3)
-    allreduce_us = wdd.time_allreduce(190550, 50) if world > 1 else None  # both policies' gradients, one bucket
-    second_pass_tick = ticks_done % T
-    win_us2 = time_episode(P)
-    kern_us = (sum(win_us) + sum(win_us2)) / (len(win_us) + len(win_us2))
-    kern_n = (len(win_us) + len(win_us2)) * WIN
+    if args.dump_outputs:
+        dm = w.cuda_data_manager
+        arrays = {"done" if k == "_done_" else k: (dm.pull_data_from_device(k), 0)
+                  for k in ("observations", "sampled_actions", "rewards", "_done_") if dm.is_data_on_device(k)}
+        arrays.update({f"batch_{k}": (v.cpu().numpy(), 1) for k, v in (rollout_batch or {}).items()})
+        dump_outputs(args.dump_outputs, arrays, E, f"_rank{rank}" if world > 1 else "")
+    if args.full:
+        repeats = [elapsed]
+        for _ in range(0 if args.no_spread else 4):  # the same K launches at the same place of the episode
+            pre = (window_first_tick - ticks_done) % T if is_tc else 0
+            run(pre)
+            ticks_done += pre
+            repeats.append(timed_region()[0])
+            ticks_done += steps
+        per_rank_ms = wdd.gather_floats(elapsed_local / steps * 1e3)
+        allreduce_us = wdd.time_allreduce(190550, 50) if world > 1 else None  # both policies' gradients, one bucket
+        second_pass_tick = ticks_done % T
+        win_us2 = time_episode(P)
+        kern_us = (sum(win_us) + sum(win_us2)) / (len(win_us) + len(win_us2))
+        kern_n = (len(win_us) + len(win_us2)) * WIN
 
     out = None
     if rank == 0:
@@ -412,38 +457,6 @@ def main():
         elif rollout_batch is not None:
             # TagGridWorld: per env-step N x (F + 2) floats recorded + the done flag; the per-tick arrays once per launch
             bytes_per_launch = ((4 * N * (4 * N + 1 + 2) + 4) * engine.ticks_per_launch + bytes_per_env_step) * E
-        kern_s = kern_us * 1e-6
-        achieved = bytes_per_launch / kern_s / 1e9 if kern_s > 0 else 0.0
-        # HBM bytes per launch from the PMC passes (scripts/collect_profiles.sh): only quoted when they
-        # were collected on exactly the code object loaded now and at this shape, else null
-        traffic, traffic_stale = None, False
-        pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-        if os.path.exists(pmc):
-            try:
-                from warp_drive_amd.managers import hip_driver
-
-                sha = hip_driver.code_object_sha256(engine.step_kernel_name)
-                shape_recs = [r for r in json.load(open(pmc)).values()
-                              if r.get("kernel") == engine.step_kernel_name and r.get("num_envs") == E
-                              and r.get("full_obs") == bool(args.full_obs) and N == 105
-                              and bool(r.get("no_tags", False)) == bool(args.no_tags)]
-                recs = [r for r in shape_recs if r.get("hsaco_sha256") == sha]
-                if args.workload == "tag_continuous" and recs:
-                    traffic = recs[0].get("hbm_bytes_per_launch")
-                # counters exist for this shape but were collected on another build of the kernels
-                traffic_stale = bool(args.workload == "tag_continuous" and shape_recs and not recs)
-            except Exception:
-                traffic = None
-        # the tick with every agent in the game: the window of the episode profile closest to the top of an episode
-        full_load_us = full_load_tick = None
-        if is_tc and args.mode == "plan":
-            starts = [((first_pass_tick + i * WIN) % T, v) for i, v in enumerate(win_us)] + \
-                     [((second_pass_tick + i * WIN) % T, v) for i, v in enumerate(win_us2)]
-            top = [sv for sv in starts if sv[0] < WIN]
-            if top:
-                full_load_tick = min(sv[0] for sv in top)
-                vals = [v for st, v in top if st == full_load_tick]
-                full_load_us = sum(vals) / len(vals)
         out = {
             "metric": metric,
             "value": world * E * steps * engine.ticks_per_launch / elapsed,
@@ -469,58 +482,93 @@ def main():
                                    "episode_length": T, "whole_episodes": steps // T,
                                    "agents_in_the_game_at_first_tick": live_first},
             },
-            "ms_per_step_spread": {"min": min(repeats) / steps * 1e3, "median": sorted(repeats)[len(repeats) // 2] / steps * 1e3,
-                                   "max": max(repeats) / steps * 1e3, "repeats": len(repeats)},
-            "per_rank_ms_per_step": per_rank_ms,
             "cpus_of_rank0": (len(pinned) if pinned else None),  # N > 1: CPUs this rank was pinned to (next to its GPU)
-            "allreduce_us": allreduce_us,
-            "roofline": {
-                "bound": "hbm", "kernel": engine.step_kernel_name, "achieved": achieved, "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_stale": traffic_stale,
-                # the same launch duration priced on the bytes the counters saw (rows of agents out of the game are
-                # not rewritten: less than the algorithmic bytes) ...
-                "frac_moved": (traffic / kern_s / 1e9 / HBM_PEAK_GBS) if (traffic and kern_s > 0) else None,
-                # ... and the algorithmic bytes at the cost of a tick with every agent in the game
-                "frac_full_load": (bytes_per_launch / (full_load_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if full_load_us else None,
-                "full_load_us": full_load_us, "full_load_window_first_tick": full_load_tick,
-                "algorithmic_bytes_per_launch": bytes_per_launch, "avg_kernel_us": kern_s * 1e6,
-                "samples": kern_n,
-                "timing": f"HIP events around windows of {WIN} back-to-back launches, one whole episode "
-                          f"({P} launches) before + one after the timed region",
-            },
-            # tick cost along the episode, from the two timing passes (all replicas are at the same tick)
-            "episode": {"window_ticks": WIN, "first_pass_starts_at_tick": first_pass_tick,
-                        "second_pass_starts_at_tick": second_pass_tick,
-                        "us_per_tick_mean": kern_us, "us_per_tick_min": min(win_us + win_us2),
-                        "us_per_tick_max": max(win_us + win_us2),
-                        "us_per_tick_windows_first_pass": [round(v, 2) for v in win_us]},
-            "roofline_valu": valu_roofline(engine.step_kernel_name, E, bool(args.full_obs), kern_us)
-            if is_tc else None,
         }
-        if is_tc and args.mode == "plan" and kern_us > 0:
-            # The cost of a TagContinuous tick falls along the episode (agents leave the game), so a `value` timed over a
-            # window that is not a whole number of episodes is the rate of THAT window (the contract: exactly K timed
-            # steps), not of the workload.  The rate that belongs next to `roofline.frac` -- both from the two
-            # whole-episode HIP-event passes -- is always printed beside it, and the line says which kind `value` is.
-            whole = (steps % T == 0) and steps >= T
-            out["value_episode_average"] = world * E / (kern_us * 1e-6)
-            out["value_window"] = {"whole_episodes": whole, "first_tick": window_first_tick, "ticks": steps,
-                                   "note": None if whole else "`value` is the rate of a window shorter than (or not a multiple "
-                                   "of) an episode; quote `value_episode_average` next to roofline.frac"}
-        if not args.no_cpu_baseline and args.workload == "tag_continuous" and world == 1:  # N = 1 only
-            try:
-                out["cpu_baseline"] = cpu_baseline({k: v for k, v in cfg.items()})
-            except Exception as err:  # the baseline is reported context, never a reason to lose the GPU number
-                out["cpu_baseline"] = {"value": None, "unit": "env_steps/s", "cores": os.cpu_count(),
-                                       "kind": "port", "sample": f"failed: {err}"}
+        if args.full:
+            kern_s = kern_us * 1e-6
+            achieved = bytes_per_launch / kern_s / 1e9 if kern_s > 0 else 0.0
+            # HBM bytes per launch from the PMC passes (scripts/collect_profiles.sh): only quoted when they
+            # were collected on exactly the code object loaded now and at this shape, else null
+            traffic, traffic_stale = None, False
+            pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+            if os.path.exists(pmc):
+                try:
+                    from warp_drive_amd.managers import hip_driver
 
-    # BASELINE configs[3] is a TRAINING configuration (PPO + the gradient all-reduce over RCCL): at N > 1 the line also
-    # carries one training iteration timed from the inside, on every rank (collectives inside: all ranks take part).
+                    sha = hip_driver.code_object_sha256(engine.step_kernel_name)
+                    shape_recs = [r for r in json.load(open(pmc)).values()
+                                  if r.get("kernel") == engine.step_kernel_name and r.get("num_envs") == E
+                                  and r.get("full_obs") == bool(args.full_obs) and N == 105
+                                  and bool(r.get("no_tags", False)) == bool(args.no_tags)]
+                    recs = [r for r in shape_recs if r.get("hsaco_sha256") == sha]
+                    if args.workload == "tag_continuous" and recs:
+                        traffic = recs[0].get("hbm_bytes_per_launch")
+                    # counters exist for this shape but were collected on another build of the kernels
+                    traffic_stale = bool(args.workload == "tag_continuous" and shape_recs and not recs)
+                except Exception:
+                    traffic = None
+            # the tick with every agent in the game: the window of the episode profile closest to the top of an episode
+            full_load_us = full_load_tick = None
+            if is_tc and args.mode == "plan":
+                starts = [((first_pass_tick + i * WIN) % T, v) for i, v in enumerate(win_us)] + \
+                         [((second_pass_tick + i * WIN) % T, v) for i, v in enumerate(win_us2)]
+                top = [sv for sv in starts if sv[0] < WIN]
+                if top:
+                    full_load_tick = min(sv[0] for sv in top)
+                    vals = [v for st, v in top if st == full_load_tick]
+                    full_load_us = sum(vals) / len(vals)
+            out.update({
+                "ms_per_step_spread": {"min": min(repeats) / steps * 1e3, "median": sorted(repeats)[len(repeats) // 2] / steps * 1e3,
+                                       "max": max(repeats) / steps * 1e3, "repeats": len(repeats)},
+                "per_rank_ms_per_step": per_rank_ms,
+                "allreduce_us": allreduce_us,
+                "roofline": {
+                    "bound": "hbm", "kernel": engine.step_kernel_name, "achieved": achieved, "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_stale": traffic_stale,
+                    # the same launch duration priced on the bytes the counters saw (rows of agents out of the game are
+                    # not rewritten: less than the algorithmic bytes) ...
+                    "frac_moved": (traffic / kern_s / 1e9 / HBM_PEAK_GBS) if (traffic and kern_s > 0) else None,
+                    # ... and the algorithmic bytes at the cost of a tick with every agent in the game
+                    "frac_full_load": (bytes_per_launch / (full_load_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if full_load_us else None,
+                    "full_load_us": full_load_us, "full_load_window_first_tick": full_load_tick,
+                    "algorithmic_bytes_per_launch": bytes_per_launch, "avg_kernel_us": kern_s * 1e6,
+                    "samples": kern_n,
+                    "timing": f"HIP events around windows of {WIN} back-to-back launches, one whole episode "
+                              f"({P} launches) before + one after the timed region",
+                },
+                # tick cost along the episode, from the two timing passes (all replicas are at the same tick)
+                "episode": {"window_ticks": WIN, "first_pass_starts_at_tick": first_pass_tick,
+                            "second_pass_starts_at_tick": second_pass_tick,
+                            "us_per_tick_mean": kern_us, "us_per_tick_min": min(win_us + win_us2),
+                            "us_per_tick_max": max(win_us + win_us2),
+                            "us_per_tick_windows_first_pass": [round(v, 2) for v in win_us]},
+                "roofline_valu": valu_roofline(engine.step_kernel_name, E, bool(args.full_obs), kern_us)
+                if is_tc else None,
+            })
+            if is_tc and args.mode == "plan" and kern_us > 0:
+                # The cost of a TagContinuous tick falls along the episode (agents leave the game), so a `value` timed over a
+                # window that is not a whole number of episodes is the rate of THAT window (the contract: exactly K timed
+                # steps), not of the workload.  The rate that belongs next to `roofline.frac` -- both from the two
+                # whole-episode HIP-event passes -- is always printed beside it, and the line says which kind `value` is.
+                whole = (steps % T == 0) and steps >= T
+                out["value_episode_average"] = world * E / (kern_us * 1e-6)
+                out["value_window"] = {"whole_episodes": whole, "first_tick": window_first_tick, "ticks": steps,
+                                       "note": None if whole else "`value` is the rate of a window shorter than (or not a multiple "
+                                       "of) an episode; quote `value_episode_average` next to roofline.frac"}
+            if not args.no_cpu_baseline and args.workload == "tag_continuous" and world == 1:  # N = 1 only
+                try:
+                    out["cpu_baseline"] = cpu_baseline({k: v for k, v in cfg.items()})
+                except Exception as err:  # the baseline is reported context, never a reason to lose the GPU number
+                    out["cpu_baseline"] = {"value": None, "unit": "env_steps/s", "cores": os.cpu_count(),
+                                           "kind": "port", "sample": f"failed: {err}"}
+
+    # BASELINE configs[3] is a TRAINING configuration (PPO + the gradient all-reduce over RCCL): with --full at N > 1 the line
+    # also carries one training iteration timed from the inside, on every rank (collectives inside: all ranks take part).
     # The kernel line above is the contract and is complete by now: whatever the trainer leg does -- an exception (reported
     # in the line; the ranks agree on it before they enter a collective, training/bench_iteration.py), or a rank that dies
     # or hangs inside a collective (nobody can be called back from there) -- the line is printed and the job ends: a
     # watchdog on every rank prints it (rank 0) and leaves after --trainer-timeout seconds.
-    if is_tc and (args.trainer_leg == "on" or (args.trainer_leg == "auto" and world > 1)):
+    if is_tc and (args.trainer_leg == "on" or (args.trainer_leg == "auto" and args.full and world > 1)):
         import threading
 
         from warp_drive_amd.training.bench_iteration import run_configs3_iteration

@@ -25,7 +25,7 @@ for _ in range(rounds):
         if os.path.exists(os.path.join(vdir, "env")):  # KEY=VALUE lines: host-side switches that belong to the variant
             env.update(dict(line.strip().split("=", 1) for line in open(os.path.join(vdir, "env")) if "=" in line))
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1000", "--warmup", "100",
-                              "--no-cpu-baseline", "--no-spread"] + extra, capture_output=True, text=True, env=env)
+                              "--no-cpu-baseline", "--no-spread", "--full"] + extra, capture_output=True, text=True, env=env)
         try:
             d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
             res[n].append((d["ms_per_step"] * 1e3, d["roofline"]["avg_kernel_us"], d["roofline"].get("full_load_us") or 0.0))

@@ -11,18 +11,18 @@ timeout 400 bash scripts/collect_profiles.sh $TAG 2000 16000 > /dev/null 2>&1
 # 2. instruction mix / SQ counters at the headline size
 timeout 300 bash scripts/pmc_mix_tc.sh $TAG 2000 > /dev/null 2>&1
 # 3. plain bench lines: default (with the CPU baseline), the driver's shape, the worst case (nobody is ever tagged)
-timeout 120 python bench.py > $O/${TAG}_bench_default.json 2>/dev/null
+timeout 120 python bench.py --full > $O/${TAG}_bench_default.json 2>/dev/null
 timeout 120 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_driver_shape.json 2>/dev/null
-timeout 120 python bench.py --no-tags --steps 1000 --warmup 100 --no-cpu-baseline > $O/${TAG}_bench_notags.json 2>/dev/null
-timeout 120 python bench.py --full-obs --no-cpu-baseline --steps 500 --warmup 50 > $O/${TAG}_bench_fullobs.json 2>/dev/null
+timeout 120 python bench.py --full --no-tags --steps 1000 --warmup 100 --no-cpu-baseline > $O/${TAG}_bench_notags.json 2>/dev/null
+timeout 120 python bench.py --full --full-obs --no-cpu-baseline --steps 500 --warmup 50 > $O/${TAG}_bench_fullobs.json 2>/dev/null
 # 4. big replicas (the episode-average rate is in the line: value_episode_average)
-timeout 200 python bench.py --num-runners 1000 --steps 100 --warmup 10 --no-cpu-baseline --no-spread > $O/${TAG}_bench_tc_1005agents.json 2>/dev/null
-timeout 200 python bench.py --num-runners 500 --steps 500 --warmup 50 --no-cpu-baseline --no-spread > $O/${TAG}_bench_tc_505agents.json 2>/dev/null
+timeout 200 python bench.py --full --num-runners 1000 --steps 100 --warmup 10 --no-cpu-baseline --no-spread > $O/${TAG}_bench_tc_1005agents.json 2>/dev/null
+timeout 200 python bench.py --full --num-runners 500 --steps 500 --warmup 50 --no-cpu-baseline --no-spread > $O/${TAG}_bench_tc_505agents.json 2>/dev/null
 # 5. side workloads
-for t in 1 50; do timeout 100 python bench.py --workload cartpole --ticks-per-launch $t --no-cpu-baseline > $O/${TAG}_bench_cartpole_T$t.json 2>/dev/null; done
-timeout 100 python bench.py --workload tag_gridworld --no-cpu-baseline > $O/${TAG}_bench_gridworld_E1000.json 2>/dev/null
-for t in 50 200; do timeout 100 python bench.py --workload tag_gridworld --ticks-per-launch $t --no-cpu-baseline --steps 500 --warmup 50 > $O/${TAG}_bench_gridworld_E1000_T$t.json 2>/dev/null; done
-timeout 100 python bench.py --workload tag_gridworld --num-envs 100000 --ticks-per-launch 50 --no-cpu-baseline --steps 100 --warmup 10 > $O/${TAG}_bench_gridworld_E100000_T50.json 2>/dev/null
+for t in 1 50; do timeout 100 python bench.py --full --workload cartpole --ticks-per-launch $t --no-cpu-baseline > $O/${TAG}_bench_cartpole_T$t.json 2>/dev/null; done
+timeout 100 python bench.py --full --workload tag_gridworld --no-cpu-baseline > $O/${TAG}_bench_gridworld_E1000.json 2>/dev/null
+for t in 50 200; do timeout 100 python bench.py --full --workload tag_gridworld --ticks-per-launch $t --no-cpu-baseline --steps 500 --warmup 50 > $O/${TAG}_bench_gridworld_E1000_T$t.json 2>/dev/null; done
+timeout 100 python bench.py --full --workload tag_gridworld --num-envs 100000 --ticks-per-launch 50 --no-cpu-baseline --steps 100 --warmup 10 > $O/${TAG}_bench_gridworld_E100000_T50.json 2>/dev/null
 # 6. the tick along an episode
 timeout 120 python scripts/episode_profile.py > $O/${TAG}_episode_profile.txt 2>&1
 # 7. trainer: rollout + iteration at configs[2]; TagGridWorld / Cartpole rollouts with the policies inside the kernel

@@ -13,20 +13,20 @@ S=$O/${TAG}_side_workloads.txt
 cd /tmp && export TMPDIR=/tmp
 run() {
   name=$1; shift
-  python $R/bench.py --no-cpu-baseline "$@" > $O/${TAG}_bench_$name.json 2>/dev/null
-  echo "## $name: python bench.py --no-cpu-baseline $*" >> $S
+  python $R/bench.py --full --no-cpu-baseline "$@" > $O/${TAG}_bench_$name.json 2>/dev/null
+  echo "## $name: python bench.py --full --no-cpu-baseline $*" >> $S
   python -c "
 import json
 d=[json.loads(l) for l in open('$O/${TAG}_bench_$name.json') if l.startswith('{')][-1]
 r=d['roofline']
 print('plain run: value=%.4g %s, ms_per_step=%.5f (spread %.5f..%.5f), %s avg %.2f us, algorithmic %.4g B/launch, achieved %.0f GB/s, frac %.3f' % (d['value'], d['unit'], d['ms_per_step'], d['ms_per_step_spread']['min'], d['ms_per_step_spread']['max'], r['kernel'], r['avg_kernel_us'], r['algorithmic_bytes_per_launch'], r['achieved'], r['frac']))" >> $S
   d=/tmp/prof_side; rm -rf $d
-  rocprofv3 --kernel-trace --stats -d $d -o kt -- python $R/bench.py --no-cpu-baseline --no-spread "$@" > /dev/null 2>&1
+  rocprofv3 --kernel-trace --stats -d $d -o kt -- python $R/bench.py --full --no-cpu-baseline --no-spread "$@" > /dev/null 2>&1
   echo "rocprofv3 --kernel-trace --stats (same command + --no-spread):" >> $S
   python $R/scripts/rocpd_summary.py kernel $(find $d -name "*.db" | head -1) | head -4 >> $S
   for c in FETCH_SIZE WRITE_SIZE; do
     d=/tmp/prof_side_$c; rm -rf $d
-    rocprofv3 --kernel-trace --pmc $c -d $d -o pmc -- python $R/bench.py --no-cpu-baseline --no-spread "$@" --steps 40 --warmup 10 > /dev/null 2>&1
+    rocprofv3 --kernel-trace --pmc $c -d $d -o pmc -- python $R/bench.py --full --no-cpu-baseline --no-spread "$@" --steps 40 --warmup 10 > /dev/null 2>&1
     python $R/scripts/rocpd_summary.py pmc $(find $d -name "*.db" | head -1) $c | python -c "
 import json,sys
 rows=[r for r in json.load(sys.stdin) if r['kernel'].startswith('Hip')]

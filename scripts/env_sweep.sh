@@ -4,7 +4,7 @@
 # usage: scripts/env_sweep.sh [num_envs ...] > gpurun_out/profiles/<tag>_env_sweep.txt
 cd "$(dirname "$0")/.."
 for E in ${@:-500 1000 1500 2000 3000 4000 8000 16000}; do
-  python bench.py --steps 1000 --warmup 100 --no-cpu-baseline --num-envs $E 2>/dev/null | python -c "
+  python bench.py --full --steps 1000 --warmup 100 --no-cpu-baseline --num-envs $E 2>/dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 r = d['roofline']

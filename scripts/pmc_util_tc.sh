@@ -10,7 +10,7 @@ for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY" \
            "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_IFETCH SQ_INSTS_VALU_TRANS_F32" \
            "SQ_THREAD_CYCLES_VALU SQ_INSTS_VALU_INT32 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64"; do
   d=/tmp/pmc_util; rm -rf $d
-  rocprofv3 --kernel-trace --pmc $grp -d $d -o pmc -- python $R/bench.py --steps 30 --warmup 5 --no-cpu-baseline > /dev/null 2>&1
+  rocprofv3 --kernel-trace --pmc $grp -d $d -o pmc -- python $R/bench.py --full --steps 30 --warmup 5 --no-cpu-baseline > /dev/null 2>&1
   db=$(find $d -name "*.db" | head -1)
   for c in $grp; do
     python $R/scripts/rocpd_summary.py pmc $db $c | python -c "

@@ -27,7 +27,7 @@ def _env():
 
 def _bench(extra):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5",
-                          "--num-envs", "500", "--no-cpu-baseline"] + extra,
+                          "--num-envs", "500", "--no-cpu-baseline", "--full"] + extra,
                          capture_output=True, text=True, env=_env(), cwd=ROOT, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -67,7 +67,7 @@ def test_bench_line_carries_the_configs3_trainer_iteration():
     assert "failed" not in one, one
     assert one["algorithm"] == ["PPO"] and one["collectives_per_iteration"] == 0 and one["allreduce_us"] is None
     assert one["env_steps_per_iteration_all_ranks"] == 60 * 12 and one["gradient_bucket_bytes"] == 762200
-    two = _bench(["--gpus", "2"] + small)   # auto: on at N > 1
+    two = _bench(["--gpus", "2"] + small)   # auto: on at N > 1 with --full
     t = two["trainer"]
     assert "failed" not in t, t
     assert t["collectives_per_iteration"] == 1 and t["allreduce_us"] > 0 and len(t["allreduce_us_per_rank"]) == 2
@@ -174,7 +174,7 @@ def test_two_ranks_over_rccl_when_the_box_has_two_gpus(tmp_path):
         env.pop(k, None)
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
-                          "--no-cpu-baseline"], capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
+                          "--no-cpu-baseline", "--full"], capture_output=True, text=True, env=env, cwd=ROOT, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 2 and len(d["per_rank_ms_per_step"]) == 2 and d["allreduce_us"] > 0
