@@ -97,6 +97,18 @@ int wd_plan_add(void *plan, void *function, uint32_t grid_x, uint32_t grid_y, ui
 int wd_plan_size(void *plan, int *n_launches);
 /* enqueue the whole plan `repeats` times on `stream` (plain launches) */
 int wd_plan_run(void *plan, int repeats, void *stream);
+/* replica cohorts: entry `entry_index` restricted to cohort `cohort`'s replicas (0 <= cohort < 4).  Once cohorts
+ * 0 .. C-1 (C >= 2) are set for every entry, wd_plan_run with repeats >= 2 forks: cohort 0 runs on `stream`, cohort c
+ * on a plan-owned non-blocking stream that waits on an event recorded on `stream`; each cohort runs all `repeats`
+ * repetitions of its launches, and `stream` then waits on every side stream (work enqueued on `stream` afterwards
+ * is ordered after every cohort).  repeats == 1 and the graph calls below run the whole-range entries on `stream`.
+ * Cohorts must be added before the plan's first cohort run. */
+int wd_plan_add_cohort(void *plan, int entry_index, int cohort, void *function, uint32_t grid_x,
+                       uint32_t grid_y, uint32_t grid_z, uint32_t block_x, uint32_t block_y,
+                       uint32_t block_z, uint32_t shared_mem_bytes, const void *arg_buffer,
+                       size_t arg_bytes);
+/* number of cohorts a multi-repetition wd_plan_run uses (1 = no cohorts) */
+int wd_plan_cohorts(void *plan, int *n_cohorts);
 /* capture `repeats_per_graph` repetitions into a hipGraph once, then replay it */
 int wd_plan_instantiate_graph(void *plan, int repeats_per_graph, void *stream);
 int wd_plan_run_graph(void *plan, int graph_launches, void *stream);
@@ -105,6 +117,7 @@ int wd_plan_run_graph(void *plan, int graph_launches, void *stream);
  * (at most max_samples pairs are kept; -1 disables).  A plan that consists of one launch is
  * bracketed over min(sample_stride, 8) consecutive repetitions per event pair, so the event
  * cost is amortised and the result is the average launch duration of back-to-back launches.
+ * With cohorts, every multi-repetition run is bracketed as a whole on `stream` (fork to join).
  * wd_plan_read_timing synchronises the recorded events and returns the summed milliseconds
  * and the number of launches they cover. */
 int wd_plan_enable_timing(void *plan, int entry_index, int sample_stride, int max_samples);

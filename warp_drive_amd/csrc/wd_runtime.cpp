@@ -60,6 +60,10 @@ void set_err(const char *fmt, ...) {
     hipError_t (*)(hipFunction_t, unsigned int, unsigned int, unsigned int, unsigned int,      \
                    unsigned int, unsigned int, unsigned int, hipStream_t, void **, void **))   \
   X(hipStreamSynchronize, hipError_t (*)(hipStream_t))                                         \
+  X(hipStreamCreateWithFlags, hipError_t (*)(hipStream_t *, unsigned int))                     \
+  X(hipStreamDestroy, hipError_t (*)(hipStream_t))                                             \
+  X(hipStreamWaitEvent, hipError_t (*)(hipStream_t, hipEvent_t, unsigned int))                 \
+  X(hipEventCreateWithFlags, hipError_t (*)(hipEvent_t *, unsigned int))                       \
   X(hipDeviceSynchronize, hipError_t (*)(void))                                                \
   X(hipEventCreate, hipError_t (*)(hipEvent_t *))                                              \
   X(hipEventRecord, hipError_t (*)(hipEvent_t, hipStream_t))                                   \
@@ -128,10 +132,12 @@ inline int check(hipError_t e, const char *what) {
   } while (0)
 
 struct PlanEntry {
-  hipFunction_t fn;
+  hipFunction_t fn = nullptr;
   uint32_t g[3], b[3], shmem;
   std::vector<unsigned char> args;
 };
+
+constexpr int kMaxCohorts = 4;  // caller's stream + 3 side streams: within the default 4 hardware queues
 
 struct Plan {
   std::vector<PlanEntry> entries;
@@ -141,8 +147,15 @@ struct Plan {
   int timed_entry = -1, stride = 1, max_samples = 0, used = 0;
   int group = 1;      // launches bracketed by one event pair (> 1 only for single-launch plans)
   bool open = false;  // a start event was recorded, its end event not yet
+  int pending = 0;    // launches of the timed entry inside the open bracket
   long run_counter = 0;
-  std::vector<hipEvent_t> ev;  // 2 * max_samples
+  std::vector<hipEvent_t> ev;     // 2 * max_samples
+  std::vector<int> launches;      // per closed bracket: launches of the timed entry it covers
+  // replica cohorts (wd_plan_add_cohort): cohorts[c][i] is entry i restricted to cohort c's replicas
+  std::vector<std::vector<PlanEntry>> cohorts;
+  std::vector<hipStream_t> side;     // cohorts 1 .. C-1 (created on first use)
+  hipEvent_t fork = nullptr;
+  std::vector<hipEvent_t> join;      // one per side stream
 };
 
 int launch_packed(hipFunction_t fn, const uint32_t g[3], const uint32_t b[3], uint32_t shmem,
@@ -343,11 +356,12 @@ int wd_plan_size(void *plan, int *n) {
   *n = static_cast<int>(static_cast<Plan *>(plan)->entries.size());
   return 0;
 }
-int wd_plan_run(void *plan, int repeats, void *stream) {
-  WD_REQUIRE_RT();
-  if (!plan) return WD_ERR_BAD_ARG;
-  Plan *p = static_cast<Plan *>(plan);
-  hipStream_t s = static_cast<hipStream_t>(stream);
+}  // extern "C"
+
+namespace {
+
+// the plan's launches `repeats` times, in order, on one stream
+int plan_run_single(Plan *p, int repeats, hipStream_t s) {
   for (int r = 0; r < repeats; ++r, ++p->run_counter) {
     // A plan of ONE launch is timed over `group` consecutive repetitions per event pair: back-to-back
     // launches leave no gap, so elapsed / group is the kernel's average launch duration as a profiler
@@ -362,14 +376,120 @@ int wd_plan_run(void *plan, int repeats, void *stream) {
         p->open = true;
       }
       if (int rc = launch_packed(e.fn, e.g, e.b, e.shmem, s, e.args.data(), e.args.size())) return rc;
+      if (timed && p->open) ++p->pending;
       if (timed && p->open && phase == p->group - 1) {
         if (int rc = check(g_hip.hipEventRecord(p->ev[2 * p->used + 1], s), "hipEventRecord")) return rc;
+        p->launches.push_back(p->pending);
+        p->pending = 0;
         p->open = false;
         ++p->used;
       }
     }
   }
   return 0;
+}
+
+bool cohorts_complete(const Plan *p) {
+  if (p->cohorts.size() < 2) return false;
+  for (auto &c : p->cohorts) {
+    if (c.size() != p->entries.size()) return false;
+    for (auto &e : c)
+      if (!e.fn) return false;
+  }
+  return true;
+}
+
+// The cohorts' launches `repeats` times each, cohort c on its own stream: cohort 0 on `s`, cohorts 1.. on plan-owned
+// non-blocking streams forked from `s` by an event and joined back into it, so whatever the caller enqueues on `s`
+// afterwards is ordered after every cohort.
+int plan_run_cohorts(Plan *p, int repeats, hipStream_t s) {
+  const int C = static_cast<int>(p->cohorts.size());
+  if (p->side.empty()) {
+    if (int rc = check(g_hip.hipEventCreateWithFlags(&p->fork, hipEventDisableTiming), "hipEventCreateWithFlags"))
+      return rc;
+    for (int c = 1; c < C; ++c) {
+      hipStream_t st = nullptr;
+      hipEvent_t ej = nullptr;
+      if (int rc = check(g_hip.hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreateWithFlags"))
+        return rc;
+      p->side.push_back(st);
+      if (int rc = check(g_hip.hipEventCreateWithFlags(&ej, hipEventDisableTiming), "hipEventCreateWithFlags"))
+        return rc;
+      p->join.push_back(ej);
+    }
+  }
+  // timing: one bracket on the caller's stream around the whole group of cohorts (every tick of the timed entry)
+  const bool timed = p->timed_entry >= 0 && (p->open || p->used < p->max_samples);
+  if (timed && !p->open) {
+    if (int rc = check(g_hip.hipEventRecord(p->ev[2 * p->used], s), "hipEventRecord")) return rc;
+    p->open = true;
+  }
+  if (int rc = check(g_hip.hipEventRecord(p->fork, s), "hipEventRecord(fork)")) return rc;
+  for (int c = 1; c < C; ++c)
+    if (int rc = check(g_hip.hipStreamWaitEvent(p->side[c - 1], p->fork, 0), "hipStreamWaitEvent(fork)")) return rc;
+  // tick-major: the host enqueues tick r of every cohort before tick r + 1 of any (enqueuing one cohort's ticks
+  // after the other's would leave the later cohorts waiting for the host while the first one runs alone)
+  for (int r = 0; r < repeats; ++r)
+    for (int c = 0; c < C; ++c) {
+      hipStream_t st = c == 0 ? s : p->side[c - 1];
+      for (auto &e : p->cohorts[c])
+        if (int rc = launch_packed(e.fn, e.g, e.b, e.shmem, st, e.args.data(), e.args.size())) return rc;
+    }
+  for (int c = 1; c < C; ++c) {
+    if (int rc = check(g_hip.hipEventRecord(p->join[c - 1], p->side[c - 1]), "hipEventRecord(join)")) return rc;
+    if (int rc = check(g_hip.hipStreamWaitEvent(s, p->join[c - 1], 0), "hipStreamWaitEvent(join)")) return rc;
+  }
+  p->run_counter += repeats;
+  if (timed) {
+    p->pending += repeats;
+    if (int rc = check(g_hip.hipEventRecord(p->ev[2 * p->used + 1], s), "hipEventRecord")) return rc;
+    p->launches.push_back(p->pending);
+    p->pending = 0;
+    p->open = false;
+    ++p->used;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int wd_plan_add_cohort(void *plan, int entry_index, int cohort, void *function, uint32_t gx, uint32_t gy,
+                       uint32_t gz, uint32_t bx, uint32_t by, uint32_t bz, uint32_t shmem, const void *buf,
+                       size_t bytes) {
+  Plan *p = static_cast<Plan *>(plan);
+  if (!p || !function || entry_index < 0 || entry_index >= static_cast<int>(p->entries.size()) || cohort < 0 ||
+      cohort >= kMaxCohorts || !p->side.empty()) {
+    set_err("wd_plan_add_cohort: bad entry %d / cohort %d (at most %d cohorts, before the first run)", entry_index,
+            cohort, kMaxCohorts);
+    return WD_ERR_BAD_ARG;
+  }
+  if (static_cast<int>(p->cohorts.size()) <= cohort) p->cohorts.resize(cohort + 1);
+  auto &c = p->cohorts[cohort];
+  if (c.size() < p->entries.size()) c.resize(p->entries.size());
+  PlanEntry &e = c[entry_index];
+  e.fn = static_cast<hipFunction_t>(function);
+  e.g[0] = gx; e.g[1] = gy; e.g[2] = gz;
+  e.b[0] = bx; e.b[1] = by; e.b[2] = bz;
+  e.shmem = shmem;
+  e.args.assign(static_cast<const unsigned char *>(buf), static_cast<const unsigned char *>(buf) + bytes);
+  return 0;
+}
+int wd_plan_cohorts(void *plan, int *n) {
+  if (!plan || !n) return WD_ERR_BAD_ARG;
+  Plan *p = static_cast<Plan *>(plan);
+  *n = cohorts_complete(p) ? static_cast<int>(p->cohorts.size()) : 1;
+  return 0;
+}
+int wd_plan_run(void *plan, int repeats, void *stream) {
+  WD_REQUIRE_RT();
+  if (!plan) return WD_ERR_BAD_ARG;
+  Plan *p = static_cast<Plan *>(plan);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // one tick: the whole-range entries (no fork / join events for callers that run tick by tick)
+  if (repeats >= 2 && cohorts_complete(p)) return plan_run_cohorts(p, repeats, s);
+  return plan_run_single(p, repeats, s);
 }
 int wd_plan_enable_timing(void *plan, int entry_index, int sample_stride, int max_samples) {
   WD_REQUIRE_RT();
@@ -381,6 +501,8 @@ int wd_plan_enable_timing(void *plan, int entry_index, int sample_stride, int ma
   p->run_counter = 0;
   p->timed_entry = -1;
   p->open = false;
+  p->pending = 0;
+  p->launches.clear();
   p->group = 1;
   if (entry_index < 0) return 0;
   if (entry_index >= static_cast<int>(p->entries.size()) || sample_stride < 1 || max_samples < 1)
@@ -410,9 +532,13 @@ int wd_plan_read_timing(void *plan, float *total_ms, int *n_samples) {
     total += ms;
   }
   *total_ms = total;
-  *n_samples = p->used * p->group;  // launches covered by the summed time
+  int n = 0;
+  for (int k : p->launches) n += k;
+  *n_samples = n;  // launches covered by the summed time
   p->used = 0;
   p->open = false;
+  p->pending = 0;
+  p->launches.clear();
   return 0;
 }
 int wd_plan_instantiate_graph(void *plan, int reps, void *stream) {
@@ -424,7 +550,7 @@ int wd_plan_instantiate_graph(void *plan, int reps, void *stream) {
   if (int rc = check(g_hip.hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal),
                      "hipStreamBeginCapture"))
     return rc;
-  int rc = wd_plan_run(plan, reps, stream);
+  int rc = plan_run_single(p, reps, s);  // the whole-range entries on one stream: no cohorts in a graph
   hipGraph_t graph = nullptr;
   int rc2 = check(g_hip.hipStreamEndCapture(s, &graph), "hipStreamEndCapture");
   if (rc) return rc;
@@ -447,8 +573,12 @@ int wd_plan_destroy(void *plan) {
   Plan *p = static_cast<Plan *>(plan);
   if (!p) return 0;
   if (p->exec && g_hip.ready) (void)g_hip.hipGraphExecDestroy(p->exec);
-  if (g_hip.ready)
+  if (g_hip.ready) {
     for (auto e : p->ev) (void)g_hip.hipEventDestroy(e);
+    for (auto st : p->side) (void)g_hip.hipStreamDestroy(st);
+    for (auto e : p->join) (void)g_hip.hipEventDestroy(e);
+    if (p->fork) (void)g_hip.hipEventDestroy(p->fork);
+  }
   delete p;
   return 0;
 }

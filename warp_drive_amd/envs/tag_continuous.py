@@ -435,6 +435,8 @@ class TagContinuous(CUDAEnvironmentContext):
         name = self.cuda_step.name.replace("Step", "TickA")
         return self._fast_path() and self.cuda_function_manager.has_function(name)
 
+    TICK_ENV_RANGES = True  # tick_launch(env_range=) restricts the tick to a replica range (rollout cohorts)
+
     def tick_launch(self, sampler, probabilities, resetter, env_range=None):
         """Fused rollout tick: sample both action heads + step + reset finished replicas in ONE
         launch (HipTagContinuousTick[_K<k>]).  probabilities = [acceleration, turn] float32 CUDA

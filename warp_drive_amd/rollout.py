@@ -14,6 +14,8 @@ fixed LaunchPlan replayed from C (or captured once into a hipGraph):
 The probability tensors the sampler reads are whatever the policy wrote last (torch
 tensors aliased in place); for kernel-only throughput they are constant uniform tensors.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -29,6 +31,21 @@ class UnsupportedRolloutShape(RuntimeError):
     """an env's tick entry was asked for a variant (live in-kernel policy, presampled actions, ...) that does not exist
     for this env shape -- a capability answer, raised explicitly (never an `assert`: it must survive `python -O` and must
     not be confused with an assertion that caught a bug)"""
+
+
+# Replica cohorts of the fused tick (TagContinuous): a multi-tick run() splits the replicas into C ranges, each
+# replayed on its own stream (LaunchPlan.add_cohort, wd_runtime.cpp), so one cohort's fetch, row flush, drain and
+# kernel boundary run under the other cohort's work.  Measured at 2000 replicas (interleaved A/B medians): C = 1 24.4 us
+# per tick, C = 2 21.9, C = 3 22.6 (docs/rounds/r07.md).  1 = one whole-range launch per tick.
+TICK_COHORTS = int(os.environ.get("WD_TICK_COHORTS", "2"))
+COHORT_ALIGN = 32  # cohort boundaries at multiples of 32 replicas: 32 rows of 4 * N bytes are N whole 128-byte lines
+
+
+def cohort_bounds(n_envs, cohorts):
+    """replica ranges [(begin, end), ...] of `cohorts` near-equal cohorts whose inner boundaries are multiples of
+    COHORT_ALIGN replicas"""
+    cuts = [0] + [int(round(n_envs * c / cohorts / COHORT_ALIGN)) * COHORT_ALIGN for c in range(1, cohorts)] + [n_envs]
+    return list(zip(cuts[:-1], cuts[1:]))
 
 
 class RolloutEngine:
@@ -79,6 +96,7 @@ class RolloutEngine:
         actions = dm.device_data(_ACTIONS)  # [E, N, H] int32 (H = 1 for Discrete)
         H = len(head_sizes)
         self.entry_names = []
+        self.cohorts = 1  # replica cohorts a multi-tick run() replays in parallel (one kernel per cohort and tick)
         self._graph_ticks = 0
         # an env class that offers tick_launch() fuses sampling, step and reset in its own kernel
         # (restarts from a reset pool draw random members: that stays with the pool reset kernel)
@@ -107,6 +125,9 @@ class RolloutEngine:
             self.step_entry = 0
             self.step_kernel_name = fn.name
             self.entry_names.append(fn.name)
+            if (not self.presampled and rollout_policy is None and rollout_batch is None and self.ticks_per_launch == 1
+                    and getattr(env_wrapper.env, "TICK_ENV_RANGES", False)):
+                self._add_cohorts(env_wrapper, sampler, probabilities, E, grid[0], dev)
             return
         assert not self.presampled, "presampled_actions needs the env's fused tick entry"
         for k, (p, a) in enumerate(zip(probabilities, head_sizes)):
@@ -124,8 +145,25 @@ class RolloutEngine:
             self.plan.add(fn, args, block, grid, 0)
             self.entry_names.append(fn.name)
 
+    def _add_cohorts(self, env_wrapper, sampler, probabilities, E, blocks, dev):
+        """split the fused tick into replica cohorts when every cohort still covers at least half of the CUs"""
+        C = min(4, TICK_COHORTS)  # caller's stream + side streams within the default 4 hardware queues
+        if C < 2:
+            return
+        half_cus = torch.cuda.get_device_properties(dev).multi_processor_count // 2
+        bounds = cohort_bounds(E, C)
+        epb = max(1, -(-E // blocks))  # replicas per block
+        if any(-(-(e - b) // epb) < half_cus for b, e in bounds):
+            return
+        env = env_wrapper.env
+        for c, rng in enumerate(bounds):
+            fn, args, block, grid, shared = env.tick_launch(sampler, probabilities, env_wrapper.env_resetter, env_range=rng)
+            self.plan.add_cohort(0, c, fn, args, block, grid, shared)
+        self.cohorts = self.plan.cohorts
+
     def run(self, ticks, stream=None):
-        """Enqueue `ticks` rollout ticks (asynchronous)."""
+        """Enqueue `ticks` rollout ticks (asynchronous).  With cohorts, ticks >= 2 fork the cohorts onto their own
+        streams and join them back into `stream` before returning."""
         self.plan.run(ticks, stream)
 
     def run_graph(self, ticks, ticks_per_graph=10, stream=None):
