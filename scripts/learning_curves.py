@@ -3,7 +3,7 @@
 configurations (the numbers tests/test_gpu_learning.py's thresholds were chosen from; reference README.md:60 shows the
 Cartpole curve of the reference trainer).
 
-    python scripts/learning_curves.py [--which cartpole_kernel cartpole_tick gridworld_kernel gridworld_tick] [--iters N]
+    python scripts/learning_curves.py [--which cartpole_kernel cartpole_tick gridworld_kernel gridworld_tick acrobot] [--iters N]
 """
 import argparse
 import json
@@ -30,6 +30,10 @@ CONFIGS = {
                                                                                                "model_ckpt_filepath": ""}}
                                                       for p in ("runner", "tagger")}}, "tagger"),
     "gridworld_tick": ("tag_gridworld", {"trainer": {"num_envs": 600, "train_batch_size": 600 * 100, "num_episodes": 10 ** 6, "seed": 7}}, "tagger"),
+    # Acrobot pays -1 per tick until the tip swings above the bar: the mean episodic reward is minus the mean episode
+    # length (-200 = never; restarts drawn from the config's reset pool)
+    "acrobot": ("single_acrobot", {"trainer": {"num_envs": 1000, "train_batch_size": 1000 * 50, "num_episodes": 10 ** 6, "seed": 7},
+                                   "env": {"episode_length": 200}}, "shared"),
     # the taggers learn against a runner that stays the random initial policy: their episodic reward can only rise
     "gridworld_kernel_frozen_runner": ("tag_gridworld", {
         "trainer": {"num_envs": 600, "train_batch_size": 600 * 100, "num_episodes": 10 ** 6, "seed": 7},

@@ -54,6 +54,8 @@ UNITS = {
     "wd_kernels_mlp.hsaco": ("policy_mlp.hip", ["-DWD_MLP_PART=1"]),
     "wd_kernels_update.hsaco": ("policy_mlp.hip", ["-DWD_MLP_PART=2"]),
     "wd_kernels_gw5.hsaco": ("tag_gridworld_n5.hip", []),
+    # ClassicControl Acrobot, MountainCar, ContinuousMountainCar, Pendulum: step + fused tick of each
+    "wd_kernels_cc.hsaco": ("classic_control.hip", []),
     "wd_kernels_test.hsaco": ("wd_test_kernels.hip", []),
 }
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")

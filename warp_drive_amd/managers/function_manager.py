@@ -457,12 +457,18 @@ class HIPSampler(CUDASampler):
             fn(*args, block=block, grid=grid, shared=shared)
         else:
             # deterministic (continuous) action + OU noise, numba_function_manager.py:348-364
-            self.sample_ou_process(
-                self._rng_state, distribution, data_manager.device_data(action_name),
-                data_manager.device_data(f"{action_name}_ou_state"),
-                np.float32(sample_params.get("damping", 0.15)), np.float32(sample_params.get("stddev", 0.2)),
-                np.float32(sample_params.get("scale", 1.0)), np.int32(n_rows), _stream_tag(action_name),
-                block=(256, 1, 1), grid=(max(1, min(4096, (n_rows + 255) // 256)), 1))
+            fn, args, block, grid, shared = self.ou_launch(
+                data_manager, distribution, action_name, n_rows, sample_params.get("damping", 0.15),
+                sample_params.get("stddev", 0.2), sample_params.get("scale", 1.0), _stream_tag(action_name))
+            fn(*args, block=block, grid=grid, shared=shared)
+
+    def ou_launch(self, data_manager, distribution, action_name, n_rows, damping, stddev, scale, tag):
+        """(function, args, block, grid, shared) of one OU / Gaussian draw into `action_name` (its `_ou_state`
+        updated); shared with the rollout launch plan."""
+        args = (self._rng_state, distribution, data_manager.device_data(action_name),
+                data_manager.device_data(f"{action_name}_ou_state"), np.float32(damping), np.float32(stddev),
+                np.float32(scale), np.int32(n_rows), tag)
+        return self.sample_ou_process, args, (256, 1, 1), (max(1, min(4096, (n_rows + 255) // 256)), 1), 0
 
     @staticmethod
     def assign(data_manager, actions: np.ndarray, action_name: str):
@@ -587,28 +593,43 @@ class HIPEnvironmentReset(CUDAEnvironmentReset):
         self._random_initialized = True
 
     def reset_when_done_from_pool(self, data_manager, force_reset):
+        for fn, args, block, grid in self.pool_launches(data_manager, force_reset):
+            fn(*args, block=block, grid=grid)
+
+    def pool_launches(self, data_manager, force_reset):
+        """[(function, args, block, grid), ...] of the reset from the pools (one launch per pooled array); shared with
+        the rollout launch plan."""
         pools = data_manager.reset_target_to_pool
         if len(pools) == 0:
-            return
+            return []
         assert self._random_initialized, (
             "reset_when_done_from_pool() requires the random seed initialized first, please call init_reset_pool()")
         block, grid = self._geometry()
         items = list(pools.items())
+        launches = []
         for i, (name, pool_name) in enumerate(items):
             p_shape = data_manager.get_shape(pool_name)
             assert p_shape[0] > 1, "reset function assumes the 0th dimension is n_pool"
             row = int(np.prod(p_shape[1:])) if len(p_shape) > 1 else 1
             # every array of one reset call draws the same pool row per replica; the epoch
             # advances with the last array only
-            self.reset_from_pool(self._pool_rng, data_manager.device_data(name), data_manager.device_data(pool_name),
-                                 data_manager.device_data("_done_"), np.int32(row), np.int32(p_shape[0]),
-                                 np.int32(force_reset), data_manager.meta_info("n_envs"),
-                                 np.int32(1 if i == len(items) - 1 else 0), block=block, grid=grid)
+            launches.append((self.reset_from_pool,
+                             (self._pool_rng, data_manager.device_data(name), data_manager.device_data(pool_name),
+                              data_manager.device_data("_done_"), np.int32(row), np.int32(p_shape[0]),
+                              np.int32(force_reset), data_manager.meta_info("n_envs"),
+                              np.int32(1 if i == len(items) - 1 else 0)), block, grid))
+        return launches
+
+    def undo_launch(self, data_manager, force_reset):
+        """(function, args, block, grid) of undo_done_flag_and_reset_timestep"""
+        n = self._num_envs
+        return (self.undo, (data_manager.device_data("_done_"), data_manager.device_data("_timestep_"),
+                            np.int32(force_reset), data_manager.meta_info("n_envs")),
+                (256, 1, 1), (max(1, min(4096, (n + 255) // 256)), 1))
 
     def _undo_done_flag_and_reset_timestep(self, data_manager, force_reset):
-        n = self._num_envs
-        self.undo(data_manager.device_data("_done_"), data_manager.device_data("_timestep_"), np.int32(force_reset),
-                  data_manager.meta_info("n_envs"), block=(256, 1, 1), grid=(max(1, min(4096, (n + 255) // 256)), 1))
+        fn, args, block, grid = self.undo_launch(data_manager, force_reset)
+        fn(*args, block=block, grid=grid)
 
     def __del__(self):
         for p in [getattr(self, "_table", None), getattr(self, "_pool_rng", None)] + list(

@@ -22,7 +22,7 @@ import torch
 from warp_drive_amd.managers import hip_driver as drv
 from warp_drive_amd.managers.function_manager import HIPSampler, _stream_tag
 from warp_drive_amd.utils.constants import Constants
-from warp_drive_amd.utils.spaces import Discrete, MultiDiscrete
+from warp_drive_amd.utils.spaces import Box, Discrete, MultiDiscrete
 
 _ACTIONS = Constants.ACTIONS
 
@@ -50,7 +50,8 @@ def cohort_bounds(n_envs, cohorts):
 
 class RolloutEngine:
     def __init__(self, env_wrapper, sampler: HIPSampler, probabilities=None, reset_done=True, fused=True,
-                 rollout_batch=None, rollout_policy=None, ticks_per_launch=None, presampled_actions=False):
+                 rollout_batch=None, rollout_policy=None, ticks_per_launch=None, presampled_actions=False,
+                 damping=0.15, stddev=0.2, scale=1.0):
         """probabilities: list (one per action head) of contiguous float32 CUDA tensors
         [n_envs, n_agents, n_actions_of_head]; None = uniform.  rollout_batch: the trainer's [T, E, ...] batch
         tensors for envs whose tick kernel fuses T ticks per launch and records every tick itself
@@ -59,7 +60,12 @@ class RolloutEngine:
         (None = the env object's own `ticks_per_launch` attribute); the env object is left as it was, so another
         engine on the same wrapper is not affected.  presampled_actions: the tick does NOT draw the actions -- whoever
         runs before it (the policy forward's epilogue, training/policy_kernel.py) has written `sampled_actions` -- and
-        is the env's step + reset entry (`env.has_presampled_tick()`)."""
+        is the env's step + reset entry (`env.has_presampled_tick()`).  A one-dimensional `Box` action space: the
+        one probability tensor [n_envs, n_agents, 1] holds the means of the actions, and the draw is
+        sample_ou_process's OU / Gaussian one with `damping`, `stddev`, `scale` (HIPSampler.sample's defaults).
+        With a reset pool the reset entry restarts finished replicas from it (HIPEnvironmentReset.reset_when_done:
+        init_reset_pool() first); the fused tick does so itself for envs that say TICK_POOL_RESET."""
+        self.ou_params = (float(damping), float(stddev), float(scale))
         env = env_wrapper.env
         self.presampled = bool(presampled_actions)
         saved = getattr(env, "ticks_per_launch", 1)
@@ -78,14 +84,20 @@ class RolloutEngine:
         dm = env_wrapper.cuda_data_manager
         E, N = env_wrapper.n_envs, env_wrapper.n_agents
         space = env_wrapper.env.action_space[0]
+        self.continuous = isinstance(space, Box)
         if isinstance(space, MultiDiscrete):
             head_sizes = [int(v) for v in space.nvec]
         elif isinstance(space, Discrete):
             head_sizes = [int(space.n)]
+        elif self.continuous and len(space.shape) == 1 and int(space.shape[0]) == 1:
+            head_sizes = [1]  # one float action: the mean per replica and agent
         else:
-            raise NotImplementedError("RolloutEngine drives discrete action spaces")
+            raise NotImplementedError("RolloutEngine drives discrete action spaces and one-dimensional Box ones")
+        pools = len(dm.reset_target_to_pool) > 0
         dev = dm.data_on_device_via_torch(_ACTIONS).device
-        if probabilities is None:
+        if probabilities is None and self.continuous:
+            probabilities = [torch.zeros((E, N, 1), dtype=torch.float32, device=dev)]
+        elif probabilities is None:
             probabilities = [torch.full((E, N, a), 1.0 / a, dtype=torch.float32, device=dev) for a in head_sizes]
         assert len(probabilities) == len(head_sizes)
         for p, a in zip(probabilities, head_sizes):
@@ -99,10 +111,11 @@ class RolloutEngine:
         self.cohorts = 1  # replica cohorts a multi-tick run() replays in parallel (one kernel per cohort and tick)
         self._graph_ticks = 0
         # an env class that offers tick_launch() fuses sampling, step and reset in its own kernel
-        # (restarts from a reset pool draw random members: that stays with the pool reset kernel)
+        # (restarts from a reset pool draw random members: that stays with the pool reset kernel, unless the env's tick
+        # kernel draws them itself -- TICK_POOL_RESET)
         self.fused = bool(fused and reset_done and hasattr(env_wrapper.env, "tick_launch")
                           and H == getattr(env_wrapper.env, "TICK_HEADS", 2)
-                          and len(dm.reset_target_to_pool) == 0
+                          and (not pools or getattr(env_wrapper.env, "TICK_POOL_RESET", False))
                           and getattr(env_wrapper.env, "can_fuse_tick", lambda: True)())
         # env ticks per launch (> 1 only for envs whose fused kernel loops over ticks, fixed policy)
         self.ticks_per_launch = int(getattr(env_wrapper.env, "ticks_per_launch", 1)) if self.fused else 1
@@ -111,6 +124,8 @@ class RolloutEngine:
             extra = {"batch": rollout_batch} if rollout_batch is not None else {}
             if rollout_policy is not None:
                 extra["policy"] = rollout_policy
+            if self.continuous:
+                extra["ou_params"] = self.ou_params
             if self.presampled and not env_wrapper.env.has_presampled_tick():
                 raise UnsupportedRolloutShape("this env / shape has no step + reset entry for given actions")
             if rollout_policy is not None:
@@ -130,7 +145,12 @@ class RolloutEngine:
                 self._add_cohorts(env_wrapper, sampler, probabilities, E, grid[0], dev)
             return
         assert not self.presampled, "presampled_actions needs the env's fused tick entry"
-        for k, (p, a) in enumerate(zip(probabilities, head_sizes)):
+        if self.continuous:  # OU / Gaussian around the means, HIPSampler.sample's launch
+            fn, args, block, grid, shared = sampler.ou_launch(dm, probabilities[0], _ACTIONS, E * N, *self.ou_params,
+                                                              _stream_tag(_ACTIONS))
+            self.plan.add(fn, args, block, grid, shared)
+            self.entry_names.append("sample_ou_process")
+        for k, (p, a) in enumerate(zip([] if self.continuous else probabilities, head_sizes)):
             fn, args, block, grid, shared = sampler.categorical_launch(
                 p, actions, E * N, a, False, _stream_tag(f"{_ACTIONS}_{k}"), out_stride=H, out_offset=k)
             self.plan.add(fn, args, block, grid, shared)
@@ -140,10 +160,20 @@ class RolloutEngine:
         self.step_entry = len(self.entry_names)
         self.step_kernel_name = fn.name
         self.entry_names.append(fn.name)
-        if reset_done:
+        if reset_done and not pools:
             fn, args, block, grid = env_wrapper.env_resetter.fused_launch(dm, np.int32(0), 1)
             self.plan.add(fn, args, block, grid, 0)
             self.entry_names.append(fn.name)
+        elif reset_done:  # HIPEnvironmentReset.reset_when_done(mode="if_done"): table, pools, then done / timestep
+            resetter = env_wrapper.env_resetter
+            if not resetter._random_initialized:
+                raise RuntimeError("the env has a reset pool: call init_reset_pool() before building the rollout")
+            fn, args, block, grid = resetter.fused_launch(dm, np.int32(0), 0)
+            launches = [(fn, args, block, grid)] + resetter.pool_launches(dm, np.int32(0)) + \
+                [resetter.undo_launch(dm, np.int32(0))]
+            for fn, args, block, grid in launches:
+                self.plan.add(fn, args, block, grid, 0)
+                self.entry_names.append(fn.name)
 
     def _add_cohorts(self, env_wrapper, sampler, probabilities, E, blocks, dev):
         """split the fused tick into replica cohorts when every cohort still covers at least half of the CUs"""

@@ -20,13 +20,15 @@ import yaml
 from warp_drive_amd import distributed as wdd
 from warp_drive_amd.env_wrapper import EnvWrapper
 from warp_drive_amd.envs.cartpole import CUDAClassicControlCartPoleEnv
+from warp_drive_amd.envs.classic_control import CUDAClassicControlAcrobotEnv, CUDAClassicControlMountainCarEnv
 from warp_drive_amd.envs.tag_continuous import TagContinuous
 from warp_drive_amd.envs.tag_gridworld import CUDATagGridWorld
 from warp_drive_amd.training.trainer import Trainer
 
 _CONFIGS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "run_configs")
 _ENVS = {"tag_continuous": TagContinuous, "tag_gridworld": CUDATagGridWorld,
-         "single_cartpole": CUDAClassicControlCartPoleEnv}
+         "single_cartpole": CUDAClassicControlCartPoleEnv, "single_acrobot": CUDAClassicControlAcrobotEnv,
+         "single_mountain_car": CUDAClassicControlMountainCarEnv}
 
 
 def policy_map_for(name, env):

@@ -111,6 +111,8 @@ class Trainer:
 
         # ---- device data: first reset pushes the env arrays, then the placeholders
         env_wrapper.reset_all_envs()
+        if len(env_wrapper.cuda_data_manager.reset_target_to_pool):  # restarts drawn from a reset pool (trainer_base.py)
+            env_wrapper.init_reset_pool(wdd.rank_seed(tcfg.get("seed", 0) or 0, self.rank))
         self.sampler = HIPSampler(env_wrapper.cuda_function_manager)
         self.sampler.init_random(seed=wdd.rank_seed(tcfg.get("seed", 0) or 0, self.rank) + 1)
         create_and_push_data_placeholders(env_wrapper=env_wrapper, action_sampler=self.sampler,
