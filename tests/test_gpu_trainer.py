@@ -401,10 +401,87 @@ def test_fused_objective_equals_autograd(algo, heads, norm):
         obj.compute_loss_and_metrics_from_logits(0, out, actions, rewards, done, heads, True)
 
 
-@pytest.mark.parametrize("R,C", [(10007, 256), (4096, 64), (333, 128)])
+@pytest.mark.parametrize("heads", [[63], [1, 62], [32, 31], [1]])
+def test_fused_objective_vs_float64_at_the_edges(heads):
+    """HipPolicyGradientHead against FLOAT64 autograd of the framework objective at the edges of what it accepts: a
+    64-wide output row (64 KB of LDS per block), one-action heads, heads on both sides of 32, raw logits up to +-500 (a
+    saturated policy: probabilities that underflow), and an output tensor that is a contiguous view at a float offset
+    not divisible by 4 (the kernel's single-float copy path).  The actions are drawn from the float64 probabilities, as
+    a rollout would.  Gradient and logged terms within max(4 x the framework's float32 error, 8 float32 ulps of the
+    float64 value)."""
+    from tests.hip_harness import require_gpu
+    from warp_drive_amd.managers import hip_driver as drv
+    from warp_drive_amd.managers.function_manager import HIPFunctionManager
+    from warp_drive_amd.training import update_kernels
+    from warp_drive_amd.training.losses import A2C
+
+    require_gpu()
+    fm = HIPFunctionManager(num_agents=1, num_envs=1)
+    fm.load_hip_from_binary_file()
+    kernels = update_kernels.UpdateKernels(fm)
+    torch.manual_seed(sum(heads) + len(heads))
+    T, E, n, W = 5, 37, 11, sum(heads) + 1
+    R = T * E * n
+    dev = torch.device("cuda:0")
+    spread = 10.0 ** (torch.rand(R, 1, device=dev) * 2.7)        # per row: logits of magnitude ~1 up to 500
+    z = (torch.rand(R, W, device=dev) * 2.0 - 1.0) * spread
+    z[:, -1] = torch.randn(R, device=dev)                         # (the value column)
+    assert float(z[:, :-1].abs().max()) >= 400.0
+    base = torch.zeros(R * W + 4, device=dev)
+    out = base[1:1 + R * W].view(T, E, n, W).requires_grad_(False)
+    out.copy_(z.view(T, E, n, W))
+    assert out.is_contiguous() and out.data_ptr() % 16 != 0
+    out.requires_grad_(True)
+    probs64 = []
+    start = 0
+    for a in heads:
+        probs64.append(torch.softmax(z[:, start:start + a].double(), dim=-1))
+        start += a
+    actions = torch.stack([torch.multinomial(p, 1)[:, 0] for p in probs64], dim=-1).view(T, E, n, len(heads)).to(torch.int32)
+    rewards = torch.randn(T, E, n, device=dev)
+    done = (torch.rand(T, E, device=dev) < 0.1).to(torch.int32)
+    obj = A2C(discount_factor_gamma=0.97, normalize_advantage=True, normalize_return=True, vf_loss_coeff=0.7,
+              entropy_coeff=0.03)
+    before = drv.LAUNCH_COUNTS["HipPolicyGradientHead"]
+    loss_k, m_k = obj.compute_loss_and_metrics_from_logits(0, out, actions, rewards, done, heads, True, kernels=kernels)
+    (g_k,) = torch.autograd.grad(loss_k, out)
+    assert drv.LAUNCH_COUNTS["HipPolicyGradientHead"] == before + 1
+
+    def framework(dtype):
+        o = z.view(T, E, n, W).to(dtype).detach().requires_grad_(True)
+        probs, start = [], 0
+        for a in heads:
+            probs.append(torch.softmax(o[..., start:start + a], dim=-1))
+            start += a
+        loss, m = obj.compute_loss_and_metrics(timestep=0, actions_batch=actions.long(), rewards_batch=rewards.to(dtype),
+                                               done_flags_batch=done, action_probabilities_batch=probs,
+                                               value_functions_batch=o[..., start], perform_logging=True)
+        (g,) = torch.autograd.grad(loss, o)
+        return g, m
+
+    g64, m64 = framework(torch.float64)
+    g32, m32 = framework(torch.float32)
+    assert torch.isfinite(g_k).all()
+    ulp = 2.0 ** -24
+    err, err_f32 = float((g_k.double() - g64).abs().max()), float((g32.double() - g64).abs().max())
+    scale = float(g64.abs().max())
+    ratios = {"gradient": err / err_f32 if err_f32 else float("nan")}
+    terms = ("Total loss", "Policy loss", "Value function loss", "Mean entropy")
+    for k in terms:
+        e, e32 = abs(m_k[k] - m64[k]), abs(m32[k] - m64[k])
+        ratios[k] = e / e32 if e32 else float("nan")
+    print(f"heads {heads}: err / err_f32", {k: f"{v:.2f}" for k, v in ratios.items()})
+    assert err <= max(4.0 * err_f32, 8 * ulp * scale), (err, err_f32, scale)
+    for k in terms:
+        e, e32 = abs(m_k[k] - m64[k]), abs(m32[k] - m64[k])
+        assert e <= max(4.0 * e32, 8 * ulp * abs(m64[k])), (k, m_k[k], m32[k], m64[k])
+
+
+@pytest.mark.parametrize("R,C", [(10007, 256), (4096, 64), (333, 128), (5003, 16), (777, 32)])
 def test_relu_backward_with_column_sums(R, C):
     """HipReluBackwardColumnSums: mask + bias gradient in one pass = threshold_backward followed by a column sum"""
     from tests.hip_harness import require_gpu
+    from warp_drive_amd.managers import hip_driver as drv
     from warp_drive_amd.managers.function_manager import HIPFunctionManager
     from warp_drive_amd.training.update_kernels import UpdateKernels
 
@@ -416,7 +493,9 @@ def test_relu_backward_with_column_sums(R, C):
     g = torch.randn(R, C, device="cuda")
     y = torch.relu(torch.randn(R, C, device="cuda"))
     assert k.supports_relu_backward(g, y)
+    before = drv.LAUNCH_COUNTS["HipReluBackwardColumnSums"]
     got, sums = k.relu_backward_colsum(g, y)
+    assert drv.LAUNCH_COUNTS["HipReluBackwardColumnSums"] == before + 1
     want = torch.ops.aten.threshold_backward(g, y, 0)
     assert torch.equal(got, want)
     assert torch.allclose(sums, want.sum(0), rtol=1e-5, atol=1e-4)
@@ -485,12 +564,15 @@ def test_update_from_stored_rollout_activations(tmp_path):
         tr.graceful_close()
 
 
-@pytest.mark.parametrize("R,W,C", [(10007, 43, 256), (5000, 6, 64), (777, 3, 128), (200007, 43, 256), (70000, 6, 256), (65536 + 31, 3, 256)])
+@pytest.mark.parametrize("R,W,C", [(10007, 43, 256), (5000, 6, 64), (777, 3, 128), (200007, 43, 256), (70000, 6, 256), (65536 + 31, 3, 256),
+                                   (3001, 43, 64), (4099, 43, 128), (2053, 6, 128), (65535, 6, 256), (1029, 3, 64),
+                                   (30011, 3, 256)])
 def test_head_backward_kernel(R, W, C):
     """HipHeadBackward_W<w> (vector units) and, for 256 hidden units and >= 65536 rows, HipHeadBackwardBx3_W<w> (bf16 matrix
     cores, bf16x3): the output layer's backward, the hidden layer's ReLU mask + bias gradient and the output layer's weight
     gradient in one pass, against the three framework operations it replaces (ragged row counts: the last R % 32 rows)"""
     from tests.hip_harness import require_gpu
+    from warp_drive_amd.managers import hip_driver as drv
     from warp_drive_amd.managers.function_manager import HIPFunctionManager
     from warp_drive_amd.training.update_kernels import UpdateKernels
 
@@ -503,7 +585,10 @@ def test_head_backward_kernel(R, W, C):
     w3 = torch.randn(W, C, device="cuda") * 0.2
     h2 = torch.relu(torch.randn(R, C, device="cuda"))
     assert k.supports_head_backward(g3, w3, h2)
+    name = f"HipHeadBackwardBx3_W{W}" if C == 256 and R >= 65536 else f"HipHeadBackward_W{W}"
+    before = drv.LAUNCH_COUNTS[name]
     g2, db2, dw3, db3 = k.head_backward(g3, w3, h2)
+    assert drv.LAUNCH_COUNTS[name] == before + 1, name
     assert (db3 is not None) == (C == 256 and R >= 65536)
     if db3 is not None:
         assert torch.allclose(db3, g3.double().sum(0).float(), rtol=1e-4, atol=1e-2)
@@ -519,6 +604,7 @@ def test_linear_mask_backward_kernel(R, C):
     """HipLinearMaskBackwardBx3_<C>: g_out = [h > 0] * (g_in . W) with the product in bf16x3 arithmetic -- against the
     float64 product: float32-accurate (relative error of the size of a float32 GEMM's own), mask exact, ragged R"""
     from tests.hip_harness import require_gpu
+    from warp_drive_amd.managers import hip_driver as drv
     from warp_drive_amd.managers.function_manager import HIPFunctionManager
     from warp_drive_amd.training.update_kernels import UpdateKernels
 
@@ -531,7 +617,9 @@ def test_linear_mask_backward_kernel(R, C):
     w = torch.randn(C, C, device="cuda") / C ** 0.5
     h = torch.relu(torch.randn(R, C, device="cuda"))
     assert k.supports_linear_mask_backward(g, w, h)
+    before = drv.LAUNCH_COUNTS[f"HipLinearMaskBackwardBx3_{C}"]
     got = k.linear_mask_backward(g, w, h)
+    assert drv.LAUNCH_COUNTS[f"HipLinearMaskBackwardBx3_{C}"] == before + 1
     exact = (g.double() @ w.double()) * (h > 0)
     f32 = (g @ w) * (h > 0)  # the framework's float32 GEMM, for scale
     err, err_f32 = float((got.double() - exact).abs().max()), float((f32.double() - exact).abs().max())
@@ -540,12 +628,14 @@ def test_linear_mask_backward_kernel(R, C):
 
 
 @pytest.mark.parametrize("R,ci,bias", [(70001, 256, False), (65536 + 4, 71, True), (1 << 20, 71, True), (300004, 33, False),
-                                       (1 << 20, 256, False)])
+                                       (1 << 20, 256, False), (65536, 1, True), (70001, 4, True), (65536 + 17, 21, True),
+                                       (65536, 64, True), (100003, 95, True), (65536, 95, False)])
 def test_weight_grad_kernel(R, ci, bias, monkeypatch):
     """HipWeightGradBx3_256x{256,96}: g^T @ x over the batch in bf16x3 arithmetic (+ the bias gradient as a column of ones)
     -- against the float64 product: float32-accurate (error of the size of the framework's float32 GEMM's own), ragged
     row counts (a last step of fewer than 16 rows, blocks with nothing to do), narrow inputs padded with zero columns"""
     from tests.hip_harness import require_gpu
+    from warp_drive_amd.managers import hip_driver as drv
     from warp_drive_amd.managers.function_manager import HIPFunctionManager
     from warp_drive_amd.training.update_kernels import UpdateKernels
 
@@ -557,7 +647,10 @@ def test_weight_grad_kernel(R, ci, bias, monkeypatch):
     g = torch.randn(R, 256, device="cuda") * (torch.rand(R, 1, device="cuda") < 0.7)   # (whole zero rows, as masked gradients have)
     x = torch.relu(torch.randn(R, ci, device="cuda")) + 0.25
     assert k.supports_weight_grad(g, x, with_bias=bias)
+    name = f"HipWeightGradBx3_256x{256 if ci == 256 else 96}"
+    before = drv.LAUNCH_COUNTS[name]
     gw, gb = k.weight_grad(g, x, with_bias=bias)
+    assert drv.LAUNCH_COUNTS[name] == before + 1, name
     exact = g.double().t() @ x.double()
     f32 = g.t() @ x
     err, err_f32 = float((gw.double() - exact).abs().max()), float((f32.double() - exact).abs().max())

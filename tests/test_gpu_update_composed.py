@@ -116,6 +116,78 @@ def test_composed_backward_on_stored_activations_vs_float64_autograd(algo, norma
     print("relative error (kernels, framework float32) per parameter:", {k: (f"{a:.1e}", f"{b:.1e}") for k, (a, b) in report.items()})
 
 
+_HEADS_OF_WIDTH = {43: [21, 21], 6: [5], 3: [2]}
+_UPDATE_KERNEL_PREFIXES = ("HipPolicyGradientHead", "HipHeadBackward", "HipLinearMaskBackward", "HipWeightGrad",
+                           "HipReluBackwardColumnSums")
+
+
+# Observed baseline: every parameter within 4 x the float32 error except the layer-2 bias at (64, 3, 4, 9999) (7 x) and
+# (128, 43, 40, 10009) (5 x) and vf_head.weight at (64, 3, 4, 9999) (5.6 x) -- all under the 2e-6 * scale floor; the
+# layer-2 bias is HipHeadBackward_W<w>'s per-thread column sum over 4096-row blocks
+@pytest.mark.parametrize("H,W,F,R", [
+    (64, 43, 71, 10007), (128, 6, 21, 9973), (128, 43, 40, 10009), (64, 3, 4, 9999),   # HipHeadBackward_W* (C = 64 / 128)
+    (256, 3, 4, 65536 + 7), (256, 6, 21, 131072),                                      # Bx3 head, HipWeightGradBx3_256x96
+])
+def test_composed_backward_across_network_shapes_vs_float64_autograd(H, W, F, R):
+    """forward_logits + the fused objective + _MlpTwoHidden.backward at the other network shapes the update kernels
+    accept: narrow hidden layers (HipHeadBackward_W<w> at C = 64 / 128 threads, HipLinearMaskBackwardBx3_64 / 128, the
+    weight gradients in the framework) at a ragged R of ~1e4, and [256, 256] policies with narrow heads and inputs
+    (HipHeadBackwardBx3_W3 / W6, HipWeightGradBx3_256x96 with ci = 4 / 21) over the 65 536-row threshold -- ragged, and
+    R % 32 == 0 (no host-side tail).  The kernels that ran are exactly those of `update_plan`; the loss to 1e-6, every
+    parameter gradient within 4 x the framework's own float32 error of float64 autograd (floor: 2e-6 of the largest
+    entry)."""
+    from tests.hip_harness import require_gpu
+    from warp_drive_amd.managers import hip_driver as drv
+    from warp_drive_amd.managers.function_manager import HIPFunctionManager
+    from warp_drive_amd.training.losses import A2C
+    from warp_drive_amd.training.models import FullyConnected
+    from warp_drive_amd.training.update_kernels import UpdateKernels
+
+    require_gpu()
+    dev = torch.device("cuda:0")
+    fm = HIPFunctionManager(num_agents=1, num_envs=1)
+    fm.load_hip_from_binary_file()
+    kernels = UpdateKernels(fm)
+    torch.manual_seed(H + W + F)
+    heads = _HEADS_OF_WIDTH[W]
+    T, n = 1, 1
+    E = R
+    model = FullyConnected(F, heads, (H, H)).to(dev)
+    model.update_kernels = kernels
+    obs = torch.randn(T, E, n, F, device=dev) * (torch.rand(T, E, n, F, device=dev) < 0.8)
+    actions = torch.stack([torch.randint(0, a, (T, E, n), device=dev) for a in heads], dim=-1).to(torch.int32)
+    rewards = torch.randn(T, E, n, device=dev) * (torch.rand(T, E, n, device=dev) < 0.2)
+    done = (torch.rand(T, E, device=dev) < 0.1).to(torch.int32)
+    objective = A2C(discount_factor_gamma=0.98, normalize_advantage=True, normalize_return=True, vf_loss_coeff=0.5,
+                    entropy_coeff=0.03)
+    plan = kernels.update_plan(model, R)
+    planned = sorted(v for v in plan.values() if not v.startswith("framework"))
+    if H == 256:
+        assert f"HipHeadBackwardBx3_W{W}" in planned and "HipWeightGradBx3_256x96" in planned, plan
+    else:
+        assert f"HipHeadBackward_W{W}" in planned and f"HipLinearMaskBackwardBx3_{H}" in planned, plan
+    before = dict(drv.LAUNCH_COUNTS)
+    logits = model.forward_logits(obs)
+    loss, _ = objective.compute_loss_and_metrics_from_logits(0, logits, actions, rewards, done, heads, False, kernels=kernels)
+    loss.backward()
+    torch.cuda.synchronize()
+    ran = sorted(k for k, v in drv.LAUNCH_COUNTS.items() if v > before.get(k, 0) and k.startswith(_UPDATE_KERNEL_PREFIXES))
+    assert ran == planned, (ran, plan)
+    got = {name: p.grad.detach().clone() for name, p in model.named_parameters()}
+
+    want, loss64 = _float64_reference(model, obs, actions, rewards, done, objective, heads)
+    f32 = _float32_framework(model, obs, actions, rewards, done, objective)
+    assert abs(float(loss) - loss64) <= 1e-6 * max(1.0, abs(loss64)), (float(loss), loss64)
+    report = {}
+    for name in want:
+        scale = float(want[name].abs().max())
+        err = float((got[name].double() - want[name]).abs().max())
+        err_f32 = float((f32[name].double() - want[name]).abs().max())
+        report[name] = f"{err / err_f32:.2f}" if err_f32 > 0 else f"{err:.1e} / 0"
+        assert err <= max(4.0 * err_f32, 2e-6 * scale), (name, err, err_f32, scale)
+    print(f"(H, W, F, R) = {(H, W, F, R)}: err / err_f32 per parameter:", report)
+
+
 def test_trainer_update_over_the_threshold_stored_vs_recomputed_vs_framework(tmp_path):
     """`Trainer._update_model_params` with both policies over 65 536 rows and ragged (tagger: 66 x 201 x 5 = 66 330 rows,
     66 330 % 32 = 26; runner: 1 326 600 rows, % 32 = 8): THREE trainers in one process on the same rollout --

@@ -176,3 +176,43 @@ def test_bf16x3_packed_layout_reproduces_the_network(H, F, heads):
         want = torch.cat([hd(h) for hd in dm.policy_head] + [dm.vf_head(h)], dim=1).numpy()
     np.testing.assert_allclose(out[:, :want.shape[1]], want, rtol=0, atol=2e-6)
     assert np.all(out[:, want.shape[1]:] == 0.0)
+
+
+def _heads_for(H, kt1):
+    """output widths that vary with the instantiation: one head of 63 (W = 64), two spanning both output tiles, narrow"""
+    return {1: [63], 2: [30, 33], 3: [5, 3]}[kt1] if H != 128 else {1: [2], 2: [21, 21], 3: [1, 62]}[kt1]
+
+
+@pytest.mark.parametrize("arithmetic", ["float32", "bf16x3"])
+@pytest.mark.parametrize("kt1", [1, 2, 3])
+@pytest.mark.parametrize("H", [64, 128, 256])
+def test_packed_layout_of_every_instantiation(H, kt1, arithmetic):
+    """every (H, KT1) the kernel source instantiates, in both packed layouts: the emulated contraction reproduces the
+    float64 network (observation rows of an odd length inside the k-tile range, so the zero padding of the last k-tile
+    is exercised), padded output rows stay zero"""
+    from warp_drive_amd.training.models import FullyConnected
+    from warp_drive_amd.training.policy_kernel import FusedPolicyForward
+
+    F, heads = 32 * kt1 - 5, _heads_for(H, kt1)
+    torch.manual_seed(H + 7 * kt1)
+    model = FullyConnected(F, heads, fc_dims=(H, H))
+    assert FusedPolicyForward.supports(model, F)
+    dev = _NoDevice()
+    fused = FusedPolicyForward(dev, model, F, arithmetic=arithmetic)
+    assert fused.kt1 == kt1 and dev.names == [f"HipPolicyMlp{'Bx3' if arithmetic == 'bf16x3' else ''}_{H}x{H}_k{kt1}"]
+    x = torch.randn(32, F)
+    if arithmetic == "bf16x3":
+        assert tuple(fused.packed[0].shape) == (kt1, 3, H // 32, 2, 64, 8)
+        out = _emulate_bx3(fused.packed, F, H, x.numpy())
+    else:
+        assert tuple(fused.packed[0].shape) == (kt1, H // 32, 4, 64, 4)
+        out = _emulate(fused.packed, F, H, x.numpy().astype(np.float64))
+    with torch.no_grad():
+        dm = FullyConnected(F, heads, fc_dims=(H, H)).double()
+        dm.load_state_dict({k: v.double() for k, v in model.state_dict().items()})
+        h = x.double()
+        for i in range(2):
+            h = dm.fc[str(i)](h)
+        want = torch.cat([hd(h) for hd in dm.policy_head] + [dm.vf_head(h)], dim=1).numpy()
+    np.testing.assert_allclose(out[:, :want.shape[1]], want, rtol=0, atol=2e-6)
+    assert np.all(out[:, want.shape[1]:] == 0.0)

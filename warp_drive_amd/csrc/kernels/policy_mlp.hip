@@ -261,15 +261,20 @@ __global__ void __launch_bounds__(256) HipPolicyGradientHead(const float *__rest
       for (int j = 0; j < A; ++j) m = fmaxf(m, zh[j]);
       float total = 0.0f;
       for (int j = 0; j < A; ++j) total += expf(zh[j] - m);
-      const float lse = m + logf(total);
+      // log p_j = (z_j - m) - log(total): the shift by the maximum comes FIRST.  z_j - (m + log(total)) rounded
+      // m + log(total) to an ulp of m (3e-5 at |m| ~ 500: raw logits of a saturated policy), which moved every log p_j,
+      // and so every p_j, by up to 1.5e-5 relative -- 100 x the framework's float32 softmax (found by
+      // tests/test_gpu_trainer.py::test_fused_objective_vs_float64_at_the_edges).  Identical results where m = 0 (the
+      // stored outputs of the rollout are shifted by their maximum already).
+      const float lse = logf(total);
       float H = 0.0f;
       for (int j = 0; j < A; ++j) {
-        const float lp = zh[j] - lse;
+        const float lp = (zh[j] - m) - lse;
         H -= expf(lp) * lp;
       }
-      logp_taken += zh[min(max(taken, 0), A - 1)] - lse;
+      logp_taken += (zh[min(max(taken, 0), A - 1)] - m) - lse;
       for (int j = 0; j < A; ++j) {
-        const float lp = zh[j] - lse, pj = expf(lp);
+        const float lp = (zh[j] - m) - lse, pj = expf(lp);
         zh[j] = (a * (pj - (j == taken ? 1.0f : 0.0f)) + ent_coeff * pj * (lp + H)) * inv_R;
       }
       s_ent += H;

@@ -192,10 +192,12 @@ class FusedRolloutTick:
 
     def __init__(self, function_manager, forwards, agent_ids, obs, actions, rewards, done, rng_state, stream_tag,
                  batch_row, obs_batches, action_batches, reward_batches, done_batch, ep_rewards, ep_sums, ep_count,
-                 stored=None):
+                 stored=None, probs=None):
         """stored (optional): per policy None or (h1 [T, E, n_pol, H], h2 [T, E, n_pol, H], out [T, E, n_pol, A0 + A1 + 1])
         float32 -- the forward launch also writes row t of the hidden activations and of the outputs, which is all the
-        update's forward pass would recompute (bf16x3 arithmetic only)."""
+        update's forward pass would recompute (bf16x3 arithmetic only).
+        probs (optional): two float32 tensors [E, N, A0], [E, N, A1] -- the forward launch also writes the probabilities
+        it drew the actions from (the trainer does not need them; tests replay the draws on them)."""
         assert 1 <= len(forwards) <= 2
         f0 = forwards[0]
         assert all((f.H, f.kt1, f.heads, f.F) == (f0.H, f0.kt1, f0.heads, f0.F) for f in forwards), \
@@ -241,7 +243,11 @@ class FusedRolloutTick:
             per_policy.append([null, np.int32(0), np.int32(1), np.int32(0)] + [null] * 11)
         self.slot = torch.from_numpy(slot.astype(np.int32)).to(dev)
         assert batch_row.dtype == torch.int64 and batch_row.numel() == E
-        self.fwd_args = [obs, np.int32(F), np.int32(N), np.int32(f0.heads[0]), np.int32(f0.heads[1]), null, null, batch_row,
+        if probs is not None:
+            for t, a in zip(probs, f0.heads):
+                assert t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (E, N, a), (tuple(t.shape), a)
+        p0, p1 = (null, null) if probs is None else probs
+        self.fwd_args = [obs, np.int32(F), np.int32(N), np.int32(f0.heads[0]), np.int32(f0.heads[1]), p0, p1, batch_row,
                          rng_state, actions, np.int32(stream_tag), np.int32(blocks[0] if len(forwards) == 2 else 2 ** 30),
                          *per_policy[0], *per_policy[1]]
         self.fwd_grid, self.fwd_block = (sum(blocks), 1), (64 * f0.WAVES_PER_BLOCK, 1, 1)
