@@ -3,7 +3,9 @@
 stamps at the phase boundaries + counters of the search's fallbacks, written through a __device__ pointer the harness
 sets).  Build the stamped code object here (hipcc cross-compiles), run on the GPU box:
     python experiments/phase_profile.py build
-    python experiments/phase_profile.py [num_envs] [episode tick of the stamped launch] [runners per replica]
+    python experiments/phase_profile.py [num_envs] [episode tick of the stamped launch] [runners per replica] [ticks of the stamped launch]
+With the multi-tick entry (WD_TICK_ROLLOUT=1, the default) the stamped launch is a run of [ticks] ticks (default 32) and ONE
+of its trips is stamped, the middle one, which is the episode tick asked for; WD_TICK_ROLLOUT=0 stamps a one-tick launch.
 The stamped object replaces the product's through WD_HSACO_DIR (build/variants/prof/), everything else is the product."""
 import os
 import subprocess
@@ -31,6 +33,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "build":
 E = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
 T_STAMP = int(sys.argv[2]) if len(sys.argv) > 2 else 300  # (episodes are 500 ticks; the live-agent count falls along them)
 N_RUNNERS = int(sys.argv[3]) if len(sys.argv) > 3 else 100  # 5 taggers + this many runners per replica
+N_TICKS = int(sys.argv[4]) if len(sys.argv) > 4 else 32  # ticks of the stamped launch (multi-tick entry only)
 name = "prof"
 os.environ["WD_HSACO_DIR"] = PROF_DIR
 os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
@@ -67,13 +70,21 @@ t0 = time.perf_counter()
 engine.run(1000)
 torch.cuda.synchronize()
 print(f"=== {name}: wall per tick {(time.perf_counter() - t0) / 1000 * 1e6:.2f} us (stamped build)")
-engine.run((T_STAMP - 1300) % 500)
+looped = engine.rollout_kernel_name is not None
+stamp_trip = N_TICKS // 2 if looped else 0
+engine.run((T_STAMP - stamp_trip - 1300) % 500)
 torch.cuda.synchronize()
+if looped:  # the stamped object of the loop has its own copy of the probe pointer, and the trip to stamp
+    mod = w.cuda_function_manager._module_of(engine.rollout_kernel_name)
+    drv.memcpy_htod(mod.get_global("tc_prof_g")[0], np.array([int(buf)], dtype=np.uint64))
+    drv.memcpy_htod(mod.get_global("tc_prof_tick_g")[0], np.array([stamp_trip], dtype=np.int32))
+    print(f"multi-tick entry {engine.rollout_kernel_name}: a launch of {N_TICKS} ticks, trip {stamp_trip} stamped "
+          "(the wavefront counters add up over the whole launch)")
 live = w.cuda_data_manager.pull_data_from_device("still_in_the_game").sum(axis=1).mean()
 print(f"stamped launch = tick {T_STAMP} of an episode, {live:.1f} agents in the game")
 drv.memset(buf, 0, n_waves * SLOTS * 8)
 torch.cuda.synchronize()
-engine.run(1)
+engine.run(N_TICKS if looped else 1)
 torch.cuda.synchronize()
 raw = np.zeros(n_waves * SLOTS, dtype=np.uint64)
 drv.memcpy_dtoh(raw, buf)

@@ -107,6 +107,13 @@ int wd_plan_add_cohort(void *plan, int entry_index, int cohort, void *function, 
                        uint32_t grid_y, uint32_t grid_z, uint32_t block_x, uint32_t block_y,
                        uint32_t block_z, uint32_t shared_mem_bytes, const void *arg_buffer,
                        size_t arg_bytes);
+/* multi-tick form of a plan of ONE entry: a kernel that advances `n` ticks in one launch, n being the int32 at byte
+ * `ticks_offset` of its argument buffer.  Once set, wd_plan_run with repeats >= 2 launches this form on `stream` -- no
+ * fork or join events, cohorts or not -- with the repetitions as its tick count, split into launches of at most
+ * `max_ticks` ticks.  repeats == 1 and the graph calls keep the one-tick entry. */
+int wd_plan_set_multi_tick(void *plan, void *function, uint32_t grid_x, uint32_t grid_y, uint32_t grid_z,
+                           uint32_t block_x, uint32_t block_y, uint32_t block_z, uint32_t shared_bytes,
+                           const void *arg_buffer, size_t arg_bytes, size_t ticks_offset, int max_ticks);
 /* number of cohorts a multi-repetition wd_plan_run uses (1 = no cohorts) */
 int wd_plan_cohorts(void *plan, int *n_cohorts);
 /* capture `repeats_per_graph` repetitions into a hipGraph once, then replay it */

@@ -49,6 +49,11 @@ UNITS = {
     # (and its block size: 105 agents = one replica per 128-thread block, envs/tag_continuous.py::_geometry)
     "wd_kernels_tc_k10_n105a21.hsaco": ("tag_continuous.hip", ["-DWD_TC_KM=10", "-DWD_TC_SHAPE_N=105",
                                                                  "-DWD_TC_SHAPE_A=21", "-DWD_TC_SHAPE_THREADS=128"]),
+    # the same shape's multi-tick entry (every block loops over the ticks of a run), an object of its own: the one-tick
+    # object above stays byte-identical whatever happens to the loop
+    "wd_kernels_tc_k10_n105a21_rollout.hsaco": ("tag_continuous.hip", ["-DWD_TC_KM=10", "-DWD_TC_SHAPE_N=105",
+                                                                         "-DWD_TC_SHAPE_A=21", "-DWD_TC_SHAPE_THREADS=128",
+                                                                         "-DWD_TC_ROLLOUT=1"]),
     # the trainer's kernels, one source, two objects compiled side by side: the rollout's (policy forward, record) and the
     # update's (returns, objective, backward passes)
     "wd_kernels_mlp.hsaco": ("policy_mlp.hip", ["-DWD_MLP_PART=1"]),

@@ -138,6 +138,8 @@
 //                                      (105 agents, K = 10, 21-way heads, 128 threads: -3.8 % per tick for the sizes, -3.3 % more for
 //                                      the block size, experiments/README.md)
 //                                                                                           -> wd_kernels_tc_k10_n105a21.hsaco
+//   ... -DWD_TC_ROLLOUT=1              the same shape's multi-tick entry `HipTagContinuousRollout_K<k>_N<n>A<a>` alone
+//                                                                                           -> wd_kernels_tc_k10_n105a21_rollout.hsaco
 // Separate objects, so that work on the big-replica search never moves the registers or the code layout of the
 // headline kernel.  Every fast size class has three entries: Step (actions given), Tick (sample both heads + step +
 // restore finished replicas) and TickA (actions given -- drawn by the policy forward's epilogue, policy_mlp.hip --
@@ -168,6 +170,20 @@ __global__ void HipTagContinuousTick(WD_TC_PARAMS WD_TC_FUSE_PARAMS) {
 // one shape, sizes folded: N, K (exactly KM) and the two head sizes are constants from here on
 #define WD_TC_SHAPE_NAME(stem) WD_TC_CAT(WD_TC_CAT(WD_TC_CAT(WD_TC_CAT(WD_TC_CAT(stem, WD_TC_KM), _N), WD_TC_SHAPE_N), A), WD_TC_SHAPE_A)
 static_assert(WD_TC_SHAPE_N <= 128, "the shape-specialised entries use the 7-bit-id search of replicas up to 128 agents");
+#if defined(WD_TC_ROLLOUT)
+// -DWD_TC_ROLLOUT: a unit of its own with ONE entry, `HipTagContinuousRollout_K<k>_N<n>A<a>`: the Tick entry's arguments
+// plus the number of ticks; every block takes its replica through that many ticks (tc_fast_rollout, tc_fast.h).  A separate
+// object, so that the one-tick entries below (and the records keyed to their object) never move with it.
+static_assert(WD_TC_SHAPE_N > 64 && WD_TC_SHAPE_THREADS == 128, "one replica per 128-thread block");
+__global__ void __launch_bounds__(512, 4) WD_TC_SHAPE_NAME(HipTagContinuousRollout_K)(WD_TC_PARAMS WD_TC_FUSE_PARAMS,
+                                                                                      int kNumTicks) {
+  WD_TC_SMEM();
+  WD_TC_PACK();
+  WD_TC_FUSE_PACK();
+  a.N = WD_TC_SHAPE_N; a.K = WD_TC_KM;
+  tc_fast_rollout<WD_TC_KM, true, 7>(a, fz, tc_smem, WD_TC_SHAPE_A, WD_TC_SHAPE_A, kNumTicks);
+}
+#else
 __global__ void __launch_bounds__(512, 4) WD_TC_SHAPE_NAME(HipTagContinuousStep_K)(WD_TC_PARAMS) {
   WD_TC_SMEM();
   WD_TC_PACK();
@@ -188,6 +204,7 @@ __global__ void __launch_bounds__(512, 4) WD_TC_SHAPE_NAME(HipTagContinuousTickA
   a.N = WD_TC_SHAPE_N; a.K = WD_TC_KM;
   tc_fast_impl<WD_TC_KM, true, true, 7, false>(a, fz, tc_smem, WD_TC_SHAPE_A, WD_TC_SHAPE_A);
 }
+#endif  // WD_TC_ROLLOUT
 
 #else
 

@@ -14,12 +14,19 @@
 namespace {
 
 // EXACTK: K == KMAX, known at compile time (row offsets become immediates, the K-dependent selects fold away)
-template <int KMAX, bool FUSED, bool EXACTK, int IDB, bool SAMPLE = FUSED>
-__device__ __forceinline__ void tc_fast_impl(const TcArgs &a, const TcFuse &fz, unsigned char *smem, int n_acc,
-                                             int n_turn) {
+// LOOP: called as the body of the multi-tick entry (tc_fast_rollout below) for trip `tick` of a launch; the replica-independent tables
+// are built on trip 0 and stay (`n_taggers` carries their length); the probes stamp the one trip the harness chose
+template <int KMAX, bool FUSED, bool EXACTK, int IDB, bool SAMPLE = FUSED, bool LOOP = false>
+__device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, unsigned char *smem, int n_acc,
+                                            int n_turn, int tick = 0, int n_taggers_in = 0) {
+  WD_TC_PROBE_TICK(LOOP, tick);
   const int N = a.N, K = EXACTK ? KMAX : a.K;
   const int F = 7 * K + 1;
-  const int tid = threadIdx.x, T_ = WD_TC_BLOCKDIM;
+  int tid_ = threadIdx.x;
+  // (a value the compiler cannot see through, per trip: without it every address that depends on the thread alone -- two
+  // registers per array -- is computed once and held across the loop, far beyond the register budget)
+  if constexpr (LOOP) asm volatile("" : "+v"(tid_));
+  const int tid = tid_, T_ = WD_TC_BLOCKDIM;
   const int epb = max(1, T_ / N);
   // (readfirstlane: the wavefront index is uniform, but only the hardware knows -- without it every loop whose
   // bounds depend on it is compiled as a divergent loop)
@@ -76,8 +83,14 @@ __device__ __forceinline__ void tc_fast_impl(const TcArgs &a, const TcFuse &fz, 
   TcIn in;
   tc_issue_loads<FUSED, SAMPLE>(in, a, fz, env0, epb, N, n_acc, n_turn, tid, slab_acc, slab_turn, true);
   const bool tab_in_lds = (n_acc <= WD_TC_TAB) && (n_turn <= WD_TC_TAB);
-  const int n_taggers = tc_build_tables(tb, a, N, n_acc, n_turn, tab_in_lds, in);
-  if (env0 >= a.E) return;  // whole block (no barrier is skipped by part of a block)
+  int n_taggers_ = n_taggers_in;
+  if constexpr (LOOP) {
+    if (tick == 0) n_taggers_ = tc_build_tables(tb, a, N, n_acc, n_turn, tab_in_lds, in);
+  } else {
+    n_taggers_ = tc_build_tables(tb, a, N, n_acc, n_turn, tab_in_lds, in);
+  }
+  const int n_taggers = n_taggers_;
+  if (env0 >= a.E) return n_taggers;  // whole block (no barrier is skipped by part of a block; the same on every trip)
   WD_TC_PROBE(1);
 
   const int env = env0 + el;
@@ -615,6 +628,31 @@ __device__ __forceinline__ void tc_fast_impl(const TcArgs &a, const TcFuse &fz, 
     }
   }
   WD_TC_PROBE(15); WD_TC_PROBE_RT(17);
+  return n_taggers;
+}
+
+// `ticks` ticks of the block's replicas in ONE launch (one replica per block; the fused, sampling tick).  The replicas of a
+// launch are independent, so nothing but the kernel boundary made replica r's tick t + 1 wait for replica s's tick t: here
+// every block runs on at its own pace and the blocks of a CU drift out of phase (one block's fetch and row flush under
+// another's search).  Every trip is the whole one-tick kernel: all inputs are read again from memory, both slabs are
+// fetched again, every output of every tick is stored.  Between two trips each wavefront waits for its own stores
+// (s_waitcnt vmcnt(0)) and the block meets at a barrier:
+//   * the next trip reads what this one stored -- state, time step, RNG words, and, once per episode, the rows OTHER
+//     threads of the block restored (tc_reset_finished).  All wavefronts of a block share their CU's vector L1, which
+//     the stores write through, and every such read is a vector load issued after the barrier: it cannot return a line
+//     older than the stores (the tables read with scalar loads -- the RNG key, the reset table -- are never written);
+//   * the probability slabs alias the work area: the next trip's global_load_lds may only go out once every wavefront
+//     is done with this trip's staging buffers and tables.
+// No barrier across blocks, no communication between them.
+template <int KMAX, bool EXACTK, int IDB>
+__device__ __forceinline__ void tc_fast_rollout(const TcArgs &a, const TcFuse &fz, unsigned char *smem, int n_acc,
+                                                int n_turn, int ticks) {
+  int n_taggers = 0;
+  for (int tick = 0; tick < ticks; ++tick) {
+    n_taggers = tc_fast_impl<KMAX, true, EXACTK, IDB, true, true>(a, fz, smem, n_acc, n_turn, tick, n_taggers);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  }
 }
 
 }  // namespace

@@ -156,6 +156,11 @@ struct Plan {
   std::vector<hipStream_t> side;     // cohorts 1 .. C-1 (created on first use)
   hipEvent_t fork = nullptr;
   std::vector<hipEvent_t> join;      // one per side stream
+  // multi-tick form of a one-entry plan (wd_plan_set_multi_tick): ONE launch advances `n` ticks, n written into its
+  // argument buffer at `ticks_offset` per call
+  PlanEntry multi;
+  size_t ticks_offset = 0;
+  int max_ticks = 0;
 };
 
 int launch_packed(hipFunction_t fn, const uint32_t g[3], const uint32_t b[3], uint32_t shmem,
@@ -451,10 +456,57 @@ int plan_run_cohorts(Plan *p, int repeats, hipStream_t s) {
   return 0;
 }
 
+// `repeats` ticks as launches of the multi-tick form on the caller's stream (no fork, no join): at most `max_ticks`
+// ticks per launch, so that no single launch runs for longer than a few tens of milliseconds
+int plan_run_multi(Plan *p, int repeats, hipStream_t s) {
+  const bool timed = p->timed_entry >= 0 && (p->open || p->used < p->max_samples);
+  if (timed && !p->open) {
+    if (int rc = check(g_hip.hipEventRecord(p->ev[2 * p->used], s), "hipEventRecord")) return rc;
+    p->open = true;
+  }
+  PlanEntry &e = p->multi;
+  for (int left = repeats; left > 0;) {
+    const int32_t n = left < p->max_ticks ? left : p->max_ticks;
+    std::memcpy(e.args.data() + p->ticks_offset, &n, sizeof(n));  // (the launch copies the buffer)
+    if (int rc = launch_packed(e.fn, e.g, e.b, e.shmem, s, e.args.data(), e.args.size())) return rc;
+    left -= n;
+  }
+  p->run_counter += repeats;
+  if (timed) {  // one bracket around the whole run, counted as `repeats` launches of the timed entry (as with cohorts)
+    p->pending += repeats;
+    if (int rc = check(g_hip.hipEventRecord(p->ev[2 * p->used + 1], s), "hipEventRecord")) return rc;
+    p->launches.push_back(p->pending);
+    p->pending = 0;
+    p->open = false;
+    ++p->used;
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
 
+int wd_plan_set_multi_tick(void *plan, void *function, uint32_t gx, uint32_t gy, uint32_t gz, uint32_t bx,
+                           uint32_t by, uint32_t bz, uint32_t shmem, const void *buf, size_t bytes,
+                           size_t ticks_offset, int max_ticks) {
+  Plan *p = static_cast<Plan *>(plan);
+  if (!p || !function || !buf || p->entries.size() != 1 || max_ticks < 1 || ticks_offset % 4 != 0 ||
+      ticks_offset + sizeof(int32_t) > bytes) {
+    set_err("wd_plan_set_multi_tick: needs a plan of exactly one entry, a tick count inside the %zu argument bytes "
+            "(offset %zu) and max_ticks >= 1", bytes, ticks_offset);
+    return WD_ERR_BAD_ARG;
+  }
+  PlanEntry &e = p->multi;
+  e.fn = static_cast<hipFunction_t>(function);
+  e.g[0] = gx; e.g[1] = gy; e.g[2] = gz;
+  e.b[0] = bx; e.b[1] = by; e.b[2] = bz;
+  e.shmem = shmem;
+  e.args.assign(static_cast<const unsigned char *>(buf), static_cast<const unsigned char *>(buf) + bytes);
+  p->ticks_offset = ticks_offset;
+  p->max_ticks = max_ticks;
+  return 0;
+}
 int wd_plan_add_cohort(void *plan, int entry_index, int cohort, void *function, uint32_t gx, uint32_t gy,
                        uint32_t gz, uint32_t bx, uint32_t by, uint32_t bz, uint32_t shmem, const void *buf,
                        size_t bytes) {
@@ -488,6 +540,7 @@ int wd_plan_run(void *plan, int repeats, void *stream) {
   Plan *p = static_cast<Plan *>(plan);
   hipStream_t s = static_cast<hipStream_t>(stream);
   // one tick: the whole-range entries (no fork / join events for callers that run tick by tick)
+  if (repeats >= 2 && p->multi.fn) return plan_run_multi(p, repeats, s);  // one launch loops over the ticks
   if (repeats >= 2 && cohorts_complete(p)) return plan_run_cohorts(p, repeats, s);
   return plan_run_single(p, repeats, s);
 }

@@ -463,6 +463,20 @@ class TagContinuous(CUDAEnvironmentContext):
         args = args + [sampler.rng_state, probabilities[0], probabilities[1], table, n_arrays, _stream_tag("tick")]
         return fn, args, block, grid, self.lds_bytes(epb, fused=True, threads=block[0])
 
+    def rollout_launch(self, sampler, probabilities, resetter):
+        """Multi-tick form of the fused tick (HipTagContinuousRollout_K<k>_N<n>A<a>): the Tick entry's launch with one
+        more argument, the number of ticks every block takes its replica through (np.int32, LAST; the plan rewrites it
+        per run).  None when the build has no such entry for this shape."""
+        if not self._fast_path() or "Step" not in self.cuda_step.name:
+            return None
+        fm = self.cuda_function_manager
+        name = self.cuda_step.name.replace("Step", "Rollout")
+        if not fm.has_function(name):
+            return None
+        _, args, block, grid, shared = self.tick_launch(sampler, probabilities, resetter)
+        fm.initialize_functions([name])
+        return fm.get_function(name), args + [np.int32(1)], block, grid, shared
+
     # ------------------------------------------------------------------------------ step
     def step(self, actions=None):
         self.timestep += 1

@@ -86,7 +86,7 @@ C_ABI_SYMBOLS = (
     "wd_memset", "wd_module_load", "wd_module_load_data", "wd_module_unload", "wd_get_function",
     "wd_get_global", "wd_function_attribute", "wd_launch", "wd_launch_packed", "wd_sync",
     "wd_device_sync", "wd_plan_create", "wd_plan_add", "wd_plan_size", "wd_plan_run",
-    "wd_plan_add_cohort", "wd_plan_cohorts",
+    "wd_plan_add_cohort", "wd_plan_cohorts", "wd_plan_set_multi_tick",
     "wd_plan_instantiate_graph", "wd_plan_run_graph", "wd_plan_enable_timing", "wd_plan_read_timing",
     "wd_plan_destroy", "wd_event_create",
     "wd_event_record", "wd_event_synchronize", "wd_event_elapsed_ms", "wd_event_destroy",
@@ -147,6 +147,7 @@ def load_library(path=None):
             "wd_plan_run": ([_vp, _i32, _vp], _i32),
             "wd_plan_add_cohort": ([_vp, _i32, _i32, _vp] + [_u32] * 7 + [_vp, _sz], _i32),
             "wd_plan_cohorts": ([_vp, P(_i32)], _i32),
+            "wd_plan_set_multi_tick": ([_vp, _vp] + [_u32] * 7 + [_vp, _sz, _sz, _i32], _i32),
             "wd_plan_instantiate_graph": ([_vp, _i32, _vp], _i32),
             "wd_plan_run_graph": ([_vp, _i32, _vp], _i32),
             "wd_plan_enable_timing": ([_vp, _i32, _i32, _i32], _i32),
@@ -426,6 +427,17 @@ class LaunchPlan:
         g, b = _dim3(grid), _dim3(block)
         _check(_lib.wd_plan_add_cohort(_vp(self.handle), int(entry_index), int(cohort), _vp(fn.handle), g[0], g[1],
                                        g[2], b[0], b[1], b[2], int(shared), packed, len(packed)), "wd_plan_add_cohort")
+
+    def set_multi_tick(self, fn, args, block, grid, shared=0, max_ticks=2048):
+        """the plan's multi-tick form (wd_plan_set_multi_tick): `fn` advances as many ticks per launch as its LAST
+        argument (an int32) says; run(n >= 2) then is launches of it with at most `max_ticks` ticks each"""
+        assert isinstance(args[-1], np.int32)
+        packed = _pack_args(args)
+        self._keep.append(args)
+        g, b = _dim3(grid), _dim3(block)
+        _check(_lib.wd_plan_set_multi_tick(_vp(self.handle), _vp(fn.handle), g[0], g[1], g[2], b[0], b[1], b[2],
+                                           int(shared), packed, len(packed), len(packed) - 4, int(max_ticks)),
+               "wd_plan_set_multi_tick")
 
     @property
     def cohorts(self):

@@ -38,6 +38,11 @@ class UnsupportedRolloutShape(RuntimeError):
 # kernel boundary run under the other cohort's work.  Measured at 2000 replicas (interleaved A/B medians): C = 1 24.4 us
 # per tick, C = 2 21.9, C = 3 22.6 (docs/rounds/r07.md).  1 = one whole-range launch per tick.
 TICK_COHORTS = int(os.environ.get("WD_TICK_COHORTS", "2"))
+# Multi-tick form of the fused tick (TagContinuous, the shape-specialised entry): a run(n >= 2) is ONE launch whose
+# blocks loop over the n ticks of their replica, so no replica waits at a kernel boundary for the slowest one
+# (LaunchPlan.set_multi_tick; docs/rounds/r08.md).  0 = the cohort path exactly as before.
+TICK_ROLLOUT = int(os.environ.get("WD_TICK_ROLLOUT", "1"))
+ROLLOUT_MAX_TICKS = 2048  # ticks per launch: ~45 ms at the BASELINE shape; longer runs are split
 COHORT_ALIGN = 32  # cohort boundaries at multiples of 32 replicas: 32 rows of 4 * N bytes are N whole 128-byte lines
 
 
@@ -110,6 +115,7 @@ class RolloutEngine:
         self.entry_names = []
         self.cohorts = 1  # replica cohorts a multi-tick run() replays in parallel (one kernel per cohort and tick)
         self._graph_ticks = 0
+        self.rollout_kernel_name = None  # the multi-tick entry a run(n >= 2) launches (None: one launch per tick)
         # an env class that offers tick_launch() fuses sampling, step and reset in its own kernel
         # (restarts from a reset pool draw random members: that stays with the pool reset kernel, unless the env's tick
         # kernel draws them itself -- TICK_POOL_RESET)
@@ -143,6 +149,11 @@ class RolloutEngine:
             if (not self.presampled and rollout_policy is None and rollout_batch is None and self.ticks_per_launch == 1
                     and getattr(env_wrapper.env, "TICK_ENV_RANGES", False)):
                 self._add_cohorts(env_wrapper, sampler, probabilities, E, grid[0], dev)
+                if TICK_ROLLOUT and hasattr(env_wrapper.env, "rollout_launch"):
+                    multi = env_wrapper.env.rollout_launch(sampler, probabilities, env_wrapper.env_resetter)
+                    if multi is not None:
+                        self.plan.set_multi_tick(*multi, max_ticks=ROLLOUT_MAX_TICKS)
+                        self.rollout_kernel_name = multi[0].name
             return
         assert not self.presampled, "presampled_actions needs the env's fused tick entry"
         if self.continuous:  # OU / Gaussian around the means, HIPSampler.sample's launch
@@ -192,8 +203,9 @@ class RolloutEngine:
         self.cohorts = self.plan.cohorts
 
     def run(self, ticks, stream=None):
-        """Enqueue `ticks` rollout ticks (asynchronous).  With cohorts, ticks >= 2 fork the cohorts onto their own
-        streams and join them back into `stream` before returning."""
+        """Enqueue `ticks` rollout ticks (asynchronous).  With a multi-tick entry (`rollout_kernel_name`), ticks >= 2 are
+        launches of it on `stream`; else, with cohorts, ticks >= 2 fork the cohorts onto their own streams and join
+        them back into `stream` before returning."""
         self.plan.run(ticks, stream)
 
     def run_graph(self, ticks, ticks_per_graph=10, stream=None):
