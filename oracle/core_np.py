@@ -130,3 +130,126 @@ def single_head_tick_uniform(n_rows, epochs, seed_lo, seed_hi, stream_tag):
     sel = (ep & np.uint32(3)).astype(np.int64)
     bits = np.choose(sel, [np.asarray(w, dtype=np.uint32) for w in words])
     return u01_open_closed(bits.astype(np.uint32))
+
+
+# ---------------------------------------------------------------------------------------------
+# The three draws of the standalone service kernels (csrc/kernels/wd_core.hip), each a pure function of
+# (seed words, row, epoch, stream tag).  `epochs` broadcasts against `rows`.
+# ---------------------------------------------------------------------------------------------
+POOL_STREAM_TAG = 0x706F6F6C  # "pool": counter word 2 of reset_when_done_from_pool
+
+
+def seed_words(seed):
+    """(word 0, word 1) of the RNG state header as init_random writes them: the host masks the seed to 31 bits, the
+    kernel fixes word 1."""
+    return int(seed) & 0x7FFFFFFF, 0x5BD1E995
+
+
+def categorical_uniform(rows, epochs, seed_lo, seed_hi, stream_tag):
+    """sample_actions: word x of counter (row, epoch, tag, 0) -> float32 u in (0, 1]."""
+    x, _, _, _ = philox4x32_10(np.asarray(rows, dtype=np.uint32), np.asarray(epochs, dtype=np.uint32),
+                               np.uint32(int(stream_tag) & 0xFFFFFFFF), np.uint32(0), seed_lo, seed_hi)
+    return u01_open_closed(x)
+
+
+def ou_uniforms(rows, epochs, seed_lo, seed_hi, stream_tag):
+    """sample_ou_process: words x and y of counter (row, epoch, tag, 1) -> float32 (u1, u2), each in (0, 1]."""
+    x, y, _, _ = philox4x32_10(np.asarray(rows, dtype=np.uint32), np.asarray(epochs, dtype=np.uint32),
+                               np.uint32(int(stream_tag) & 0xFFFFFFFF), np.uint32(1), seed_lo, seed_hi)
+    return u01_open_closed(x), u01_open_closed(y)
+
+
+TWO_PI_F32 = np.float32(6.283185307179586)  # the kernel's float32 constant (6.2831855f)
+
+
+def box_muller_f64(u1, u2):
+    """sqrt(-2 ln u1) * cos(2 pi u2) in float64 with the exact 2 pi, on the float32 uniforms."""
+    u1, u2 = np.asarray(u1, dtype=np.float64), np.asarray(u2, dtype=np.float64)
+    return np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)
+
+
+def box_muller_f32(u1, u2):
+    """The same formula the way the kernel writes it, every operation in numpy float32: the float32 constant and the
+    float32 product 6.2831855f * u2 (so it carries the argument rounding any float32 evaluation has)."""
+    u1, u2 = np.asarray(u1, dtype=np.float32), np.asarray(u2, dtype=np.float32)
+    return (np.sqrt(np.float32(-2.0) * np.log(u1)) * np.cos(TWO_PI_F32 * u2)).astype(np.float32)
+
+
+def ou_step_f64(ou_state, distr, u1, u2, damping, stddev, scale):
+    """One sample_ou_process step in float64 from the float32 inputs and parameters the device gets:
+    ou = (1 - damping) * ou + stddev * N; action = distr + scale * ou.  Returns (ou, action) float64."""
+    f = lambda v: np.float64(np.float32(v))  # the kernel's arguments are float32
+    ou = (1.0 - f(damping)) * np.asarray(ou_state, np.float32).astype(np.float64) + f(stddev) * box_muller_f64(u1, u2)
+    return ou, np.asarray(distr, np.float32).astype(np.float64) + f(scale) * ou
+
+
+def ou_step_f32(ou_state, distr, u1, u2, damping, stddev, scale):
+    """The same step, every operation in numpy float32 (the yardstick of the device's error)."""
+    f = np.float32
+    ou = ((f(1.0) - f(damping)) * np.asarray(ou_state, f) + f(stddev) * box_muller_f32(u1, u2)).astype(f)
+    return ou, (np.asarray(distr, f) + f(scale) * ou).astype(f)
+
+
+def pool_p(envs, epochs, seed_lo, seed_hi):
+    """reset_when_done_from_pool: word x of counter (env, epoch, "pool", 2) -> float32 p = (x >> 8) * 2^-24 in [0, 1)."""
+    x, _, _, _ = philox4x32_10(np.asarray(envs, dtype=np.uint32), np.asarray(epochs, dtype=np.uint32),
+                               np.uint32(POOL_STREAM_TAG), np.uint32(2), seed_lo, seed_hi)
+    return (x >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+
+
+def pool_pick_from_p(p, n_pool):
+    """min(int(float32(p) * float32(n_pool)), n_pool - 1)"""
+    prod = np.asarray(p, dtype=np.float32) * np.float32(n_pool)
+    return np.minimum(prod.astype(np.int64), int(n_pool) - 1)
+
+
+def pool_pick(envs, epochs, seed_lo, seed_hi, n_pool):
+    """The pool row a finished replica copies."""
+    return pool_pick_from_p(pool_p(envs, epochs, seed_lo, seed_hi), n_pool)
+
+
+def find_end_draws(seed_lo, seed_hi, stream_tag, counter3, n_rows, n_epochs, words=(0,)):
+    """Search (row, epoch) in [0, n_rows) x [0, n_epochs) for draws at the two ends of the generator's range: for every
+    word w in `words` of counter (row, epoch, tag, counter3), the draws with `bits >> 8` == 0xFFFFFF (u == 1.0; pool p
+    the largest below 1) and == 0 (u == 2^-24; pool p == 0).  Returns {(w, "hi"): [(row, epoch), ...], (w, "lo"): [...]},
+    each list in (epoch, row) order.  2^25 Philox calls take a few seconds: callers cache the result."""
+    out = {(w, k): [] for w in words for k in ("hi", "lo")}
+    total, chunk = int(n_rows) * int(n_epochs), 1 << 18
+    for base in range(0, total, chunk):
+        idx = np.arange(base, min(base + chunk, total), dtype=np.int64)
+        epoch, row = idx // n_rows, idx % n_rows
+        blk = philox4x32_10(row.astype(np.uint32), epoch.astype(np.uint32), np.uint32(int(stream_tag) & 0xFFFFFFFF),
+                            np.uint32(counter3), seed_lo, seed_hi)
+        for w in words:
+            top = blk[w] >> np.uint32(8)
+            for key, val in (("hi", 0xFFFFFF), ("lo", 0)):
+                for i in np.flatnonzero(top == np.uint32(val)):
+                    out[(w, key)].append((int(row[i]), int(epoch[i])))
+    return out
+
+
+def sample_actions_search(distr, u):
+    """`sample_actions` (the reference's sequential float32 prefix sum + binary search with its kEps early exit) for all
+    rows at once: distr float32 [R, A], u float32 [R] -> int32 [R].  Same probes in the same order as search_index."""
+    distr = np.asarray(distr, dtype=np.float32)
+    R, A = distr.shape
+    cum = np.cumsum(distr, axis=-1, dtype=np.float32)
+    uu = np.asarray(u, dtype=np.float32).reshape(R)
+    idx = np.arange(R)
+    left, right = np.zeros(R, dtype=np.int64), np.full(R, A - 1, dtype=np.int64)
+    out = np.full(R, -1, dtype=np.int64)
+    while True:
+        active = (out < 0) & (left <= right)
+        if not active.any():
+            break
+        mid = np.where(active, left + (right - left) // 2, 0)
+        cm = cum[idx, mid]
+        hit = active & (np.abs((cm - uu).astype(np.float32)) < K_EPS)
+        out[hit] = mid[hit]
+        below = active & ~hit & (cm < uu)
+        above = active & ~hit & ~(cm < uu)
+        left[below] = mid[below] + 1
+        right[above] = mid[above] - 1
+    open_ = out < 0
+    out[open_] = np.where(left[open_] > A - 1, A - 1, left[open_])
+    return out.astype(np.int32)

@@ -12,7 +12,6 @@ pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 ENVS = ("acrobot", "mountain_car", "continuous_mountain_car", "pendulum")
-POOL_KEY = 0x706F6F6C
 
 
 def _spec(env):
@@ -45,19 +44,12 @@ def _words(ptr, n):
     return out
 
 
-def _pool_rows(words, envs):
-    """the pool row reset_when_done_from_pool draws for each replica in `envs` (host replay of its Philox key)"""
-    from oracle.core_np import philox4x32_10
-
-    x, _, _, _ = philox4x32_10(envs.astype(np.uint32), words[4 + envs], np.uint32(POOL_KEY), np.uint32(2),
-                               words[0], words[1])
-    p = (x >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
-    return words, p
-
-
 def _pool_pick(words, envs, n_pool):
-    _, p = _pool_rows(words, envs)
-    return np.minimum((p * np.float32(n_pool)).astype(np.int64), n_pool - 1)
+    """the pool row reset_when_done_from_pool draws for each replica in `envs` (host replay of its Philox draw,
+    oracle/core_np.py::pool_pick, from the device's own header and epoch words)"""
+    from oracle.core_np import pool_pick
+
+    return pool_pick(envs, words[4 + envs], words[0], words[1], n_pool)
 
 
 def _spread_states(env, rng, E):
