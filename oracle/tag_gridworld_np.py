@@ -64,12 +64,15 @@ class TagGridWorldOracle:
         self.rewards = np.zeros((self.E, self.N), dtype=np.float64)
         return self.obs
 
-    def reset_done_envs(self):
+    def reset_done_envs(self, x=None, y=None):
         """Device-side reset semantics: reset.cu:9-75 applied to loc_x, loc_y and
-        the observations placeholder (data_loader.py:360-364), then undo done."""
+        the observations placeholder (data_loader.py:360-364), then undo done.
+        x, y (optional, int [E, N]): the row each replica restarts from instead of the
+        starting locations (restarts from a reset pool); rows of replicas that are not
+        done are ignored."""
         m = self.done > 0
-        self.loc_x[m] = self.start_x
-        self.loc_y[m] = self.start_y
+        self.loc_x[m] = self.start_x if x is None else np.asarray(x, dtype=np.int32)[m]
+        self.loc_y[m] = self.start_y if y is None else np.asarray(y, dtype=np.int32)[m]
         self.obs[m] = self.obs_at_reset[m]
         self.timestep[m] = 0
         self.done[m] = 0

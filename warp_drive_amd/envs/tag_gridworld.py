@@ -204,13 +204,52 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
         runner (run_configs/tag_gridworld.yaml maps them to the "tagger" / "runner" policies)"""
         return [list(range(self.num_agents - 1)), [self.num_agents - 1]]
 
+    ROLLOUT_POLICY_MAX_LDS = 160 * 1024   # dynamic LDS the live-policy rollout may ask for: a gfx950 workgroup's
+
+    def live_policy_lds_bytes(self, width, cache_dwords=None):
+        """dynamic LDS of HipTagGridWorldRollout_N5_H<width> (the layout of gw5_rollout in tag_gridworld_n5.hip): the
+        image and the restore cache of 12 replicas, 64 coordinate quotients, the time table rounded up to 16 bytes,
+        the two packed policies"""
+        N, F = self.num_agents, 4 * self.num_agents + 1
+        if cache_dwords is None:   # the reset arrays of the shape the kernel is admitted for: positions + observations
+            cache_dwords = 2 * N + N * F
+        lds5 = 4 * (12 * N * F + 12 * cache_dwords + 64 + (int(self.episode_length) + 1 + 3) // 4 * 4
+                    + 2 * gridworld_policy_floats(width))
+        return (lds5 + 15) // 16 * 16
+
     def has_live_policy_rollout(self, width, n_actions):
         """does a rollout kernel exist that evaluates the two policy networks itself (HipTagGridWorldRollout_N5_H<width>)
-        for this env shape?  5 agents, full observations, 5 actions, hidden width 32 / 64 (RolloutEngine asks before it
-        calls `tick_launch(policy=...)`)"""
+        for this env shape?  5 agents, full observations, 5 actions, hidden width 32 / 64, and its tables (the time
+        table grows with the episode length) within ROLLOUT_POLICY_MAX_LDS (RolloutEngine asks before it calls
+        `tick_launch(policy=...)`)"""
         return (int(width) in self.ROLLOUT_POLICY_WIDTHS and int(n_actions) == 5 and len(self.step_actions) == 5
                 and self._specialised_rollout_shape()
+                and self.live_policy_lds_bytes(width) <= self.ROLLOUT_POLICY_MAX_LDS
                 and self.cuda_function_manager.has_function(f"HipTagGridWorldRollout_N5_H{int(width)}"))
+
+    def image_fits(self, epb):
+        """does a block of `epb` replicas keep its observation rows in LDS (lds_bytes: the image is part of the sum)?"""
+        F = 4 * self.num_agents + 1 if self.use_full_observation else 6
+        return self.lds_bytes(epb) > 4 * epb * self.num_agents * F
+
+    def _rollout_geometry(self, cache_dwords):
+        """geometry of the T-tick rollout, which needs the LDS observation image: `_geometry()` where its blocks have
+        one; else (wide rows: 15 agents with full observations have an image at 4 replicas per block and none at 17)
+        the largest block size that has one, preferring a size that also holds the restore cache.  No size has one:
+        UnsupportedRolloutShape -- the caller keeps its one-launch-per-tick path."""
+        choice = self._geometry()
+        if self.image_fits(choice[0]):
+            return choice
+        fm = self.cuda_function_manager
+        fits = [g for g in (fm.packed_geometry(self.num_agents, max_threads=max(m, self.num_agents))
+                            for m in (256, 128, 64)) if self.image_fits(g[0])]
+        if not fits:
+            from warp_drive_amd.rollout import UnsupportedRolloutShape
+
+            raise UnsupportedRolloutShape(f"{self.num_agents} agents: the observation rows of one replica do not fit "
+                                          "the LDS image the rollout kernel needs")
+        with_cache = [g for g in fits if self.lds_bytes(g[0]) + 4 * g[0] * cache_dwords <= 60000]
+        return (with_cache or fits)[0]
 
     def tick_launch(self, sampler, probabilities, resetter, env_range=None, batch=None, policy=None):
         """Fused rollout tick: sample the action + step + reset finished replicas in ONE launch
@@ -233,7 +272,8 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
         name = self.cuda_step.name.replace("Step", "Rollout" if rollout else "Tick")
         fm.initialize_functions([name])
         _, reset_args, _, _ = resetter.fused_launch(dm, 0, 0)  # builds / refreshes the descriptor table
-        epb, block, grid = self._geometry()
+        cache_dwords = sum(int(np.prod(dm.get_shape(k)[1:])) for k in dm.reset_data_list) if rollout else 0
+        epb, block, grid = self._rollout_geometry(cache_dwords) if rollout else self._geometry()
         if rollout and self._specialised_rollout_shape():
             # the specialised rollout kernel runs blocks of ONE wavefront (12 replicas) at every batch size
             epb, block, grid = 12, (64, 1, 1), ((int(dm.meta_info("n_envs")) + 11) // 12, 1)
@@ -245,7 +285,7 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
 
             E, N, T = int(dm.meta_info("n_envs")), self.num_agents, int(self.ticks_per_launch)
             F = 4 * N + 1 if self.use_full_observation else 6
-            assert int(probabilities[0].shape[-1]) <= 8 and self.lds_bytes(epb) > 4 * epb * N * F and len(self.step_actions) == 5, \
+            assert int(probabilities[0].shape[-1]) <= 8 and self.image_fits(epb) and len(self.step_actions) == 5, \
                 "the rollout kernel needs the LDS observation image and at most 8 actions"
             want = {"obs": ((E, N, F), torch.float32), "actions": ((E, N, 1), torch.int32),
                     "rewards": ((E, N), torch.float32), "done": ((E,), torch.int32)}
@@ -255,7 +295,6 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
                     tuple(t.shape[1:]) == shape, (key, tuple(t.shape), t.dtype)
             # the rows finished replicas are restored from are kept in LDS for the whole launch (no loads inside the
             # tick loop): the sum of the registered arrays' row lengths per replica, 0 = no room
-            cache_dwords = sum(int(np.prod(dm.get_shape(k)[1:])) for k in dm.reset_data_list)
             lds = self.lds_bytes(epb)
             if lds + 4 * epb * cache_dwords <= 60000:
                 lds += 4 * epb * cache_dwords
@@ -276,9 +315,10 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
                 special = f"{special}_H{width}"
                 fm.initialize_functions([special])
                 # the fixed-policy kernel's LDS with the time table rounded up to 16 bytes, then the two policies
-                lds5 = 4 * (epb * N * F + epb * cache_dwords + 64 + (int(self.episode_length) + 1 + 3) // 4 * 4 + 2 * n_w)
+                lds5 = self.live_policy_lds_bytes(width, cache_dwords)
+                assert lds5 <= self.ROLLOUT_POLICY_MAX_LDS, (lds5, self.ROLLOUT_POLICY_MAX_LDS)
                 return (fm.get_function(special), args + [fm.global_address("kIndexToActionArr"), tagger, runner], block,
-                        grid, (lds5 + 15) // 16 * 16)
+                        grid, lds5)
             if special is not None:
                 # the kernel specialised for this shape (csrc/kernels/tag_gridworld_n5.hip, its own code object):
                 # same arguments + the device address of the action table the host uploads into the main code object
