@@ -3,7 +3,8 @@
 configurations (the numbers tests/test_gpu_learning.py's thresholds were chosen from; reference README.md:60 shows the
 Cartpole curve of the reference trainer).
 
-    python scripts/learning_curves.py [--which cartpole_kernel cartpole_tick gridworld_kernel gridworld_tick acrobot] [--iters N]
+    python scripts/learning_curves.py [--which cartpole_kernel cartpole_tick gridworld_kernel gridworld_tick acrobot acrobot_kernel
+                                               mountain_car mountain_car_kernel] [--iters N]
 """
 import argparse
 import json
@@ -34,6 +35,16 @@ CONFIGS = {
     # length (-200 = never; restarts drawn from the config's reset pool)
     "acrobot": ("single_acrobot", {"trainer": {"num_envs": 1000, "train_batch_size": 1000 * 50, "num_episodes": 10 ** 6, "seed": 7},
                                    "env": {"episode_length": 200}}, "shared"),
+    # the same two-layer policies with the whole batch in one launch (the opt-in switch of the classic-control envs)
+    "acrobot_kernel": ("single_acrobot", {"trainer": {"num_envs": 1000, "train_batch_size": 1000 * 50, "num_episodes": 10 ** 6, "seed": 7,
+                                                      "fused_rollout_policy": "all"},
+                                          "env": {"episode_length": 200}}, "shared"),
+    # MountainCar pays -1 per tick until the car reaches the flag (-200 = never)
+    "mountain_car": ("single_mountain_car", {"trainer": {"num_envs": 1000, "train_batch_size": 1000 * 50, "num_episodes": 10 ** 6, "seed": 7},
+                                             "env": {"episode_length": 200}}, "shared"),
+    "mountain_car_kernel": ("single_mountain_car", {"trainer": {"num_envs": 1000, "train_batch_size": 1000 * 50, "num_episodes": 10 ** 6,
+                                                                "seed": 7, "fused_rollout_policy": "all"},
+                                                    "env": {"episode_length": 200}}, "shared"),
     # the taggers learn against a runner that stays the random initial policy: their episodic reward can only rise
     "gridworld_kernel_frozen_runner": ("tag_gridworld", {
         "trainer": {"num_envs": 600, "train_batch_size": 600 * 100, "num_episodes": 10 ** 6, "seed": 7},
@@ -83,7 +94,7 @@ def main():
             curve = [json.loads(line)[pol]["Mean episodic reward"] for line in open(os.path.join(d, "results.json"))]
             tr.graceful_close()
         print(f"{name} (lr {args.lr}, graph {args.graph}, grid {args.grid}, seed {args.seed}): path={'one launch per batch' if tr._batch_rollout is not None else 'per tick'} "
-              f"{args.iters} iterations in {dt:.1f} s; {pol} mean episodic reward per iteration:")
+              f"{args.iters} iterations in {dt:.1f} s ({args.iters / dt:.1f} iterations/s); {pol} mean episodic reward per iteration:")
         print("   " + " ".join(f"{v:.2f}" for v in curve[:: args.every]), flush=True)
 
 

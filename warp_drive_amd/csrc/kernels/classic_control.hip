@@ -281,6 +281,71 @@ struct CcTickArgs {
 
 constexpr int CC_MAX_ACTIONS = 8;
 
+// ---- a small policy INSIDE the tick (the arithmetic of cartpole.hip::cp_policy_cum, for an observation of O floats):
+// two hidden layers of H ReLU units + one softmax head, the weights in LDS (every lane reads the same address:
+// broadcast), the activations in registers.  Packed weights (training/policy_kernel.py::pack_rollout_policy): W0 [H][O],
+// b0 [H], W1 [H][H], b1 [H], Wp [A][H], bp [A], all float32.  acc = bias, then one fmaf per input in index order; softmax
+// with the maximum subtracted, expf, one division per action, the sum in action order; restated on the host in
+// tests/classic_control_policy.py::policy_probabilities.  Returns the running float32 sums of the probabilities.
+// The activations (2 H registers) and the float64 temporaries of the env's step are live in different phases of a tick.
+template <int H, int O>
+__device__ __forceinline__ void cc_policy_cum(const float *w, const float (&o)[O], int n_actions,
+                                              float (&cumv)[CC_MAX_ACTIONS]) {
+  static_assert(O % 2 == 0 && H % 4 == 0, "the rows of W0 are read as float2, those of W1 and Wp as float4");
+  const float *W0 = w, *b0 = W0 + O * H, *W1 = b0 + H, *b1 = W1 + H * H, *Wp = b1 + H, *bp = Wp + n_actions * H;
+  float h1[H], h2[H];
+#pragma unroll
+  for (int i = 0; i < H; ++i) {
+    float acc = b0[i];
+#pragma unroll
+    for (int j = 0; j < O; j += 2) {
+      const float2 wr = *(const float2 *)(W0 + O * i + j);
+      acc = fmaf(wr.x, o[j], acc); acc = fmaf(wr.y, o[j + 1], acc);
+    }
+    h1[i] = fmaxf(acc, 0.0f);
+  }
+#pragma unroll
+  for (int i = 0; i < H; ++i) {
+    float acc = b1[i];
+#pragma unroll
+    for (int j = 0; j < H; j += 4) {
+      const float4 wr = *(const float4 *)(W1 + i * H + j);
+      acc = fmaf(wr.x, h1[j], acc); acc = fmaf(wr.y, h1[j + 1], acc);
+      acc = fmaf(wr.z, h1[j + 2], acc); acc = fmaf(wr.w, h1[j + 3], acc);
+    }
+    h2[i] = fmaxf(acc, 0.0f);
+  }
+  float logit[CC_MAX_ACTIONS], m = -__builtin_inff();
+#pragma unroll
+  for (int a = 0; a < CC_MAX_ACTIONS; ++a) {
+    logit[a] = -__builtin_inff();
+    if (a < n_actions) {  // (uniform)
+      float acc = bp[a];
+#pragma unroll
+      for (int j = 0; j < H; j += 4) {
+        const float4 wr = *(const float4 *)(Wp + a * H + j);
+        acc = fmaf(wr.x, h2[j], acc); acc = fmaf(wr.y, h2[j + 1], acc);
+        acc = fmaf(wr.z, h2[j + 2], acc); acc = fmaf(wr.w, h2[j + 3], acc);
+      }
+      logit[a] = acc;
+      m = fmaxf(m, acc);
+    }
+  }
+  float e[CC_MAX_ACTIONS], sum = 0.0f;
+#pragma unroll
+  for (int a = 0; a < CC_MAX_ACTIONS; ++a) {
+    e[a] = (a < n_actions) ? expf(logit[a] - m) : 0.0f;
+    sum += e[a];
+  }
+  float cum = 0.0f;
+#pragma unroll
+  for (int a = 0; a < CC_MAX_ACTIONS; ++a) {
+    const float p = e[a] / sum;
+    if (a < n_actions) cum = (a == 0) ? p : cum + p;
+    cumv[a] = cum;
+  }
+}
+
 // Fused rollout tick(s) (the conventions of HipClassicControlCartPoleEnvTick): per tick, draw the action, step, and
 // restart a finished replica; the state, the observation and the timestep stay in registers.  Discrete envs draw
 // the categorical action from `probs` [E, n_actions] with wd_tick_draw(row, epoch0 + k, stream_tag); continuous envs
@@ -290,8 +355,19 @@ constexpr int CC_MAX_ACTIONS = 8;
 // pool (`pool` [n_pool, S], `pool_rng` = the resetter's RNG words), restarts from the pool row that
 // reset_when_done_from_pool would draw: counter {env, epoch, 0x706f6f6c, 2}, epoch advanced on a hit only.
 // `_done_` reports the last tick; timestep is cleared.  With the four `*_batch` pointers tick k writes row k.
-template <class Env, bool BATCH>
-__device__ __forceinline__ void cc_tick_impl(const Env &e, const CcTickArgs &a) {
+// H > 0 (discrete envs, the ...EnvRollout_H<H> entries): a LIVE policy.  `weights` = dynamic LDS of n_w = O H + H + H H + H
+// + A H + A floats; the block copies the packed network `policy` into it once per launch, and every tick evaluates it
+// on the observation the lane holds (the one row k of `obs_batch` records) instead of reading `probs`.  The draw keeps
+// the fixed-probability tick's Philox counters.
+template <class Env, bool BATCH, int H = 0>
+__device__ __forceinline__ void cc_tick_impl(const Env &e, const CcTickArgs &a, float *weights = nullptr,
+                                             const float *policy = nullptr) {
+  static_assert(H == 0 || !Env::CONT, "the in-kernel policy has a softmax head");
+  if constexpr (H > 0) {
+    const int n_w = Env::O * H + H + H * H + H + a.n_actions * H + a.n_actions;
+    for (int i = threadIdx.x; i < n_w; i += blockDim.x) weights[i] = policy[i];
+    __syncthreads();
+  }
   using Act = typename std::conditional<Env::CONT, float, int>::type;
   constexpr int S = Env::S, O = Env::O;
   const CcResetEntry *table = (const CcResetEntry *)a.reset_table;
@@ -303,14 +379,14 @@ __device__ __forceinline__ void cc_tick_impl(const Env &e, const CcTickArgs &a) 
     int t = a.env_timestep_arr[env];
     float s[S], o[O];
     cc_load_row<S>(a.state_arr, env, s);
-    if (BATCH) cc_load_row<O>(a.observation_arr, env, o);
+    if (BATCH || H > 0) cc_load_row<O>(a.observation_arr, env, o);
     const uint32_t epoch0 = a.rng_state[WD_RNG_HEADER + env];
     uint32_t pool_epoch = a.pool ? a.pool_rng[WD_RNG_HEADER + env] : 0u;
     float cumv[CC_MAX_ACTIONS], mean = 0.0f, ou = 0.0f;
     if (Env::CONT) {
       mean = a.probs[env];
       ou = a.ou_state[env];
-    } else {
+    } else if (H == 0) {
       const float *row = a.probs + (long)env * a.n_actions;
       float cum = 0.0f;
 #pragma unroll
@@ -339,6 +415,7 @@ __device__ __forceinline__ void cc_tick_impl(const Env &e, const CcTickArgs &a) 
       } else {
         const float u = wd_u01_open_closed(wd_tick_draw((uint32_t)env, epoch0 + (uint32_t)k, (uint32_t)a.stream_tag,
                                                         k0, k1, blk, blk_quad));
+        if constexpr (H > 0) cc_policy_cum<H, O>(weights, o, a.n_actions, cumv);  // live policy: THIS tick's observation
         int cnt = 0;
 #pragma unroll
         for (int i = 0; i < CC_MAX_ACTIONS; ++i) cnt += (i < a.n_actions && cumv[i] < u) ? 1 : 0;
@@ -403,6 +480,15 @@ template <class Env>
 __device__ __forceinline__ void cc_tick(const Env &e, const CcTickArgs &a) {
   if (a.obs_batch) cc_tick_impl<Env, true>(e, a);
   else cc_tick_impl<Env, false>(e, a);
+}
+
+// the rollout with a live policy; `hidden` must be the entry's width and n_actions fit the registers (else: no tick)
+template <int H, class Env>
+__device__ __forceinline__ void cc_rollout(const Env &e, const CcTickArgs &a, float *weights, const float *policy,
+                                           int hidden) {
+  if (hidden != H || a.n_actions < 1 || a.n_actions > CC_MAX_ACTIONS || policy == nullptr) return;  // (uniform)
+  if (a.obs_batch) cc_tick_impl<Env, true, H>(e, a, weights, policy);
+  else cc_tick_impl<Env, false, H>(e, a, weights, policy);
 }
 
 }  // namespace
@@ -485,5 +571,29 @@ __global__ void __launch_bounds__(256) HipClassicControlPendulumEnvTick(float *s
                                                  int n_envs, CC_TICK_PARAMS) {
   cc_tick(CcPendulum{}, CC_TICK_ARGS(state_arr, action_arr, done_arr, reward_arr, observation_arr, env_timestep_arr));
 }
+
+// the rollout with a live policy (two hidden layers of HH units + one softmax head, packed weights in dynamic LDS): the
+// arguments of the env's tick, then the packed network and its width
+#define CC_ROLLOUT_ENTRIES(HH)                                                                                         \
+  __global__ void __launch_bounds__(256, 2) HipClassicControlAcrobotEnvRollout_H##HH(                                  \
+      float *state_arr, int *action_arr, int *done_arr, float *reward_arr, float *observation_arr,                     \
+      int *env_timestep_arr, int episode_length, int n_envs, CC_TICK_PARAMS, const float *policy, int hidden) {        \
+    extern __shared__ __attribute__((aligned(16))) float cc_lds[];                                                     \
+    cc_rollout<HH>(CcAcrobot{},                                                                                        \
+                   CC_TICK_ARGS(state_arr, action_arr, done_arr, reward_arr, observation_arr, env_timestep_arr),      \
+                   cc_lds, policy, hidden);                                                                            \
+  }                                                                                                                    \
+  __global__ void __launch_bounds__(256, 2) HipClassicControlMountainCarEnvRollout_H##HH(                              \
+      float *state_arr, int *action_arr, int *done_arr, float *reward_arr, float *observation_arr,                     \
+      float min_position, float max_position, float max_speed, float goal_position, float goal_velocity, float force,  \
+      float gravity, int *env_timestep_arr, int episode_length, int n_envs, CC_TICK_PARAMS, const float *policy,       \
+      int hidden) {                                                                                                    \
+    extern __shared__ __attribute__((aligned(16))) float cc_lds[];                                                     \
+    const CcMountainCar e{min_position, max_position, max_speed, goal_position, goal_velocity, force, gravity};        \
+    cc_rollout<HH>(e, CC_TICK_ARGS(state_arr, action_arr, done_arr, reward_arr, observation_arr, env_timestep_arr),   \
+                   cc_lds, policy, hidden);                                                                            \
+  }
+CC_ROLLOUT_ENTRIES(32)
+CC_ROLLOUT_ENTRIES(64)
 
 }  // extern "C"

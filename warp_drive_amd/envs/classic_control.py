@@ -10,6 +10,8 @@ gen_classic_control_golden.py).
 
 The device classes launch `HipClassicControl<X>EnvStep` and the fused tick `HipClassicControl<X>EnvTick` (sampling +
 step + restart of a finished replica, from the reset table or from a reset pool, `ticks_per_launch` ticks per launch).
+The two discrete envs also have `HipClassicControl<X>EnvRollout_H32 / _H64`: the same tick with a small policy network
+evaluated by the kernel on every tick's observation (`tick_launch(policy=...)`).
 """
 import math
 
@@ -333,9 +335,21 @@ class _CUDAClassicControlEnv(CUDAEnvironmentContext):
     ticks_per_launch = 1    # > 1: fixed-policy rollout, T ticks fused per launch
     TICK_POOL_RESET = True  # the tick kernel restarts a finished replica from the reset pool itself
     CONSTANTS = ()          # names of the physics constants the kernels take, in argument order
+    # the trainer runs a whole batch in one launch on these envs only when asked to
+    # (`trainer.fused_rollout_policy: "all"`); the discrete subclasses list the widths (ROLLOUT_POLICY_WIDTHS)
+    ROLLOUT_POLICY_OPT_IN = True
 
     def __init__(self, *args, **kwargs):
         CUDAEnvironmentContext.__init__(self)
+
+    def has_live_policy_rollout(self, width, n_actions):
+        """does a rollout kernel exist that evaluates the policy network itself (...Rollout_H<width>)?  (RolloutEngine asks
+        before it calls `tick_launch(policy=...)`)  The Box envs have none."""
+        widths = getattr(self, "ROLLOUT_POLICY_WIDTHS", ())
+        if isinstance(self.action_space[0], spaces.Box) or int(width) not in widths or not 1 <= int(n_actions) <= 8:
+            return False
+        name = self.cuda_step.name.replace("Step", f"Rollout_H{int(width)}")
+        return bool(self.cuda_function_manager.has_function(name))
 
     def get_data_dictionary(self):
         feed = DataFeed()
@@ -371,15 +385,37 @@ class _CUDAClassicControlEnv(CUDAEnvironmentContext):
         means, [E, 1, 1]] (Box: OU / Gaussian exploration with ou_params = (damping, stddev, scale), the draws of
         sample_ou_process).  With a reset pool the kernel draws the restart row itself (the resetter's pool RNG:
         init_reset_pool() first).  `batch` (optional) = {"obs": [T, E, 1, O] float32, "actions": [T, E, 1, 1],
-        "rewards": [T, E, 1] float32, "done": [T, E] int32} with T >= ticks_per_launch: tick k writes row k."""
+        "rewards": [T, E, 1] float32, "done": [T, E] int32} with T >= ticks_per_launch: tick k writes row k.
+        `policy` (optional, Acrobot and MountainCar) = (packed float32 CUDA tensor from
+        training.policy_kernel.pack_rollout_policy, hidden width): the launch evaluates the policy network on every
+        tick's observation itself (HipClassicControl<X>EnvRollout_H<width>, the packed weights in dynamic LDS) instead of
+        reading `probabilities`, which then only says how many actions there are."""
         from warp_drive_amd.managers.function_manager import _stream_tag
         from warp_drive_amd.rollout import UnsupportedRolloutShape
 
-        if policy is not None:
-            raise UnsupportedRolloutShape(f"{type(self).__name__} has no in-kernel policy")
         assert env_range is None and len(probabilities) == 1
         fm, dm = self.cuda_function_manager, self.cuda_data_manager
         name = self.cuda_step.name.replace("Step", "Tick")
+        shared, pol_args = 0, []
+        if policy is not None:
+            try:
+                packed, width = policy
+                width, n_act = int(width), int(probabilities[0].shape[-1])
+            except (TypeError, ValueError) as err:
+                raise UnsupportedRolloutShape(f"policy = (packed weights, hidden width), not {policy!r}") from err
+            if not self.has_live_policy_rollout(width, n_act):
+                raise UnsupportedRolloutShape(f"{type(self).__name__} has no in-kernel policy of width {width} with "
+                                              f"{n_act} actions")
+            import torch
+
+            O = int(dm.get_shape(_OBSERVATIONS)[-1])
+            n_w = O * width + width + width * width + width + n_act * width + n_act
+            if not (getattr(packed, "is_cuda", False) and packed.dtype == torch.float32 and packed.is_contiguous()
+                    and packed.numel() == n_w):
+                raise UnsupportedRolloutShape(f"the packed policy must be a contiguous float32 CUDA tensor of {n_w} "
+                                              f"elements (observation {O}, width {width}, {n_act} actions)")
+            name = self.cuda_step.name.replace("Step", f"Rollout_H{width}")
+            shared, pol_args = 4 * n_w, [packed, np.int32(width)]
         fm.initialize_functions([name])
         _, reset_args, _, _ = resetter.fused_launch(dm, 0, 0)  # builds / refreshes the descriptor table
         _, args, block, grid, _ = self.step_launch()
@@ -422,8 +458,8 @@ class _CUDAClassicControlEnv(CUDAEnvironmentContext):
         else:
             ou_args = [null, np.float32(0), np.float32(0), np.float32(0)]
         args = list(args) + [sampler.rng_state, probs, np.int32(probs.shape[-1]), reset_args[0], reset_args[1],
-                             _stream_tag("tick"), np.int32(T)] + batch_args + pool_args + ou_args
-        return fm.get_function(name), args, block, grid, 0
+                             _stream_tag("tick"), np.int32(T)] + batch_args + pool_args + ou_args + pol_args
+        return fm.get_function(name), args, block, grid, shared
 
     def step(self, actions=None):
         self.timestep += 1
@@ -434,12 +470,16 @@ class _CUDAClassicControlEnv(CUDAEnvironmentContext):
 
 
 class CUDAClassicControlAcrobotEnv(_CUDAClassicControlEnv, ClassicControlAcrobotEnv):
+    ROLLOUT_POLICY_WIDTHS = (32, 64)   # HipClassicControlAcrobotEnvRollout_H<width>
+
     def __init__(self, *args, **kwargs):
         ClassicControlAcrobotEnv.__init__(self, *args, **kwargs)
         _CUDAClassicControlEnv.__init__(self)
 
 
 class CUDAClassicControlMountainCarEnv(_CUDAClassicControlEnv, ClassicControlMountainCarEnv):
+    ROLLOUT_POLICY_WIDTHS = (32, 64)   # HipClassicControlMountainCarEnvRollout_H<width>
+
     CONSTANTS = ("min_position", "max_position", "max_speed", "goal_position", "goal_velocity", "force", "gravity")
 
     def __init__(self, *args, **kwargs):

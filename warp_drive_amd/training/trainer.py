@@ -294,13 +294,19 @@ class Trainer:
         # csrc/kernels/cartpole.hip; TagGridWorld with 5 agents and full observations: tag_gridworld_n5.hip -- two hidden
         # layers of 32 / 64 units, one head) run all `batch_len` ticks of a training batch -- policy forward, sampling,
         # step, reset, recording of the batch rows -- in a single launch.  `trainer.fused_rollout_policy: False` keeps
-        # the per-tick path.
+        # the per-tick path.  Envs that say ROLLOUT_POLICY_OPT_IN (Acrobot, MountainCar: envs/classic_control.py) take
+        # the single launch only with `trainer.fused_rollout_policy: "all"`.
         self._batch_rollout = None
         self._setup_batch_rollout(env_wrapper, tcfg)
 
     def _setup_batch_rollout(self, env_wrapper, tcfg):
         env = env_wrapper.env
-        if not (bool(tcfg.get("fused_rollout_policy", True)) and self.engine.fused and self._rollout_dtype is None
+        wanted = tcfg.get("fused_rollout_policy", True)
+        if isinstance(wanted, str) and wanted != "all":
+            raise ValueError(f"trainer.fused_rollout_policy: True, False or \"all\", not {wanted!r}")
+        if getattr(env, "ROLLOUT_POLICY_OPT_IN", False) and wanted != "all":
+            return
+        if not (bool(wanted) and self.engine.fused and self._rollout_dtype is None
                 and hasattr(env, "ROLLOUT_POLICY_WIDTHS") and self.batch_len > 1 and len(self.head_sizes) == 1
                 and self.head_sizes[0] <= 8):
             return
