@@ -446,7 +446,8 @@ __global__ void HipClassicControlCartPoleEnvTick(
     cp_tick_impl<0, false>(nullptr, state_arr, action_arr, done_arr, reward_arr, observation_arr, gravity, masspole, total_mass, length, polemass_length, force_mag, tau, theta_threshold_radians, x_threshold, env_timestep_arr, episode_length, n_envs, rng_state, probs, n_actions, reset_table, n_reset_arrays, stream_tag, ticks, obs_batch, action_batch, reward_batch, done_batch, policy, hidden, invariant_divide_ok);
 }
 
-// the rollout with a live policy (weights in dynamic LDS); `hidden` must equal the entry's width
+// the rollout with a live policy (weights in dynamic LDS); `hidden` must equal the entry's width and n_actions fit the
+// registers, as classic_control.hip::cc_rollout: otherwise the launch does nothing
 #define WD_CP_ROLLOUT(HH)                                                                          \
   __global__ void __launch_bounds__(256, 2) HipClassicControlCartPoleEnvRollout_H##HH(             \
     float4 *state_arr, int *action_arr, int *done_arr, \
@@ -458,6 +459,8 @@ __global__ void HipClassicControlCartPoleEnvTick(
     int stream_tag, int ticks, float4 *obs_batch, int *action_batch, float *reward_batch, int *done_batch, \
     const float *policy, int hidden, int invariant_divide_ok) {           \
     extern __shared__ __attribute__((aligned(16))) float cp_lds[];                                 \
+    /* (uniform) another width or more actions than cp_policy_cum keeps in registers: no tick */   \
+    if (hidden != HH || n_actions < 1 || n_actions > CP_MAX_REG_ACTIONS || policy == nullptr) return; \
     if (obs_batch)                                                                                 \
       cp_tick_impl<HH, true>(cp_lds, state_arr, action_arr, done_arr, reward_arr, observation_arr, gravity, masspole, total_mass, length, polemass_length, force_mag, tau, theta_threshold_radians, x_threshold, env_timestep_arr, episode_length, n_envs, rng_state, probs, n_actions, reset_table, n_reset_arrays, stream_tag, ticks, obs_batch, action_batch, reward_batch, done_batch, policy, hidden, invariant_divide_ok); \
     else                                                                                           \
