@@ -376,6 +376,133 @@ __device__ __forceinline__ void cp_tick_impl(float *cp_weights,
   }
 }
 
+// ---- evaluation: ONE episode of every replica in one launch (the ...EnvEvaluate_H<H> entries), greedy or sampled; the
+// Cartpole counterpart of classic_control.hip::cc_evaluate_impl.  cp_policy_probs is cp_policy_cum up to and including
+// the division -- the same loads, fmaf chains and softmax -- and returns the probabilities p[a] = e[a] / sum themselves
+// (oracle/cartpole_np.py::policy_probabilities), which the greedy scan needs; the sampled draw forms cp_policy_cum's
+// running sums from them with the same two expressions.
+template <int H>
+__device__ __forceinline__ void cp_policy_probs(const float *w, const float4 &s, int n_actions,
+                                                float (&prob)[CP_MAX_REG_ACTIONS]) {
+  const float *W0 = w, *b0 = W0 + 4 * H, *W1 = b0 + H, *b1 = W1 + H * H, *Wp = b1 + H, *bp = Wp + n_actions * H;
+  float h1[H], h2[H];
+#pragma unroll
+  for (int i = 0; i < H; ++i) {
+    const float4 wr = *(const float4 *)(W0 + 4 * i);
+    float acc = b0[i];
+    acc = fmaf(wr.x, s.x, acc); acc = fmaf(wr.y, s.y, acc); acc = fmaf(wr.z, s.z, acc); acc = fmaf(wr.w, s.w, acc);
+    h1[i] = fmaxf(acc, 0.0f);
+  }
+#pragma unroll
+  for (int i = 0; i < H; ++i) {
+    float acc = b1[i];
+#pragma unroll
+    for (int j = 0; j < H; j += 4) {
+      const float4 wr = *(const float4 *)(W1 + i * H + j);
+      acc = fmaf(wr.x, h1[j], acc); acc = fmaf(wr.y, h1[j + 1], acc);
+      acc = fmaf(wr.z, h1[j + 2], acc); acc = fmaf(wr.w, h1[j + 3], acc);
+    }
+    h2[i] = fmaxf(acc, 0.0f);
+  }
+  float logit[CP_MAX_REG_ACTIONS], m = -__builtin_inff();
+#pragma unroll
+  for (int a = 0; a < CP_MAX_REG_ACTIONS; ++a) {
+    logit[a] = -__builtin_inff();
+    if (a < n_actions) {
+      float acc = bp[a];
+#pragma unroll
+      for (int j = 0; j < H; j += 4) {
+        const float4 wr = *(const float4 *)(Wp + a * H + j);
+        acc = fmaf(wr.x, h2[j], acc); acc = fmaf(wr.y, h2[j + 1], acc);
+        acc = fmaf(wr.z, h2[j + 2], acc); acc = fmaf(wr.w, h2[j + 3], acc);
+      }
+      logit[a] = acc;
+      m = fmaxf(m, acc);
+    }
+  }
+  float e[CP_MAX_REG_ACTIONS], sum = 0.0f;
+#pragma unroll
+  for (int a = 0; a < CP_MAX_REG_ACTIONS; ++a) {
+    e[a] = (a < n_actions) ? expf(logit[a] - m) : 0.0f;
+    sum += e[a];
+  }
+#pragma unroll
+  for (int a = 0; a < CP_MAX_REG_ACTIONS; ++a) prob[a] = e[a] / sum;
+}
+
+// One lane per replica: the state (= the observation the network reads, as in cp_tick_impl) and the timestep are loaded
+// once, then at most `ticks` ticks of (network -> action -> cp_euler<false>), stopping at the first finished tick; the
+// terminal tick counts (sum += 1, steps += 1 before the test).  use_argmax: the first maximum of the probabilities
+// (the standalone sampler's strict-'<' scan); otherwise the counting draw with the Philox counters of the
+// fixed-probability tick.  WRITES eval_reward_sum / eval_steps / eval_done [n_envs] (eval_done: 1, or 0 when `ticks` ran
+// out first), row k of `action_trace` [ticks, n_envs] (optional) while the replica runs and, in sampled mode only, the
+// replica's epoch word += steps -- nothing else.  No restart: no reset table.  The guard is the rollout entries'.
+template <int H>
+__device__ __forceinline__ void cp_evaluate_impl(float *cp_weights, const float4 *state_arr, const CpPhysics &p,
+                                                 const int *env_timestep_arr, int episode_length, int n_envs,
+                                                 uint32_t *rng_state, int n_actions, int stream_tag, int ticks,
+                                                 const float *policy, int hidden, int use_argmax,
+                                                 float *eval_reward_sum, int *eval_steps, int *eval_done,
+                                                 int *action_trace) {
+  if (hidden != H || n_actions < 1 || n_actions > CP_MAX_REG_ACTIONS || policy == nullptr) return;  // (uniform)
+  const int n_w = 4 * H + H + H * H + H + n_actions * H + n_actions;
+  for (int i = threadIdx.x; i < n_w; i += blockDim.x) cp_weights[i] = policy[i];
+  __syncthreads();
+  const uint32_t k0 = rng_state[0], k1 = rng_state[1];
+  const bool greedy = use_argmax > 0;  // (uniform)
+  for (int env = blockIdx.x * blockDim.x + threadIdx.x; env < n_envs; env += gridDim.x * blockDim.x) {
+    int t = env_timestep_arr[env];
+    float4 s = state_arr[env];
+    uint32_t epoch0 = rng_state[WD_RNG_HEADER + env];
+    // consumed HERE, before the tick loop (as in cp_tick_impl: no wait for a load inside the loop)
+    asm volatile("" : "+v"(t), "+v"(epoch0), "+v"(s.x), "+v"(s.y), "+v"(s.z), "+v"(s.w));
+    wd_u4 blk = wd_u4{0u, 0u, 0u, 0u};
+    uint32_t blk_quad = 0xffffffffu;
+    float sum = 0.0f;
+    int steps = 0, done = 0;
+    int *trace = action_trace ? action_trace + env : nullptr;
+    for (int k = 0; k < ticks; ++k) {
+      float prob[CP_MAX_REG_ACTIONS];
+      cp_policy_probs<H>(cp_weights, s, n_actions, prob);
+      int a = 0;
+      if (greedy) {
+        float best = prob[0];
+#pragma unroll
+        for (int i = 1; i < CP_MAX_REG_ACTIONS; ++i) {
+          const bool better = i < n_actions && best < prob[i];
+          best = better ? prob[i] : best;
+          a = better ? i : a;
+        }
+      } else {
+        const float u = wd_u01_open_closed(wd_tick_draw((uint32_t)env, epoch0 + (uint32_t)k, (uint32_t)stream_tag, k0, k1,
+                                                        blk, blk_quad));
+        float cum = 0.0f;
+        int cnt = 0;
+#pragma unroll
+        for (int i = 0; i < CP_MAX_REG_ACTIONS; ++i) {
+          if (i < n_actions) cum = (i == 0) ? prob[0] : cum + prob[i];
+          cnt += (i < n_actions && cum < u) ? 1 : 0;
+        }
+        a = min(cnt, n_actions - 1);
+      }
+      if (trace) {
+        wd_store_untracked(trace, a);  // (untracked: the loop never reads it back)
+        trace += n_envs;
+      }
+      t += 1;
+      const bool terminated = cp_euler<false>(s, a, p);
+      sum += 1.0f;
+      steps += 1;
+      done = ((t == episode_length) || terminated) ? 1 : 0;
+      if (done) break;
+    }
+    eval_reward_sum[env] = sum;
+    eval_steps[env] = steps;
+    eval_done[env] = done;
+    if (!greedy) rng_state[WD_RNG_HEADER + env] = epoch0 + (uint32_t)steps;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -468,5 +595,26 @@ __global__ void HipClassicControlCartPoleEnvTick(
   }
 WD_CP_ROLLOUT(32)
 WD_CP_ROLLOUT(64)
+
+// one episode of every replica with the policy inside the kernel (cp_evaluate_impl): the step's arguments (read only),
+// then what the evaluation takes
+#define WD_CP_EVALUATE(HH)                                                                         \
+  __global__ void __launch_bounds__(256, 2) HipClassicControlCartPoleEnvEvaluate_H##HH(            \
+    const float4 *state_arr, const int *action_arr, const int *done_arr, const float *reward_arr,  \
+    const float4 *observation_arr, float gravity, float masspole, float total_mass, float length,  \
+    float polemass_length, float force_mag, float tau, float theta_threshold_radians,              \
+    float x_threshold, const int *env_timestep_arr, int episode_length, int n_envs,                \
+    uint32_t *rng_state, int n_actions, int stream_tag, int ticks, const float *policy,            \
+    int hidden, int use_argmax, float *eval_reward_sum, int *eval_steps, int *eval_done,           \
+    int *action_trace) {                                                                           \
+    extern __shared__ __attribute__((aligned(16))) float cp_lds[];                                 \
+    const CpPhysics p{gravity, masspole, total_mass, length, polemass_length, force_mag, tau,      \
+                      theta_threshold_radians, x_threshold, 1.0f / total_mass};                    \
+    cp_evaluate_impl<HH>(cp_lds, state_arr, p, env_timestep_arr, episode_length, n_envs,           \
+                         rng_state, n_actions, stream_tag, ticks, policy, hidden, use_argmax,      \
+                         eval_reward_sum, eval_steps, eval_done, action_trace);                    \
+  }
+WD_CP_EVALUATE(32)
+WD_CP_EVALUATE(64)
 
 }  // extern "C"

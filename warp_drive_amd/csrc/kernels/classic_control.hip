@@ -1,6 +1,8 @@
 // classic_control.hip -- ClassicControl Acrobot, MountainCar, ContinuousMountainCar and Pendulum: the device step of each
 // (one thread per replica, grid-stride, as HipClassicControlCartPoleEnvStep) and one fused tick template, cc_tick_impl,
 // that samples the action, steps and restarts a finished replica `ticks` times per launch with the state in registers.
+// Acrobot and MountainCar also have cc_evaluate_impl (the ...EnvEvaluate_H<H> entries): one episode of every replica in one
+// launch with the policy network inside the kernel, greedy or sampled, writing a reward sum and a step count per replica.
 //
 // Follows the reference's device kernels, example_envs/single_agent/classic_control/{acrobot,mountain_car,
 // continuous_mountain_car,pendulum}/*_step_numba.py.  Numba's type inference is restated expression by expression
@@ -491,6 +493,148 @@ __device__ __forceinline__ void cc_rollout(const Env &e, const CcTickArgs &a, fl
   else cc_tick_impl<Env, false, H>(e, a, weights, policy);
 }
 
+// ---- evaluation: ONE episode of every replica in one launch (the ...EnvEvaluate_H<H> entries), greedy or sampled.
+// cc_policy_probs is cc_policy_cum up to and including the division: the same loads, the same fmaf chains, the same
+// softmax (maximum subtracted, expf, the sum in action order, one division per action) -- it returns the probabilities
+// p[a] = e[a] / sum themselves (what tests/classic_control_policy.py::policy_probabilities restates), which the greedy
+// scan needs; the sampled draw forms cc_policy_cum's running sums from them with the same two expressions.
+template <int H, int O>
+__device__ __forceinline__ void cc_policy_probs(const float *w, const float (&o)[O], int n_actions,
+                                                float (&prob)[CC_MAX_ACTIONS]) {
+  static_assert(O % 2 == 0 && H % 4 == 0, "the rows of W0 are read as float2, those of W1 and Wp as float4");
+  const float *W0 = w, *b0 = W0 + O * H, *W1 = b0 + H, *b1 = W1 + H * H, *Wp = b1 + H, *bp = Wp + n_actions * H;
+  float h1[H], h2[H];
+#pragma unroll
+  for (int i = 0; i < H; ++i) {
+    float acc = b0[i];
+#pragma unroll
+    for (int j = 0; j < O; j += 2) {
+      const float2 wr = *(const float2 *)(W0 + O * i + j);
+      acc = fmaf(wr.x, o[j], acc); acc = fmaf(wr.y, o[j + 1], acc);
+    }
+    h1[i] = fmaxf(acc, 0.0f);
+  }
+#pragma unroll
+  for (int i = 0; i < H; ++i) {
+    float acc = b1[i];
+#pragma unroll
+    for (int j = 0; j < H; j += 4) {
+      const float4 wr = *(const float4 *)(W1 + i * H + j);
+      acc = fmaf(wr.x, h1[j], acc); acc = fmaf(wr.y, h1[j + 1], acc);
+      acc = fmaf(wr.z, h1[j + 2], acc); acc = fmaf(wr.w, h1[j + 3], acc);
+    }
+    h2[i] = fmaxf(acc, 0.0f);
+  }
+  float logit[CC_MAX_ACTIONS], m = -__builtin_inff();
+#pragma unroll
+  for (int a = 0; a < CC_MAX_ACTIONS; ++a) {
+    logit[a] = -__builtin_inff();
+    if (a < n_actions) {  // (uniform)
+      float acc = bp[a];
+#pragma unroll
+      for (int j = 0; j < H; j += 4) {
+        const float4 wr = *(const float4 *)(Wp + a * H + j);
+        acc = fmaf(wr.x, h2[j], acc); acc = fmaf(wr.y, h2[j + 1], acc);
+        acc = fmaf(wr.z, h2[j + 2], acc); acc = fmaf(wr.w, h2[j + 3], acc);
+      }
+      logit[a] = acc;
+      m = fmaxf(m, acc);
+    }
+  }
+  float e[CC_MAX_ACTIONS], sum = 0.0f;
+#pragma unroll
+  for (int a = 0; a < CC_MAX_ACTIONS; ++a) {
+    e[a] = (a < n_actions) ? expf(logit[a] - m) : 0.0f;
+    sum += e[a];
+  }
+#pragma unroll
+  for (int a = 0; a < CC_MAX_ACTIONS; ++a) prob[a] = e[a] / sum;
+}
+
+// One lane per replica: load the state, the observation and the timestep once, then at most `ticks` ticks of
+// (network on the observation in registers -> action -> Env::step), stopping at the first non-zero done; the terminal
+// tick counts (sum += reward, steps += 1 before the test).  use_argmax: the first maximum of the probabilities (the
+// standalone sampler's strict-'<' scan); otherwise the counting draw on the running sums with the Philox counters of the
+// fixed-probability tick, wd_tick_draw(env, epoch0 + k, stream_tag).  WRITES: eval_reward_sum / eval_steps / eval_done
+// [n_envs] (eval_done = the done value that ended the episode, 0 when `ticks` ran out first), row k of `action_trace`
+// [ticks, n_envs] (optional) while the replica runs, and -- sampled mode only -- the replica's epoch word += steps.
+// Nothing else: the env's arrays are read only, there is no restart, hence no reset table and no pool.  The guard is
+// cc_rollout's.  The loads are consumed before the tick loop and the trace store is untracked (wd_common.h), as in
+// cc_tick_impl: no wait inside the loop.
+template <int H, class Env>
+__device__ __forceinline__ void cc_evaluate_impl(const Env &e, const float *state_arr, const float *observation_arr,
+                                                 const int *env_timestep_arr, int episode_length, int n_envs,
+                                                 uint32_t *rng_state, int n_actions, int stream_tag,
+                                                 int ticks, float *weights, const float *policy,
+                                                 int hidden, int use_argmax, float *eval_reward_sum, int *eval_steps,
+                                                 int *eval_done, int *action_trace) {
+  static_assert(!Env::CONT, "the in-kernel policy has a softmax head");
+  if (hidden != H || n_actions < 1 || n_actions > CC_MAX_ACTIONS || policy == nullptr) return;  // (uniform)
+  constexpr int S = Env::S, O = Env::O;
+  const int n_w = O * H + H + H * H + H + n_actions * H + n_actions;
+  for (int i = threadIdx.x; i < n_w; i += blockDim.x) weights[i] = policy[i];
+  __syncthreads();
+  const uint32_t k0 = rng_state[0], k1 = rng_state[1];
+  const bool greedy = use_argmax > 0;  // (uniform)
+  for (int env = blockIdx.x * blockDim.x + threadIdx.x; env < n_envs; env += gridDim.x * blockDim.x) {
+    int t = env_timestep_arr[env];
+    float s[S], o[O];
+    cc_load_row<S>(state_arr, env, s);
+    cc_load_row<O>(observation_arr, env, o);
+    uint32_t epoch0 = rng_state[WD_RNG_HEADER + env];
+    asm volatile("" : "+v"(t), "+v"(epoch0));
+#pragma unroll
+    for (int i = 0; i < S; ++i) asm volatile("" : "+v"(s[i]));
+#pragma unroll
+    for (int i = 0; i < O; ++i) asm volatile("" : "+v"(o[i]));
+    wd_u4 blk = wd_u4{0u, 0u, 0u, 0u};
+    uint32_t blk_quad = 0xffffffffu;
+    float sum = 0.0f;
+    int steps = 0, done = 0;
+    int *trace = action_trace ? action_trace + env : nullptr;
+    for (int k = 0; k < ticks; ++k) {
+      float prob[CC_MAX_ACTIONS];
+      cc_policy_probs<H, O>(weights, o, n_actions, prob);
+      int act = 0;
+      if (greedy) {
+        float best = prob[0];
+#pragma unroll
+        for (int i = 1; i < CC_MAX_ACTIONS; ++i) {
+          const bool better = i < n_actions && best < prob[i];
+          best = better ? prob[i] : best;
+          act = better ? i : act;
+        }
+      } else {
+        const float u = wd_u01_open_closed(wd_tick_draw((uint32_t)env, epoch0 + (uint32_t)k, (uint32_t)stream_tag,
+                                                        k0, k1, blk, blk_quad));
+        float cum = 0.0f;
+        int cnt = 0;
+#pragma unroll
+        for (int i = 0; i < CC_MAX_ACTIONS; ++i) {
+          if (i < n_actions) cum = (i == 0) ? prob[0] : cum + prob[i];
+          cnt += (i < n_actions && cum < u) ? 1 : 0;
+        }
+        act = min(cnt, n_actions - 1);
+      }
+      if (trace) {
+        wd_store_untracked(trace, act);
+        trace += n_envs;
+      }
+      t += 1;
+      float rew;
+      const int term = e.step(s, act, o, rew);
+      sum += rew;
+      steps += 1;
+      done = (t == episode_length) ? 1 : term;
+      if (done) break;
+    }
+    eval_reward_sum[env] = sum;
+    eval_steps[env] = steps;
+    eval_done[env] = done;
+    if (!greedy) rng_state[WD_RNG_HEADER + env] = epoch0 + (uint32_t)steps;
+  }
+}
+
 }  // namespace
 
 // the arguments of every tick kernel after the env's step arguments
@@ -595,5 +739,35 @@ __global__ void __launch_bounds__(256) HipClassicControlPendulumEnvTick(float *s
   }
 CC_ROLLOUT_ENTRIES(32)
 CC_ROLLOUT_ENTRIES(64)
+
+// one episode of every replica with the policy inside the kernel (cc_evaluate_impl): the env's step arguments (read
+// only), then what the evaluation takes
+#define CC_EVALUATE_PARAMS                                                                                             \
+  uint32_t *rng_state, int n_actions, int stream_tag, int ticks, const float *policy, int hidden, int use_argmax,      \
+      float *eval_reward_sum, int *eval_steps, int *eval_done, int *action_trace
+#define CC_EVALUATE_CALL(HH, ENV)                                                                                      \
+  cc_evaluate_impl<HH>(ENV, state_arr, observation_arr, env_timestep_arr, episode_length, n_envs, rng_state,           \
+                       n_actions, stream_tag, ticks, cc_lds, policy, hidden, use_argmax,    \
+                       eval_reward_sum, eval_steps, eval_done, action_trace)
+#define CC_EVALUATE_ENTRIES(HH)                                                                                        \
+  __global__ void __launch_bounds__(256, 2) HipClassicControlAcrobotEnvEvaluate_H##HH(                                 \
+      const float *state_arr, const int *action_arr, const int *done_arr, const float *reward_arr,                     \
+      const float *observation_arr, const int *env_timestep_arr, int episode_length, int n_envs,                       \
+      CC_EVALUATE_PARAMS) {                                                                                            \
+    extern __shared__ __attribute__((aligned(16))) float cc_lds[];                                                     \
+    const CcAcrobot e{};                                                                                               \
+    CC_EVALUATE_CALL(HH, e);                                                                                           \
+  }                                                                                                                    \
+  __global__ void __launch_bounds__(256, 2) HipClassicControlMountainCarEnvEvaluate_H##HH(                             \
+      const float *state_arr, const int *action_arr, const int *done_arr, const float *reward_arr,                     \
+      const float *observation_arr, float min_position, float max_position, float max_speed, float goal_position,      \
+      float goal_velocity, float force, float gravity, const int *env_timestep_arr, int episode_length, int n_envs,    \
+      CC_EVALUATE_PARAMS) {                                                                                            \
+    extern __shared__ __attribute__((aligned(16))) float cc_lds[];                                                     \
+    const CcMountainCar e{min_position, max_position, max_speed, goal_position, goal_velocity, force, gravity};        \
+    CC_EVALUATE_CALL(HH, e);                                                                                           \
+  }
+CC_EVALUATE_ENTRIES(32)
+CC_EVALUATE_ENTRIES(64)
 
 }  // extern "C"

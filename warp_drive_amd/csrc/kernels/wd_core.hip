@@ -285,6 +285,26 @@ __global__ void reset_when_done_from_pool(uint32_t *rng_state, uint32_t *data,
   }
 }
 
+// --------------------------------------------------------------------- evaluation
+// First-episode accumulation of the per-tick evaluation (Trainer.evaluate_episodes): after tick `tick`, add every
+// replica's rewards [n_envs, n_agents] into `reward_sum` while its FIRST episode runs.  `end_tick` [n_envs] (preset to
+// -1) is the tick that episode ended on: a replica is live at tick k iff end_tick < 0 || end_tick == k, and the
+// agent-0 thread of a live replica whose done flag is set writes end_tick = k (steps = end_tick + 1; the terminal tick
+// counts).  One thread per (replica, agent), grid-stride, any geometry: the threads of a replica may sit in different
+// blocks and read end_tick before or after that write -- they see -1 or k, and both mean "live at tick k".
+__global__ void HipEvaluateAccumulate(const float *__restrict__ rewards, const int *__restrict__ done,
+                                      float *__restrict__ reward_sum, int *end_tick, int tick, int n_agents,
+                                      int n_envs) {
+  const long total = (long)n_envs * n_agents;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int env = (int)(i / n_agents);
+    const int end = end_tick[env];
+    if (end >= 0 && end != tick) continue;  // its first episode is over
+    reward_sum[i] += rewards[i];
+    if (i - (long)env * n_agents == 0 && done[env] != 0) end_tick[env] = tick;
+  }
+}
+
 // ---------------------------------------------------------------------------- log
 // Episode logger (log.cu:11-62): copies one replica's [n_agents, feature_dim] slice
 // into row `timestep` of a [T+1, n_agents, feature_dim] buffer.

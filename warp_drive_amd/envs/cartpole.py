@@ -150,6 +150,57 @@ class CUDAClassicControlCartPoleEnv(CUDAEnvironmentContext, ClassicControlCartPo
         name = self.cuda_step.name.replace("Step", f"Rollout_H{int(width)}")
         return int(width) in self.ROLLOUT_POLICY_WIDTHS and int(n_actions) <= 8 and self.cuda_function_manager.has_function(name)
 
+    def has_live_policy_evaluate(self, width, n_actions):
+        """does an evaluation kernel exist that runs one episode of every replica with the policy network inside it
+        (HipClassicControlCartPoleEnvEvaluate_H<width>, Trainer.evaluate_episodes)?"""
+        name = self.cuda_step.name.replace("Step", f"Evaluate_H{int(width)}")
+        return bool(int(width) in self.ROLLOUT_POLICY_WIDTHS and 1 <= int(n_actions) <= 8
+                    and self.cuda_function_manager.has_function(name))
+
+    def evaluate_launch(self, sampler, policy, use_argmax, outputs, action_trace=None, ticks=None, n_actions=None):
+        """One episode of every replica in ONE launch (HipClassicControlCartPoleEnvEvaluate_H<width>): from the state
+        and timestep the arrays hold, at most `ticks` (default: episode_length) ticks of policy network (on the state,
+        which is Cartpole's observation) -> action (use_argmax: the first maximum of the probabilities; else the
+        counting draw of the fused tick) -> Euler step, up to the first done.  policy = (packed float32 CUDA tensor,
+        hidden width) as in `tick_launch`; `n_actions` defaults to the env's two.  outputs = {"reward_sum": float32,
+        "steps": int32, "done": int32}, CUDA tensors of at least n_envs elements; `action_trace` (optional) int32
+        [>= ticks, n_envs]: row k = tick k's actions.  The launch writes those, and in sampled mode the sampler's epoch
+        words; the env's arrays are read only.  Returns (function, arguments, block, grid, shared bytes)."""
+        from warp_drive_amd.managers.function_manager import _stream_tag
+        from warp_drive_amd.rollout import UnsupportedRolloutShape
+        import torch
+
+        fm, dm = self.cuda_function_manager, self.cuda_data_manager
+        try:
+            packed, width = policy
+            width = int(width)
+            n_act = int(self.action_space[0].n if n_actions is None else n_actions)
+        except (TypeError, ValueError) as err:
+            raise UnsupportedRolloutShape(f"policy = (packed weights, hidden width), not {policy!r}") from err
+        if not self.has_live_policy_evaluate(width, n_act):
+            raise UnsupportedRolloutShape(f"no in-kernel evaluation of width {width} with {n_act} actions")
+        E = int(dm.meta_info("n_envs"))
+        n_w = 4 * width + width + width * width + width + n_act * width + n_act
+        if not (getattr(packed, "is_cuda", False) and packed.dtype == torch.float32 and packed.is_contiguous()
+                and packed.numel() == n_w):
+            raise UnsupportedRolloutShape(f"the packed policy must be a contiguous float32 CUDA tensor of {n_w} "
+                                          f"elements (width {width}, {n_act} actions)")
+        T = int(self.episode_length if ticks is None else ticks)
+        for key, dtype in (("reward_sum", torch.float32), ("steps", torch.int32), ("done", torch.int32)):
+            t = outputs[key]
+            assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.numel() >= E, (key, tuple(t.shape), t.dtype)
+        if action_trace is not None:
+            t = action_trace
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and t.shape[0] >= T and \
+                int(np.prod(t.shape[1:])) == E, ("action_trace", tuple(t.shape), t.dtype)
+        name = self.cuda_step.name.replace("Step", f"Evaluate_H{width}")
+        fm.initialize_functions([name])
+        _, args, block, grid, _ = self.step_launch()
+        args = list(args) + [sampler.rng_state, np.int32(n_act), _stream_tag("tick"), np.int32(T), packed, np.int32(width),
+                             np.int32(1 if use_argmax else 0), outputs["reward_sum"], outputs["steps"], outputs["done"],
+                             np.uint64(0) if action_trace is None else action_trace]
+        return fm.get_function(name), args, block, grid, 4 * n_w
+
     def tick_launch(self, sampler, probabilities, resetter, env_range=None, batch=None, policy=None):
         """Fused rollout tick(s): sample + step + reset of a finished replica, `ticks_per_launch`
         times in ONE launch (HipClassicControlCartPoleEnvTick).  probabilities = [float32 CUDA tensor

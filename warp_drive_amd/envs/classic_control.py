@@ -11,7 +11,9 @@ gen_classic_control_golden.py).
 The device classes launch `HipClassicControl<X>EnvStep` and the fused tick `HipClassicControl<X>EnvTick` (sampling +
 step + restart of a finished replica, from the reset table or from a reset pool, `ticks_per_launch` ticks per launch).
 The two discrete envs also have `HipClassicControl<X>EnvRollout_H32 / _H64`: the same tick with a small policy network
-evaluated by the kernel on every tick's observation (`tick_launch(policy=...)`).
+evaluated by the kernel on every tick's observation (`tick_launch(policy=...)`), and
+`HipClassicControl<X>EnvEvaluate_H32 / _H64`: one episode of every replica in one launch, greedy or sampled
+(`evaluate_launch`).
 """
 import math
 
@@ -350,6 +352,62 @@ class _CUDAClassicControlEnv(CUDAEnvironmentContext):
             return False
         name = self.cuda_step.name.replace("Step", f"Rollout_H{int(width)}")
         return bool(self.cuda_function_manager.has_function(name))
+
+    def has_live_policy_evaluate(self, width, n_actions):
+        """does an evaluation kernel exist that runs one episode of every replica with the policy network inside it
+        (...Evaluate_H<width>, Trainer.evaluate_episodes)?  The same widths and action counts as the rollout entries;
+        the Box envs have none."""
+        widths = getattr(self, "ROLLOUT_POLICY_WIDTHS", ())
+        if isinstance(self.action_space[0], spaces.Box) or int(width) not in widths or not 1 <= int(n_actions) <= 8:
+            return False
+        name = self.cuda_step.name.replace("Step", f"Evaluate_H{int(width)}")
+        return bool(self.cuda_function_manager.has_function(name))
+
+    def evaluate_launch(self, sampler, policy, use_argmax, outputs, action_trace=None, ticks=None, n_actions=None):
+        """One episode of every replica in ONE launch (HipClassicControl<X>EnvEvaluate_H<width>): from the state,
+        observation and timestep the arrays hold, at most `ticks` (default: episode_length) ticks of policy network ->
+        action (use_argmax: the first maximum of the probabilities; else the counting draw of the fused tick) -> step,
+        up to the first done.  policy = (packed float32 CUDA tensor, hidden width) as in `tick_launch`; `n_actions`
+        defaults to the env's action count.  outputs = {"reward_sum": float32, "steps": int32, "done": int32}, CUDA
+        tensors of at least n_envs elements; `action_trace` (optional) int32 [>= ticks, n_envs]: row k = tick k's
+        actions.  The launch writes those, and in sampled mode the sampler's epoch words; the env's arrays are read only.
+        Returns (function, arguments, block, grid, shared bytes)."""
+        from warp_drive_amd.managers.function_manager import _stream_tag
+        from warp_drive_amd.rollout import UnsupportedRolloutShape
+        import torch
+
+        fm, dm = self.cuda_function_manager, self.cuda_data_manager
+        try:
+            packed, width = policy
+            width = int(width)
+            n_act = int(self.action_space[0].n if n_actions is None else n_actions)
+        except (TypeError, ValueError, AttributeError) as err:
+            raise UnsupportedRolloutShape(f"policy = (packed weights, hidden width), not {policy!r}") from err
+        if not self.has_live_policy_evaluate(width, n_act):
+            raise UnsupportedRolloutShape(f"{type(self).__name__} has no in-kernel evaluation of width {width} with "
+                                          f"{n_act} actions")
+        E = int(dm.meta_info("n_envs"))
+        O = int(dm.get_shape(_OBSERVATIONS)[-1])
+        n_w = O * width + width + width * width + width + n_act * width + n_act
+        if not (getattr(packed, "is_cuda", False) and packed.dtype == torch.float32 and packed.is_contiguous()
+                and packed.numel() == n_w):
+            raise UnsupportedRolloutShape(f"the packed policy must be a contiguous float32 CUDA tensor of {n_w} "
+                                          f"elements (observation {O}, width {width}, {n_act} actions)")
+        T = int(self.episode_length if ticks is None else ticks)
+        for key, dtype in (("reward_sum", torch.float32), ("steps", torch.int32), ("done", torch.int32)):
+            t = outputs[key]
+            assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.numel() >= E, (key, tuple(t.shape), t.dtype)
+        if action_trace is not None:
+            t = action_trace
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and t.shape[0] >= T and \
+                int(np.prod(t.shape[1:])) == E, ("action_trace", tuple(t.shape), t.dtype)
+        name = self.cuda_step.name.replace("Step", f"Evaluate_H{width}")
+        fm.initialize_functions([name])
+        _, args, block, grid, _ = self.step_launch()
+        args = list(args) + [sampler.rng_state, np.int32(n_act), _stream_tag("tick"), np.int32(T), packed, np.int32(width),
+                             np.int32(1 if use_argmax else 0), outputs["reward_sum"], outputs["steps"], outputs["done"],
+                             np.uint64(0) if action_trace is None else action_trace]
+        return fm.get_function(name), args, block, grid, 4 * n_w
 
     def get_data_dictionary(self):
         feed = DataFeed()

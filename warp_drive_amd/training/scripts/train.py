@@ -3,6 +3,7 @@
 warp_drive/training/scripts/example_training_script_pycuda.py:41-225).
 
     python -m warp_drive_amd.training.scripts.train --env tag_continuous [--iters 5]
+    python -m warp_drive_amd.training.scripts.train --env single_cartpole --evaluate greedy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
         -m warp_drive_amd.training.scripts.train --env tag_continuous      # 8 x MI355X, RCCL DDP
 """
@@ -64,12 +65,20 @@ def main():
     ap.add_argument("--num_envs", type=int, default=None)
     ap.add_argument("--train_batch_size", type=int, default=None)
     ap.add_argument("--results_dir", default=None)
+    ap.add_argument("--evaluate", choices=["greedy", "sampled"], default=None,
+                    help="after training, run one episode of every replica (Trainer.evaluate_episodes) and log, per "
+                         "policy, the mean episodic reward and the mean step count")
     args = ap.parse_args()
     logging.getLogger().setLevel(logging.WARNING)
     overrides = {"trainer": {k: v for k, v in (("num_envs", args.num_envs),
                                                ("train_batch_size", args.train_batch_size)) if v is not None}}
     trainer = setup_trainer(args.env, overrides, args.results_dir)
     trainer.train(args.iters)
+    if args.evaluate is not None:
+        rewards, steps = trainer.evaluate_episodes(use_argmax=args.evaluate == "greedy")
+        for pol in trainer.policies:
+            logging.warning(f"[evaluate, {args.evaluate}, {trainer.evaluation_path}, rank {trainer.rank}] {pol}: mean "
+                            f"episodic reward {float(rewards[pol].mean()):.3f}, mean steps {float(steps[pol].mean()):.1f}")
     trainer.graceful_close()
     if trainer.rank == 0:
         print(trainer.perf_stats.get_perf_stats())

@@ -752,6 +752,122 @@ class Trainer:
             return episode_states, acts, rews, episode_probabilities
         return episode_states, acts, rews
 
+    # ------------------------------------------------------------------- evaluate_episodes
+    def _evaluation_engine(self):
+        """the single-tick engine of the per-tick evaluation: the trainer's own when the training rollout is per tick,
+        else built on first use (fused tick: sample + step + restart in one launch; envs without one: sample + step, and
+        `reset_only_done_envs()` after the flags were read, as `_tick` does)"""
+        if self._batch_rollout is None:
+            return self.engine
+        if getattr(self, "_eval_engine", None) is None:
+            engine = RolloutEngine(self.w, self.sampler, probabilities=self.probs, reset_done=True)
+            if not engine.fused:
+                engine = RolloutEngine(self.w, self.sampler, probabilities=self.probs, reset_done=False)
+            self._eval_engine = engine
+        return self._eval_engine
+
+    @torch.no_grad()
+    def _greedy_probabilities_(self):
+        """every head's rows of `self.probs` become one-hot rows at their FIRST maximum, in place: the counting draw then
+        returns exactly that index (the uniform lies in (0, 1]; the running sum is 0 before the index and 1 from it on)"""
+        for p in self.probs:
+            top = p == p.max(dim=-1, keepdim=True).values
+            p.copy_((top & (top.cumsum(dim=-1) == 1)).to(p.dtype))
+
+    def _evaluate_accumulate_launch(self, reward_sum, end_tick, tick):
+        fm = self.w.cuda_function_manager
+        fm.initialize_functions(["HipEvaluateAccumulate"])
+        E, N = self.num_envs, self.w.n_agents
+        args = [self.rewards, self.done, reward_sum, end_tick, np.int32(tick), np.int32(N), np.int32(E)]
+        return fm.get_function("HipEvaluateAccumulate"), args, (256, 1, 1), (max(1, min(4096, (E * N + 255) // 256)), 1), 0
+
+    def _one_launch_evaluation(self):
+        """(env, width) when `evaluate_episodes` is one launch: the training rollout of this trainer is one launch and the
+        env has an Evaluate entry for the policy's shape; else None"""
+        env = self.w.env
+        if self._batch_rollout is None or len(self.policies) != 1 or not hasattr(env, "has_live_policy_evaluate"):
+            return None
+        pol = self.policies[0]
+        obs_size = flattened_obs_size(env.observation_space[self.policy_map[pol][0]])
+        width = rollout_policy_width(self.models[pol], obs_size, getattr(env, "ROLLOUT_POLICY_WIDTHS", ()))
+        if width is None or len(self.head_sizes) != 1 or not env.has_live_policy_evaluate(width, self.head_sizes[0]):
+            return None
+        return env, width
+
+    @torch.no_grad()
+    def evaluate_episodes(self, **sample_params):
+        """Run every replica for ONE episode with the current policies and return (episodic_reward_sum,
+        episodic_step_sum), two dicts keyed by policy (reference trainer_base.py, `evaluate_episodes`):
+        episodic_reward_sum[policy] is np.float32 [num_envs, n_agents_of_policy], episodic_step_sum[policy] np.int32
+        [num_envs].  `use_argmax=True`: every head's action is the first maximum of its float32 probabilities (the
+        standalone sampler's strict-'<' scan); otherwise the actions are sampled exactly as the training rollout samples.
+
+        1. The call starts with `reset_all_envs()`, as the reference does.
+        2. Each replica contributes its FIRST episode and nothing after it.
+        3. Rewards are added in tick order in float32, and the terminal tick counts: a Cartpole episode that ends on its
+           L-th tick has sum L and step count L.
+        4. Two DELIBERATE DEPARTURES from the reference's loop: the reference skips the terminal tick's reward, and it
+           counts a replica again if its step kernel clears `_done_`.  Counting the terminal tick makes evaluation agree
+           with how `_tick` forms "Mean episodic reward".
+        5. Every replica finishes within `episode_length` ticks: the time-out sets done.
+        6. After the call the envs are in the state `reset_all_envs()` leaves and the running per-episode accumulators
+           (`_ep_reward`) are zero; `_ep_sum` / `_ep_cnt` are untouched.
+        7. A greedy evaluation on the one-launch path leaves the sampler's RNG words untouched; a sampled one advances a
+           replica's epoch word by the number of ticks it ran.
+        8. Multi-GPU: each rank evaluates its own replicas and returns its own arrays.
+
+        Two paths; `self.evaluation_path` says which one the last call took.  "one launch": when the training rollout of
+        this trainer is one launch and the env has an Evaluate entry (Cartpole by default, Acrobot / MountainCar under
+        `fused_rollout_policy: "all"`), one kernel runs the whole episode of every replica with the policy inside it and
+        writes two numbers per replica.  "per tick": everything else -- policy forward, (one-hot rows when greedy,) the
+        single-tick engine, HipEvaluateAccumulate on `rewards` / `_done_`, `episode_length` times, with no host
+        synchronisation per tick (one all-finished check every 32 ticks) and one pull at the end.  Restarted replicas
+        keep stepping and are masked out."""
+        use_argmax = bool(sample_params.get("use_argmax", False))
+        E, N, T = self.num_envs, self.w.n_agents, int(self.w.episode_length)
+        self.w.reset_all_envs()
+        one = self._one_launch_evaluation()
+        if one is not None:
+            env, width = one
+            pol = self.policies[0]
+            br = self._batch_rollout
+            br["pack"](self.models[pol], out=br["packed"][pol])  # the current weights
+            out = {"reward_sum": torch.zeros(E, dtype=torch.float32, device=self.device),
+                   "steps": torch.zeros(E, dtype=torch.int32, device=self.device),
+                   "done": torch.zeros(E, dtype=torch.int32, device=self.device)}
+            fn, args, block, grid, shared = env.evaluate_launch(self.sampler, policy=(br["packed"][pol], width),
+                                                                use_argmax=use_argmax, outputs=out, ticks=T)
+            fn(*args, block=block, grid=grid, shared=shared)
+            reward_sum = out["reward_sum"].cpu().numpy().reshape(E, N)
+            steps = out["steps"].cpu().numpy()
+            self.evaluation_path = "one launch"
+        else:
+            engine = self._evaluation_engine()
+            reward_sum_dev = torch.zeros((E, N), dtype=torch.float32, device=self.device)
+            end_tick = torch.full((E,), -1, dtype=torch.int32, device=self.device)
+            for k in range(T):
+                self._policy_probabilities()
+                if use_argmax:
+                    self._greedy_probabilities_()
+                engine.run(1)
+                fn, args, block, grid, shared = self._evaluate_accumulate_launch(reward_sum_dev, end_tick, k)
+                fn(*args, block=block, grid=grid, shared=shared)
+                if not engine.fused:
+                    self.w.reset_only_done_envs()
+                if (k + 1) % 32 == 0 and k + 1 < T and bool((end_tick >= 0).all()):
+                    break
+            reward_sum = reward_sum_dev.cpu().numpy()
+            steps = (end_tick.cpu().numpy() + 1).astype(np.int32)
+            assert (steps > 0).all(), "a replica did not finish within episode_length ticks"
+            self.w.reset_all_envs()
+            self.evaluation_path = "per tick"
+        for pol in self.policies:
+            self._ep_reward[pol].zero_()
+        episodic_reward_sum = {pol: np.ascontiguousarray(reward_sum[:, self.policy_map[pol]], dtype=np.float32)
+                               for pol in self.policies}
+        episodic_step_sum = {pol: steps.astype(np.int32).copy() for pol in self.policies}
+        return episodic_reward_sum, episodic_step_sum
+
     def graceful_close(self):
         torch.cuda.synchronize()
         wdd.barrier()
