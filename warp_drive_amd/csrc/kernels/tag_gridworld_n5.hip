@@ -38,6 +38,11 @@
 // subtracted, expf, one division per action -- restated in oracle/tag_gridworld_np.py::policy_probabilities.
 // Measured (profiles/r05_prepared_items_first_call.txt, 1000 replicas, 20 ticks per launch): 10.9 us per tick at
 // H = 32, 30.1 at H = 64 -- the trainer's per-tick path costs 390 - 490 us per tick of the same replicas.
+//
+// EVALUATION (`HipTagGridWorldEvaluate_N5_H32` / `_H64`, Trainer.evaluate_episodes; the TagGridWorld counterpart of
+// HipClassicControlCartPoleEnvEvaluate_H32 / _H64): ONE episode of every replica in one launch with the same two
+// networks, greedy or sampled -- the rollout's geometry, tables and tick, without recording, restart and final state
+// (gw5_evaluate below).
 #include "wd_common.h"
 #include "tag_gridworld_rewards.h"
 
@@ -122,6 +127,61 @@ __device__ __forceinline__ void gw5_policy_cum(const float *w, const float *x, f
     }
     cumv[a] = cum;
   }
+}
+
+// the action probabilities themselves (the evaluation entries: the greedy action is their first maximum): the loads,
+// fmaf chains and softmax of gw5_policy_cum, step for step, ending at the division
+template <int H>
+__device__ __forceinline__ void gw5_policy_probs(const float *w, const float *x, float (&prob)[GW5_ACTIONS]) {
+  const float *W0 = w, *b0 = W0 + H * GW5_IN_STRIDE, *W1 = b0 + H, *b1 = W1 + H * H, *Wp = b1 + H, *bp = Wp + GW5_ACTIONS * H;
+  float in[GW5_F];
+#pragma unroll
+  for (int j = 0; j < GW5_F; ++j) in[j] = x[j];
+  float h1[H], h2[H];
+#pragma unroll
+  for (int i = 0; i < H; ++i) {
+    float acc = b0[i];
+#pragma unroll
+    for (int j = 0; j < 20; j += 4) {
+      const float4 wr = *(const float4 *)(W0 + i * GW5_IN_STRIDE + j);
+      acc = fmaf(wr.x, in[j], acc); acc = fmaf(wr.y, in[j + 1], acc);
+      acc = fmaf(wr.z, in[j + 2], acc); acc = fmaf(wr.w, in[j + 3], acc);
+    }
+    acc = fmaf(W0[i * GW5_IN_STRIDE + 20], in[20], acc);
+    h1[i] = fmaxf(acc, 0.0f);
+  }
+#pragma unroll
+  for (int i = 0; i < H; ++i) {
+    float acc = b1[i];
+#pragma unroll
+    for (int j = 0; j < H; j += 4) {
+      const float4 wr = *(const float4 *)(W1 + i * H + j);
+      acc = fmaf(wr.x, h1[j], acc); acc = fmaf(wr.y, h1[j + 1], acc);
+      acc = fmaf(wr.z, h1[j + 2], acc); acc = fmaf(wr.w, h1[j + 3], acc);
+    }
+    h2[i] = fmaxf(acc, 0.0f);
+  }
+  float logit[GW5_ACTIONS], m = -__builtin_inff();
+#pragma unroll
+  for (int a = 0; a < GW5_ACTIONS; ++a) {
+    float acc = bp[a];
+#pragma unroll
+    for (int j = 0; j < H; j += 4) {
+      const float4 wr = *(const float4 *)(Wp + a * H + j);
+      acc = fmaf(wr.x, h2[j], acc); acc = fmaf(wr.y, h2[j + 1], acc);
+      acc = fmaf(wr.z, h2[j + 2], acc); acc = fmaf(wr.w, h2[j + 3], acc);
+    }
+    logit[a] = acc;
+    m = fmaxf(m, acc);
+  }
+  float e[GW5_ACTIONS], sum = 0.0f;
+#pragma unroll
+  for (int a = 0; a < GW5_ACTIONS; ++a) {
+    e[a] = expf(logit[a] - m);
+    sum += e[a];
+  }
+#pragma unroll
+  for (int a = 0; a < GW5_ACTIONS; ++a) prob[a] = e[a] / sum;
 }
 
 
@@ -340,6 +400,155 @@ __device__ __forceinline__ void gw5_rollout(
   }
 }
 
+// One episode of every replica with the two policies inside the kernel: the rollout's geometry (a wavefront = 12
+// replicas, lane = (local replica, agent)), its quotient tables and packed policies in LDS, its tick -- draw, network,
+// move, tag check by shuffle + ballot, image update -- but NO restart (no reset table, no restore cache), no recording
+// and no final state: positions, time step, epoch word and observation rows are loaded once, a replica runs from them
+// up to its first finished tick (or `ticks`) and stops; its lanes then only take part in the wavefront exchanges, and the
+// group's loop ends when a ballot finds no live replica.  use_argmax: the action is the first maximum of the
+// probabilities (the standalone sampler's strict-'<' scan); otherwise the rollout's counting draw on their running sums.
+// WRITES eval_reward_sum [n_envs, 5] (float32, sum += reward in tick order, the terminal tick included), eval_steps /
+// eval_done [n_envs] (done: 1, or 0 when `ticks` ran out first), action_trace [ticks, n_envs, 5] (optional) for the ticks
+// a replica ran and, in sampled mode only, every agent's epoch word += its replica's steps -- nothing else.  Replica
+// groups in blockIdx order (a block writes 300 bytes per launch: the rollout's XCD-contiguous order has nothing to merge).
+template <int H>
+__device__ __forceinline__ void gw5_evaluate(
+    const int *states_x_arr, const int *states_y_arr, const float *obs_arr, double wall_hit_penalty,
+    double tag_reward_for_tagger, double tag_penalty_for_runner, double step_cost_for_tagger, int use_full_observation,
+    int world_boundary, const int *env_timestep_arr, int episode_length, int n_agents, int n_envs, uint32_t *rng_state,
+    int stream_tag, int ticks, const int *action_table, const float *policy_tagger, const float *policy_runner,
+    int use_argmax, float *eval_reward_sum, int *eval_steps, int *eval_done, int *action_trace, float *gw5_smem) {
+  if (policy_tagger == nullptr || policy_runner == nullptr || n_agents != GW5_N || use_full_observation == 0 ||
+      world_boundary < 0 || world_boundary > GW5_MAX_COORD || episode_length < 1)
+    return;  // (uniform)
+  float *const s_obs = gw5_smem;                                // [12][5][21] the block's observation image
+  float *const s_div = s_obs + GW5_IMG;                         // [64] c / L
+  float *const s_tn = s_div + GW5_MAX_COORD + 1;                // [episode_length + 1] t / episode_length
+  float *const s_pol = s_tn + ((episode_length + 1 + 3) & ~3);  // [2][gw5_policy_floats(H)]: tagger, runner
+  GW_REWARD_TABLE(wall_hit_penalty, tag_reward_for_tagger, tag_penalty_for_runner, step_cost_for_tagger);
+  const int lane = threadIdx.x;                                 // (blocks are one wavefront)
+  const int el = lane / GW5_N, ag = lane - el * GW5_N;          // local replica (12 = none), agent
+  const uint32_t k0 = rng_state[0], k1 = rng_state[1];
+  const bool greedy = use_argmax > 0;  // (uniform)
+  int act_dx[5], act_dy[5];
+#pragma unroll
+  for (int i = 0; i < 5; ++i) { act_dx[i] = action_table[2 * i]; act_dy[i] = action_table[2 * i + 1]; }
+  {
+    const float L = (float)world_boundary;
+    if (lane <= world_boundary) s_div[lane] = (float)lane / L;
+    for (int q = lane; q <= episode_length; q += 64) s_tn[q] = (float)q / (float)episode_length;
+    for (int q = lane; q < gw5_policy_floats(H); q += 64) {
+      s_pol[q] = policy_tagger[q];
+      s_pol[gw5_policy_floats(H) + q] = policy_runner[q];
+    }
+  }
+  const float *const my_policy = s_pol + ((ag == GW5_N - 1) ? gw5_policy_floats(H) : 0);  // runner : tagger
+  float *const rep = s_obs + min(el, GW5_EPB - 1) * GW5_ROW;  // this lane's replica's five rows
+  const int runner_lane = min(el * GW5_N + GW5_N - 1, 63);
+
+  for (int env0 = blockIdx.x * GW5_EPB; env0 < n_envs; env0 += gridDim.x * GW5_EPB) {
+    const int env = env0 + el;
+    const bool active = (el < GW5_EPB) && (env < n_envs);
+    const int idx = env * GW5_N + ag;
+    const int n_in = min(GW5_EPB, n_envs - env0) * GW5_ROW;
+    const float *const obs_blk = obs_arr + (long)env0 * GW5_ROW;
+    int x = 0, y = 0, t = 0;
+    uint32_t epoch0 = 0u;
+    if (active) {
+      x = states_x_arr[idx];
+      y = states_y_arr[idx];
+      t = env_timestep_arr[env];
+      epoch0 = rng_state[WD_RNG_HEADER + idx];
+    }
+    for (int q = lane; q < n_in; q += 64) s_obs[q] = obs_blk[q];  // the observation the first action is chosen on
+    __syncthreads();
+    // consumed HERE, before the tick loop (as in gw5_rollout: no wait for a load inside the loop)
+    asm volatile("" : "+v"(x), "+v"(y), "+v"(t), "+v"(epoch0));
+    wd_u4 blk = wd_u4{0u, 0u, 0u, 0u};  // the Philox block of four consecutive ticks (wd_tick_draw)
+    uint32_t blk_quad = 0xffffffffu;
+    bool live = active;
+    float sum = 0.0f;
+    int steps = 0;
+    int *trace = action_trace ? action_trace + idx : nullptr;
+
+    for (int k = 0; k < ticks; ++k) {
+      if (__ballot(live) == 0ull) break;  // wave-uniform: every replica of the group has finished
+      // the other lanes' image writes of the previous tick, before this tick's row reads: the language-level statement
+      // of what holds anyway (LDS operations of one wavefront execute in issue order); as in gw5_rollout it compiles
+      // to nothing -- the instruction stream is identical with and without it
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      bool hit = false;
+      if (live) {
+        float u = 0.0f;
+        if (!greedy)  // the draw of tick k of T single-tick launches, as the rollout -- and, as there, BEFORE the network
+          u = wd_u01_open_closed(wd_tick_draw((uint32_t)idx, epoch0 + (uint32_t)k, (uint32_t)stream_tag, k0, k1, blk,
+                                              blk_quad));
+        float prob[GW5_ACTIONS];
+        gw5_policy_probs<H>(my_policy, rep + ag * GW5_F, prob);
+        int a = 0;
+        if (greedy) {
+          float best = prob[0];
+#pragma unroll
+          for (int i = 1; i < GW5_ACTIONS; ++i) {
+            const bool better = best < prob[i];
+            best = better ? prob[i] : best;
+            a = better ? i : a;
+          }
+        } else {
+          float cum = 0.0f;
+          int cnt = 0;
+#pragma unroll
+          for (int i = 0; i < GW5_ACTIONS; ++i) {
+            cum = (i == 0) ? prob[0] : cum + prob[i];
+            cnt += (cum < u) ? 1 : 0;
+          }
+          a = min(cnt, GW5_ACTIONS - 1);
+        }
+        if (trace) wd_store_untracked(trace + (long)k * n_envs * GW5_N, a);  // (untracked: the loop never reads it back)
+        // ---- movement :152-173
+        int ddx = act_dx[0], ddy = act_dy[0];
+#pragma unroll
+        for (int i = 1; i < 5; ++i) { ddx = (a == i) ? act_dx[i] : ddx; ddy = (a == i) ? act_dy[i] : ddy; }
+        const int ux = x + ddx, uy = y + ddy;
+        const int cx = min(max(ux, 0), world_boundary), cy = min(max(uy, 0), world_boundary);
+        hit = (ux != cx) || (uy != cy);  // :163-170
+        x = cx;
+        y = cy;
+        t += 1;  // :295
+      }
+      // ---- tag check :175-178 (all 64 lanes take part in the exchange; finished replicas are masked out of the result)
+      const int cell = x | (y << 8);
+      const int runner_cell = __shfl(cell, runner_lane);
+      const unsigned long long on_runner = __ballot(live && (ag < GW5_N - 1) && (cell == runner_cell));
+      const bool tag = ((unsigned)(on_runner >> (min(el, GW5_EPB - 1) * GW5_N)) & 0xfu) != 0u;
+      if (live) {
+        sum += GW_REWARD(ag < GW5_N - 1, tag, hit);
+        steps += 1;
+        // ---- the image: positions and time columns only (see gw5_rollout); a time step past the table (a start state
+        // that was already timed out) finishes the replica on this tick and its image is not read again
+        const float fx = s_div[x], fy = s_div[y];  // (clipped to 0 .. world_boundary <= 63 just above)
+        const float tnorm = s_tn[min(max(t, 0), episode_length)];
+#pragma unroll
+        for (int i = 0; i < GW5_N; ++i) {
+          rep[i * GW5_F + ag] = fx;
+          rep[i * GW5_F + GW5_N + ag] = fy;
+        }
+        rep[ag * GW5_F + 4 * GW5_N] = tnorm;
+        live = !((t >= episode_length) || tag);  // :314
+      }
+    }
+    if (active) {
+      eval_reward_sum[idx] = sum;
+      if (!greedy) rng_state[WD_RNG_HEADER + idx] = epoch0 + (uint32_t)steps;
+      if (ag == 0) {
+        eval_steps[env] = steps;
+        eval_done[env] = live ? 0 : 1;
+      }
+    }
+    __syncthreads();  // (the next trip overwrites the image)
+  }
+}
+
 }  // namespace
 
 #define GW5_PARAMS                                                                                                    \
@@ -369,3 +578,26 @@ extern "C" __global__ void __launch_bounds__(64) HipTagGridWorldRollout_N5(GW5_P
   }
 GW5_POLICY_ENTRY(32)
 GW5_POLICY_ENTRY(64)
+
+// one episode of every replica with the policies inside the kernel (gw5_evaluate): the step's arguments (read only;
+// the kernel has no use for the action, done and reward arrays), then the generator state, the stream tag, the tick
+// budget, the action table, the two packed policies, the mode, the three outputs and the optional action trace.
+// Dynamic LDS: the image, 64 coordinate quotients, the time table rounded up to 16 bytes, 2 * gw5_policy_floats(H)
+// floats (envs/tag_gridworld.py::live_policy_evaluate_lds_bytes)
+#define GW5_EVALUATE_ENTRY(HH)                                                                                        \
+  extern "C" __global__ void __launch_bounds__(64) HipTagGridWorldEvaluate_N5_H##HH(                                  \
+      const int *states_x_arr, const int *states_y_arr, const int *actions_arr, const int *done_arr,                  \
+      const float *rewards_arr, const float *obs_arr, double wall_hit_penalty, double tag_reward_for_tagger,          \
+      double tag_penalty_for_runner, double step_cost_for_tagger, int use_full_observation, int world_boundary,       \
+      const int *env_timestep_arr, int episode_length, int n_agents, int n_envs, uint32_t *rng_state, int stream_tag, \
+      int ticks, const int *action_table, const float *policy_tagger, const float *policy_runner, int use_argmax,     \
+      float *eval_reward_sum, int *eval_steps, int *eval_done, int *action_trace) {                                   \
+    extern __shared__ __attribute__((aligned(16))) float gw5_smem[];                                                  \
+    gw5_evaluate<HH>(states_x_arr, states_y_arr, obs_arr, wall_hit_penalty, tag_reward_for_tagger,                    \
+                     tag_penalty_for_runner, step_cost_for_tagger, use_full_observation, world_boundary,              \
+                     env_timestep_arr, episode_length, n_agents, n_envs, rng_state, stream_tag, ticks, action_table,  \
+                     policy_tagger, policy_runner, use_argmax, eval_reward_sum, eval_steps, eval_done, action_trace,  \
+                     gw5_smem);                                                                                       \
+  }
+GW5_EVALUATE_ENTRY(32)
+GW5_EVALUATE_ENTRY(64)

@@ -227,6 +227,69 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
                 and self.live_policy_lds_bytes(width) <= self.ROLLOUT_POLICY_MAX_LDS
                 and self.cuda_function_manager.has_function(f"HipTagGridWorldRollout_N5_H{int(width)}"))
 
+    # Trainer.evaluate_episodes takes the one-launch evaluation of this env only under
+    # `trainer.fused_rollout_policy: "all"`: the shipped configs keep the per-tick path they evaluate on
+    EVALUATE_POLICY_OPT_IN = True
+
+    def live_policy_evaluate_lds_bytes(self, width):
+        """dynamic LDS of HipTagGridWorldEvaluate_N5_H<width> (the layout of gw5_evaluate in tag_gridworld_n5.hip): the
+        rollout's without the restore cache -- the image of 12 replicas, 64 coordinate quotients, the time table
+        rounded up to 16 bytes, the two packed policies"""
+        return self.live_policy_lds_bytes(width, cache_dwords=0)
+
+    def has_live_policy_evaluate(self, width, n_actions):
+        """does an evaluation kernel exist that runs one episode of every replica with the two policy networks inside
+        it (HipTagGridWorldEvaluate_N5_H<width>, Trainer.evaluate_episodes)?  The shapes of the live-policy rollout,
+        with the evaluation's own (smaller) tables within ROLLOUT_POLICY_MAX_LDS and its entry in the manifest."""
+        return bool(self.has_live_policy_rollout(width, n_actions)
+                    and self.live_policy_evaluate_lds_bytes(width) <= self.ROLLOUT_POLICY_MAX_LDS
+                    and self.cuda_function_manager.has_function(f"HipTagGridWorldEvaluate_N5_H{int(width)}"))
+
+    def evaluate_launch(self, sampler, policy, use_argmax, outputs, action_trace=None, ticks=None):
+        """One episode of every replica in ONE launch (HipTagGridWorldEvaluate_N5_H<width>): from the positions,
+        observation rows and time step the arrays hold, at most `ticks` (default: episode_length) ticks of policy
+        networks -> action (use_argmax: the first maximum of the probabilities; else the counting draw of the rollout)
+        -> step, up to the replica's first done.  policy = ((packed tagger policy, packed runner policy), hidden width)
+        as in `tick_launch`.  outputs = {"reward_sum": float32 [E * 5] or [E, 5], "steps": int32 [E], "done": int32
+        [E]}, CUDA tensors (at least that many elements); `action_trace` (optional) int32 [>= ticks, E, 5]: row k = tick
+        k's actions of the replicas still running.  The launch writes those and, in sampled mode, the sampler's epoch
+        words; the env's arrays are read only.  Returns (function, arguments, block, grid, shared bytes)."""
+        from warp_drive_amd.managers.function_manager import _stream_tag
+        from warp_drive_amd.rollout import UnsupportedRolloutShape
+        import torch
+
+        fm, dm = self.cuda_function_manager, self.cuda_data_manager
+        try:
+            (tagger, runner), width = policy
+            width = int(width)
+        except (TypeError, ValueError) as err:
+            raise UnsupportedRolloutShape("policy = ((packed tagger policy, packed runner policy), hidden width), "
+                                          f"not {policy!r}") from err
+        if not self.has_live_policy_evaluate(width, len(self.step_actions)):
+            raise UnsupportedRolloutShape("the in-kernel evaluation exists for 5 agents with full observations, "
+                                          "5 actions and hidden widths 32 / 64 only")
+        n_w = gridworld_policy_floats(width)
+        for t in (tagger, runner):
+            if not (getattr(t, "is_cuda", False) and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n_w):
+                raise UnsupportedRolloutShape(f"a packed policy must be a contiguous float32 CUDA tensor of {n_w} "
+                                              f"elements (width {width})")
+        E, N = int(dm.meta_info("n_envs")), self.num_agents
+        T = int(self.episode_length if ticks is None else ticks)
+        for key, dtype, n in (("reward_sum", torch.float32, E * N), ("steps", torch.int32, E), ("done", torch.int32, E)):
+            t = outputs[key]
+            assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.numel() >= n, (key, tuple(t.shape), t.dtype)
+        if action_trace is not None:
+            t = action_trace
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and t.shape[0] >= T and \
+                int(np.prod(t.shape[1:])) == E * N, ("action_trace", tuple(t.shape), t.dtype)
+        name = f"HipTagGridWorldEvaluate_N5_H{width}"
+        fm.initialize_functions([name])
+        args = self._step_args() + [
+            sampler.rng_state, _stream_tag("tick"), np.int32(T), fm.global_address("kIndexToActionArr"), tagger, runner,
+            np.int32(1 if use_argmax else 0), outputs["reward_sum"], outputs["steps"], outputs["done"],
+            np.uint64(0) if action_trace is None else action_trace]
+        return fm.get_function(name), args, (64, 1, 1), ((E + 11) // 12, 1), self.live_policy_evaluate_lds_bytes(width)
+
     def image_fits(self, epb):
         """does a block of `epb` replicas keep its observation rows in LDS (lds_bytes: the image is part of the sum)?"""
         F = 4 * self.num_agents + 1 if self.use_full_observation else 6

@@ -352,7 +352,8 @@ class Trainer:
             logging.info(f"whole-batch rollout not available for this shape ({err}); using the per-tick path")
             return
         self.engine = engine
-        self._batch_rollout = {"packed": packed, "pack": pack, "split": split}
+        self._batch_rollout = {"packed": packed, "pack": pack, "split": split, "owners": owners, "width": width,
+                               "all": wanted == "all"}
         self._want_graph = False
 
     # --------------------------------------------------------------------------- rollout
@@ -782,17 +783,18 @@ class Trainer:
         return fm.get_function("HipEvaluateAccumulate"), args, (256, 1, 1), (max(1, min(4096, (E * N + 255) // 256)), 1), 0
 
     def _one_launch_evaluation(self):
-        """(env, width) when `evaluate_episodes` is one launch: the training rollout of this trainer is one launch and the
-        env has an Evaluate entry for the policy's shape; else None"""
-        env = self.w.env
-        if self._batch_rollout is None or len(self.policies) != 1 or not hasattr(env, "has_live_policy_evaluate"):
+        """(env, width) when `evaluate_episodes` is one launch: the training rollout of this trainer is one launch (so
+        every agent group of the kernel has exactly one owning policy, all of one width, packed in `_batch_rollout`)
+        and the env has an Evaluate entry for that shape; else None.  Envs that say EVALUATE_POLICY_OPT_IN
+        (TagGridWorld) take it only under `trainer.fused_rollout_policy: "all"`."""
+        env, br = self.w.env, self._batch_rollout
+        if br is None or not hasattr(env, "has_live_policy_evaluate"):
             return None
-        pol = self.policies[0]
-        obs_size = flattened_obs_size(env.observation_space[self.policy_map[pol][0]])
-        width = rollout_policy_width(self.models[pol], obs_size, getattr(env, "ROLLOUT_POLICY_WIDTHS", ()))
-        if width is None or len(self.head_sizes) != 1 or not env.has_live_policy_evaluate(width, self.head_sizes[0]):
+        if getattr(env, "EVALUATE_POLICY_OPT_IN", False) and not br["all"]:
             return None
-        return env, width
+        if len(self.head_sizes) != 1 or not env.has_live_policy_evaluate(br["width"], self.head_sizes[0]):
+            return None
+        return env, br["width"]
 
     @torch.no_grad()
     def evaluate_episodes(self, **sample_params):
@@ -817,10 +819,13 @@ class Trainer:
         8. Multi-GPU: each rank evaluates its own replicas and returns its own arrays.
 
         Two paths; `self.evaluation_path` says which one the last call took.  "one launch": when the training rollout of
-        this trainer is one launch and the env has an Evaluate entry (Cartpole by default, Acrobot / MountainCar under
-        `fused_rollout_policy: "all"`), one kernel runs the whole episode of every replica with the policy inside it and
-        writes two numbers per replica.  "per tick": everything else -- policy forward, (one-hot rows when greedy,) the
-        single-tick engine, HipEvaluateAccumulate on `rewards` / `_done_`, `episode_length` times, with no host
+        this trainer is one launch and the env has an Evaluate entry (Cartpole by default; Acrobot / MountainCar under
+        `fused_rollout_policy: "all"`, which is what makes their training rollout one launch; TagGridWorld with 5
+        agents, full observations and [32, 32] / [64, 64] policies ALSO only under `fused_rollout_policy: "all"` -- its
+        training rollout is one launch by default, its evaluation is opt-in: EVALUATE_POLICY_OPT_IN), one kernel runs
+        the whole episode of every replica with the policies inside it -- one per agent group of the env, each packed
+        from its owning policy's current weights -- and writes a reward sum per agent and a step count per replica.
+        "per tick": everything else -- policy forward, (one-hot rows when greedy,) the single-tick engine, HipEvaluateAccumulate on `rewards` / `_done_`, `episode_length` times, with no host
         synchronisation per tick (one all-finished check every 32 ticks) and one pull at the end.  Restarted replicas
         keep stepping and are masked out."""
         use_argmax = bool(sample_params.get("use_argmax", False))
@@ -829,13 +834,15 @@ class Trainer:
         one = self._one_launch_evaluation()
         if one is not None:
             env, width = one
-            pol = self.policies[0]
             br = self._batch_rollout
-            br["pack"](self.models[pol], out=br["packed"][pol])  # the current weights
-            out = {"reward_sum": torch.zeros(E, dtype=torch.float32, device=self.device),
+            for pol in self.policies:
+                br["pack"](self.models[pol], out=br["packed"][pol])  # the current weights
+            owners = br["owners"]  # one policy per agent group of the kernel, in its argument order
+            arg = br["packed"][owners[0]] if len(owners) == 1 else [br["packed"][o] for o in owners]
+            out = {"reward_sum": torch.zeros((E, N), dtype=torch.float32, device=self.device),
                    "steps": torch.zeros(E, dtype=torch.int32, device=self.device),
                    "done": torch.zeros(E, dtype=torch.int32, device=self.device)}
-            fn, args, block, grid, shared = env.evaluate_launch(self.sampler, policy=(br["packed"][pol], width),
+            fn, args, block, grid, shared = env.evaluate_launch(self.sampler, policy=(arg, width),
                                                                 use_argmax=use_argmax, outputs=out, ticks=T)
             fn(*args, block=block, grid=grid, shared=shared)
             reward_sum = out["reward_sum"].cpu().numpy().reshape(E, N)
