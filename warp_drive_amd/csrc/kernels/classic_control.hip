@@ -348,6 +348,61 @@ __device__ __forceinline__ void cc_policy_cum(const float *w, const float (&o)[O
   }
 }
 
+// ---- a deterministic actor INSIDE the tick of the Box envs (DDPG): two hidden layers of H ReLU units + one linear output z,
+// mean = fmaf(action_scale, tanhf(z), action_bias).  cc_policy_cum's arithmetic (acc = bias, then one fmaf per input in
+// index order), the weights in LDS, the activations in registers.  Packed weights (training/policy_kernel.py::
+// pack_rollout_actor): W0 [H][OP], b0 [H], W1 [H][H], b1 [H], Wa [H], ba [1], all float32, OP = O rounded up to even (the
+// rows of W0 are read as float2): the pad column is zero and the lane's pad observation is 0, so the pad adds +0 exactly.
+// Restated on the host in tests/classic_control_actor.py::actor_mean_f32.
+constexpr int cc_actor_op(int O) { return (O + 1) & ~1; }
+constexpr int cc_actor_floats(int H, int O) { return cc_actor_op(O) * H + H + H * H + H + H + 1; }
+
+struct CcActorArgs {
+  float action_scale, action_bias;
+  float *mean_batch;  // [T, E] or null: row k = the means of tick k
+};
+
+template <int H, int O>
+__device__ __forceinline__ float cc_actor_mean(const float *w, const float (&o)[O], float action_scale,
+                                               float action_bias) {
+  constexpr int OP = cc_actor_op(O);
+  static_assert(H % 4 == 0, "the rows of W1 and Wa are read as float4");
+  const float *W0 = w, *b0 = W0 + OP * H, *W1 = b0 + H, *b1 = W1 + H * H, *Wa = b1 + H, *ba = Wa + H;
+  float op[OP];
+#pragma unroll
+  for (int j = 0; j < OP; ++j) op[j] = (j < O) ? o[j < O ? j : 0] : 0.0f;
+  float h1[H], h2[H];
+#pragma unroll
+  for (int i = 0; i < H; ++i) {
+    float acc = b0[i];
+#pragma unroll
+    for (int j = 0; j < OP; j += 2) {
+      const float2 wr = *(const float2 *)(W0 + OP * i + j);
+      acc = fmaf(wr.x, op[j], acc); acc = fmaf(wr.y, op[j + 1], acc);
+    }
+    h1[i] = fmaxf(acc, 0.0f);
+  }
+#pragma unroll
+  for (int i = 0; i < H; ++i) {
+    float acc = b1[i];
+#pragma unroll
+    for (int j = 0; j < H; j += 4) {
+      const float4 wr = *(const float4 *)(W1 + i * H + j);
+      acc = fmaf(wr.x, h1[j], acc); acc = fmaf(wr.y, h1[j + 1], acc);
+      acc = fmaf(wr.z, h1[j + 2], acc); acc = fmaf(wr.w, h1[j + 3], acc);
+    }
+    h2[i] = fmaxf(acc, 0.0f);
+  }
+  float z = ba[0];
+#pragma unroll
+  for (int j = 0; j < H; j += 4) {
+    const float4 wr = *(const float4 *)(Wa + j);
+    z = fmaf(wr.x, h2[j], z); z = fmaf(wr.y, h2[j + 1], z);
+    z = fmaf(wr.z, h2[j + 2], z); z = fmaf(wr.w, h2[j + 3], z);
+  }
+  return fmaf(action_scale, tanhf(z), action_bias);
+}
+
 // Fused rollout tick(s) (the conventions of HipClassicControlCartPoleEnvTick): per tick, draw the action, step, and
 // restart a finished replica; the state, the observation and the timestep stay in registers.  Discrete envs draw
 // the categorical action from `probs` [E, n_actions] with wd_tick_draw(row, epoch0 + k, stream_tag); continuous envs
@@ -361,12 +416,17 @@ __device__ __forceinline__ void cc_policy_cum(const float *w, const float (&o)[O
 // + A H + A floats; the block copies the packed network `policy` into it once per launch, and every tick evaluates it
 // on the observation the lane holds (the one row k of `obs_batch` records) instead of reading `probs`.  The draw keeps
 // the fixed-probability tick's Philox counters.
+// H > 0 (Box envs, the ...EnvRollout_A<H> entries): a LIVE deterministic actor.  `weights` = dynamic LDS of
+// cc_actor_floats(H, O) floats, copied from the packed network `policy` once per launch; every tick sets `mean` to
+// cc_actor_mean of the observation the lane holds instead of keeping the launch's one `probs[env]` (`probs` is not read),
+// and with `actor.mean_batch` records it in row k.  The OU draw, the step and the restart are the code below, unchanged.
 template <class Env, bool BATCH, int H = 0>
 __device__ __forceinline__ void cc_tick_impl(const Env &e, const CcTickArgs &a, float *weights = nullptr,
-                                             const float *policy = nullptr) {
-  static_assert(H == 0 || !Env::CONT, "the in-kernel policy has a softmax head");
+                                             const float *policy = nullptr,
+                                             const CcActorArgs &actor = CcActorArgs{1.0f, 0.0f, nullptr}) {
+  constexpr bool ACTOR = H > 0 && Env::CONT;
   if constexpr (H > 0) {
-    const int n_w = Env::O * H + H + H * H + H + a.n_actions * H + a.n_actions;
+    const int n_w = ACTOR ? cc_actor_floats(H, Env::O) : Env::O * H + H + H * H + H + a.n_actions * H + a.n_actions;
     for (int i = threadIdx.x; i < n_w; i += blockDim.x) weights[i] = policy[i];
     __syncthreads();
   }
@@ -386,7 +446,7 @@ __device__ __forceinline__ void cc_tick_impl(const Env &e, const CcTickArgs &a, 
     uint32_t pool_epoch = a.pool ? a.pool_rng[WD_RNG_HEADER + env] : 0u;
     float cumv[CC_MAX_ACTIONS], mean = 0.0f, ou = 0.0f;
     if (Env::CONT) {
-      mean = a.probs[env];
+      if constexpr (!ACTOR) mean = a.probs[env];
       ou = a.ou_state[env];
     } else if (H == 0) {
       const float *row = a.probs + (long)env * a.n_actions;
@@ -405,6 +465,10 @@ __device__ __forceinline__ void cc_tick_impl(const Env &e, const CcTickArgs &a, 
       // ---- sample
       Act act;
       if constexpr (Env::CONT) {
+        if constexpr (ACTOR) {  // live actor: THIS tick's observation
+          mean = cc_actor_mean<H, O>(weights, o, actor.action_scale, actor.action_bias);
+          if (actor.mean_batch) wd_store_untracked(actor.mean_batch + ((long)k * (long)E + env), mean);
+        }
         if (draw_ou) {
           const wd_u4 rnd = wd_philox4x32_10(wd_u4{(uint32_t)env, epoch0 + (uint32_t)k, (uint32_t)a.stream_tag, 1u}, k0, k1);
           const float u1 = wd_u01_open_closed(rnd.x), u2 = wd_u01_open_closed(rnd.y);
@@ -491,6 +555,16 @@ __device__ __forceinline__ void cc_rollout(const Env &e, const CcTickArgs &a, fl
   if (hidden != H || a.n_actions < 1 || a.n_actions > CC_MAX_ACTIONS || policy == nullptr) return;  // (uniform)
   if (a.obs_batch) cc_tick_impl<Env, true, H>(e, a, weights, policy);
   else cc_tick_impl<Env, false, H>(e, a, weights, policy);
+}
+
+// the rollout of a Box env with a live actor; `hidden` must be the entry's width (else: no tick)
+template <int H, class Env>
+__device__ __forceinline__ void cc_rollout_actor(const Env &e, const CcTickArgs &a, float *weights, const float *actor,
+                                                 int hidden, const CcActorArgs &aa) {
+  static_assert(Env::CONT, "the actor's output is a Box action");
+  if (hidden != H || actor == nullptr) return;  // (uniform)
+  if (a.obs_batch) cc_tick_impl<Env, true, H>(e, a, weights, actor, aa);
+  else cc_tick_impl<Env, false, H>(e, a, weights, actor, aa);
 }
 
 // ---- evaluation: ONE episode of every replica in one launch (the ...EnvEvaluate_H<H> entries), greedy or sampled.
@@ -739,6 +813,34 @@ __global__ void __launch_bounds__(256) HipClassicControlPendulumEnvTick(float *s
   }
 CC_ROLLOUT_ENTRIES(32)
 CC_ROLLOUT_ENTRIES(64)
+
+// the rollout of the Box envs with a live deterministic actor (two hidden layers of HH units + one tanh output, packed
+// weights in dynamic LDS): the arguments of the env's tick, then the packed actor, its width, the output's scale and
+// bias, and the [T, E] record of the means (or null)
+#define CC_ACTOR_ENTRIES(HH)                                                                                           \
+  __global__ void __launch_bounds__(256, 2) HipClassicControlContinuousMountainCarEnvRollout_A##HH(                    \
+      float *state_arr, float *action_arr, int *done_arr, float *reward_arr, float *observation_arr, float min_action, \
+      float max_action, float min_position, float max_position, float max_speed, float goal_position,                  \
+      float goal_velocity, float power, int *env_timestep_arr, int episode_length, int n_envs, CC_TICK_PARAMS,         \
+      const float *actor, int hidden, float action_scale, float action_bias, float *mean_batch) {                      \
+    extern __shared__ __attribute__((aligned(16))) float cc_lds[];                                                     \
+    const CcContinuousMountainCar e{min_action, max_action, min_position, max_position,                                \
+                                    max_speed, goal_position, goal_velocity, power};                                   \
+    cc_rollout_actor<HH>(e, CC_TICK_ARGS(state_arr, action_arr, done_arr, reward_arr, observation_arr,                 \
+                                         env_timestep_arr),                                                            \
+                         cc_lds, actor, hidden, CcActorArgs{action_scale, action_bias, mean_batch});                   \
+  }                                                                                                                    \
+  __global__ void __launch_bounds__(256, 2) HipClassicControlPendulumEnvRollout_A##HH(                                 \
+      float *state_arr, float *action_arr, int *done_arr, float *reward_arr, float *observation_arr,                   \
+      int *env_timestep_arr, int episode_length, int n_envs, CC_TICK_PARAMS, const float *actor, int hidden,           \
+      float action_scale, float action_bias, float *mean_batch) {                                                      \
+    extern __shared__ __attribute__((aligned(16))) float cc_lds[];                                                     \
+    cc_rollout_actor<HH>(CcPendulum{}, CC_TICK_ARGS(state_arr, action_arr, done_arr, reward_arr, observation_arr,      \
+                                                    env_timestep_arr),                                                 \
+                         cc_lds, actor, hidden, CcActorArgs{action_scale, action_bias, mean_batch});                   \
+  }
+CC_ACTOR_ENTRIES(32)
+CC_ACTOR_ENTRIES(64)
 
 // one episode of every replica with the policy inside the kernel (cc_evaluate_impl): the env's step arguments (read
 // only), then what the evaluation takes

@@ -13,7 +13,8 @@ step + restart of a finished replica, from the reset table or from a reset pool,
 The two discrete envs also have `HipClassicControl<X>EnvRollout_H32 / _H64`: the same tick with a small policy network
 evaluated by the kernel on every tick's observation (`tick_launch(policy=...)`), and
 `HipClassicControl<X>EnvEvaluate_H32 / _H64`: one episode of every replica in one launch, greedy or sampled
-(`evaluate_launch`).
+(`evaluate_launch`).  The two Box envs have `HipClassicControl<X>EnvRollout_A32 / _A64`: the tick with a deterministic
+actor network evaluated by the kernel on every tick's observation (`tick_launch(actor=...)`, DDPG).
 """
 import math
 
@@ -331,6 +332,13 @@ class ClassicControlPendulumEnv(_ClassicControlEnv):
 
 
 # ---------------------------------------------------------------------------------------------------- device envs
+def rollout_actor_floats(obs_size, width):
+    """floats of the packed actor the ...Rollout_A<width> entries read (classic_control.hip::cc_actor_floats): W0
+    [H][OP], b0 [H], W1 [H][H], b1 [H], Wa [H], ba [1], OP = the observation size rounded up to even"""
+    op = (int(obs_size) + 1) // 2 * 2
+    return op * width + width + width * width + width + width + 1
+
+
 class _CUDAClassicControlEnv(CUDAEnvironmentContext):
     """shared device side: data, reset pool, step launch and fused tick launch"""
     TICK_HEADS = 1          # action heads the fused tick kernel samples (RolloutEngine)
@@ -351,6 +359,15 @@ class _CUDAClassicControlEnv(CUDAEnvironmentContext):
         if isinstance(self.action_space[0], spaces.Box) or int(width) not in widths or not 1 <= int(n_actions) <= 8:
             return False
         name = self.cuda_step.name.replace("Step", f"Rollout_H{int(width)}")
+        return bool(self.cuda_function_manager.has_function(name))
+
+    def has_live_actor_rollout(self, width):
+        """does a rollout kernel exist that evaluates a deterministic actor itself (...Rollout_A<width>)?  (RolloutEngine
+        asks before it calls `tick_launch(actor=...)`)  Only the Box envs have one."""
+        widths = getattr(self, "ROLLOUT_ACTOR_WIDTHS", ())
+        if not isinstance(self.action_space[0], spaces.Box) or int(width) not in widths:
+            return False
+        name = self.cuda_step.name.replace("Step", f"Rollout_A{int(width)}")
         return bool(self.cuda_function_manager.has_function(name))
 
     def has_live_policy_evaluate(self, width, n_actions):
@@ -437,7 +454,7 @@ class _CUDAClassicControlEnv(CUDAEnvironmentContext):
         return self.cuda_step, self.cuda_step_function_feed(self._step_args()), block, grid, 0
 
     def tick_launch(self, sampler, probabilities, resetter, env_range=None, batch=None, policy=None,
-                    ou_params=(0.15, 0.2, 1.0)):
+                    ou_params=(0.15, 0.2, 1.0), actor=None, mean_batch=None):
         """Fused rollout tick(s): sample + step + restart of a finished replica, `ticks_per_launch` times in ONE launch
         (HipClassicControl<X>EnvTick).  probabilities = [float32 CUDA tensor [E, 1, n_actions]] (discrete) or [the
         means, [E, 1, 1]] (Box: OU / Gaussian exploration with ou_params = (damping, stddev, scale), the draws of
@@ -447,7 +464,12 @@ class _CUDAClassicControlEnv(CUDAEnvironmentContext):
         `policy` (optional, Acrobot and MountainCar) = (packed float32 CUDA tensor from
         training.policy_kernel.pack_rollout_policy, hidden width): the launch evaluates the policy network on every
         tick's observation itself (HipClassicControl<X>EnvRollout_H<width>, the packed weights in dynamic LDS) instead of
-        reading `probabilities`, which then only says how many actions there are."""
+        reading `probabilities`, which then only says how many actions there are.
+        `actor` (optional, ContinuousMountainCar and Pendulum) = (packed float32 CUDA tensor from
+        training.policy_kernel.pack_rollout_actor, hidden width, action_scale, action_bias): the launch evaluates the
+        deterministic actor on every tick's observation itself (HipClassicControl<X>EnvRollout_A<width>), mean =
+        action_scale * tanh(z) + action_bias, instead of reading the means; `mean_batch` (optional, float32 [T, E]): tick
+        k writes its means to row k."""
         from warp_drive_amd.managers.function_manager import _stream_tag
         from warp_drive_amd.rollout import UnsupportedRolloutShape
 
@@ -474,6 +496,37 @@ class _CUDAClassicControlEnv(CUDAEnvironmentContext):
                                               f"elements (observation {O}, width {width}, {n_act} actions)")
             name = self.cuda_step.name.replace("Step", f"Rollout_H{width}")
             shared, pol_args = 4 * n_w, [packed, np.int32(width)]
+        if actor is not None:
+            if policy is not None:
+                raise UnsupportedRolloutShape("a launch evaluates a policy or an actor, not both")
+            try:
+                packed, width, action_scale, action_bias = actor
+                width, action_scale, action_bias = int(width), float(action_scale), float(action_bias)
+            except (TypeError, ValueError) as err:
+                raise UnsupportedRolloutShape("actor = (packed weights, hidden width, action_scale, action_bias), "
+                                              f"not {actor!r}") from err
+            if not self.has_live_actor_rollout(width):
+                raise UnsupportedRolloutShape(f"{type(self).__name__} has no in-kernel actor of width {width}")
+            import torch
+
+            O = int(dm.get_shape(_OBSERVATIONS)[-1])
+            n_w = rollout_actor_floats(O, width)
+            if not (getattr(packed, "is_cuda", False) and packed.dtype == torch.float32 and packed.is_contiguous()
+                    and packed.numel() == n_w):
+                raise UnsupportedRolloutShape(f"the packed actor must be a contiguous float32 CUDA tensor of {n_w} "
+                                              f"elements (observation {O}, width {width})")
+            n_envs, ticks = int(dm.meta_info("n_envs")), int(self.ticks_per_launch)
+            if mean_batch is not None and not (
+                    getattr(mean_batch, "is_cuda", False) and mean_batch.dtype == torch.float32
+                    and mean_batch.is_contiguous() and mean_batch.shape[0] >= ticks
+                    and int(np.prod(mean_batch.shape[1:])) == n_envs):
+                raise UnsupportedRolloutShape(f"mean_batch must be a contiguous float32 CUDA tensor [>= {ticks}, {n_envs}]")
+            name = self.cuda_step.name.replace("Step", f"Rollout_A{width}")
+            shared = 4 * n_w
+            pol_args = [packed, np.int32(width), np.float32(action_scale), np.float32(action_bias),
+                        np.uint64(0) if mean_batch is None else mean_batch]
+        elif mean_batch is not None:
+            raise UnsupportedRolloutShape("mean_batch is what the in-kernel actor records: it needs `actor`")
         fm.initialize_functions([name])
         _, reset_args, _, _ = resetter.fused_launch(dm, 0, 0)  # builds / refreshes the descriptor table
         _, args, block, grid, _ = self.step_launch()
@@ -546,6 +599,8 @@ class CUDAClassicControlMountainCarEnv(_CUDAClassicControlEnv, ClassicControlMou
 
 
 class CUDAClassicControlContinuousMountainCarEnv(_CUDAClassicControlEnv, ClassicControlContinuousMountainCarEnv):
+    ROLLOUT_ACTOR_WIDTHS = (32, 64)    # HipClassicControlContinuousMountainCarEnvRollout_A<width>
+
     CONSTANTS = ("min_action", "max_action", "min_position", "max_position", "max_speed", "goal_position",
                  "goal_velocity", "power")
 
@@ -555,6 +610,8 @@ class CUDAClassicControlContinuousMountainCarEnv(_CUDAClassicControlEnv, Classic
 
 
 class CUDAClassicControlPendulumEnv(_CUDAClassicControlEnv, ClassicControlPendulumEnv):
+    ROLLOUT_ACTOR_WIDTHS = (32, 64)    # HipClassicControlPendulumEnvRollout_A<width>
+
     def __init__(self, *args, **kwargs):
         ClassicControlPendulumEnv.__init__(self, *args, **kwargs)
         _CUDAClassicControlEnv.__init__(self)

@@ -56,7 +56,7 @@ def cohort_bounds(n_envs, cohorts):
 class RolloutEngine:
     def __init__(self, env_wrapper, sampler: HIPSampler, probabilities=None, reset_done=True, fused=True,
                  rollout_batch=None, rollout_policy=None, ticks_per_launch=None, presampled_actions=False,
-                 damping=0.15, stddev=0.2, scale=1.0):
+                 damping=0.15, stddev=0.2, scale=1.0, rollout_actor=None, rollout_means=None):
         """probabilities: list (one per action head) of contiguous float32 CUDA tensors
         [n_envs, n_agents, n_actions_of_head]; None = uniform.  rollout_batch: the trainer's [T, E, ...] batch
         tensors for envs whose tick kernel fuses T ticks per launch and records every tick itself
@@ -65,7 +65,10 @@ class RolloutEngine:
         (None = the env object's own `ticks_per_launch` attribute); the env object is left as it was, so another
         engine on the same wrapper is not affected.  presampled_actions: the tick does NOT draw the actions -- whoever
         runs before it (the policy forward's epilogue, training/policy_kernel.py) has written `sampled_actions` -- and
-        is the env's step + reset entry (`env.has_presampled_tick()`).  A one-dimensional `Box` action space: the
+        is the env's step + reset entry (`env.has_presampled_tick()`).  rollout_actor: (packed weights, hidden width,
+        action_scale, action_bias) of a deterministic actor that a Box env's kernel evaluates itself on every tick
+        (`env.has_live_actor_rollout(width)`), rollout_means: the [T, E] float32 record of its means.
+        A one-dimensional `Box` action space: the
         one probability tensor [n_envs, n_agents, 1] holds the means of the actions, and the draw is
         sample_ou_process's OU / Gaussian one with `damping`, `stddev`, `scale` (HIPSampler.sample's defaults).
         With a reset pool the reset entry restarts finished replicas from it (HIPEnvironmentReset.reset_when_done:
@@ -77,12 +80,14 @@ class RolloutEngine:
         if ticks_per_launch is not None:
             env.ticks_per_launch = int(ticks_per_launch)
         try:
-            self._build(env_wrapper, sampler, probabilities, reset_done, fused, rollout_batch, rollout_policy)
+            self._build(env_wrapper, sampler, probabilities, reset_done, fused, rollout_batch, rollout_policy,
+                        rollout_actor, rollout_means)
         finally:
             if ticks_per_launch is not None:
                 env.ticks_per_launch = saved
 
-    def _build(self, env_wrapper, sampler, probabilities, reset_done, fused, rollout_batch, rollout_policy):
+    def _build(self, env_wrapper, sampler, probabilities, reset_done, fused, rollout_batch, rollout_policy,
+               rollout_actor=None, rollout_means=None):
         assert env_wrapper.env_backend == "hip"
         self.w = env_wrapper
         self.sampler = sampler
@@ -132,6 +137,15 @@ class RolloutEngine:
                 extra["policy"] = rollout_policy
             if self.continuous:
                 extra["ou_params"] = self.ou_params
+            if rollout_actor is not None:
+                has = getattr(env_wrapper.env, "has_live_actor_rollout", None)
+                if has is None or len(rollout_actor) != 4 or not has(int(rollout_actor[1])):
+                    raise UnsupportedRolloutShape(
+                        f"{type(env_wrapper.env).__name__} has no rollout kernel that evaluates an actor of hidden width "
+                        f"{rollout_actor[1] if len(rollout_actor) > 1 else None}")
+                extra["actor"] = rollout_actor
+                if rollout_means is not None:
+                    extra["mean_batch"] = rollout_means
             if self.presampled and not env_wrapper.env.has_presampled_tick():
                 raise UnsupportedRolloutShape("this env / shape has no step + reset entry for given actions")
             if rollout_policy is not None:
@@ -156,6 +170,8 @@ class RolloutEngine:
                         self.rollout_kernel_name = multi[0].name
             return
         assert not self.presampled, "presampled_actions needs the env's fused tick entry"
+        if rollout_actor is not None:
+            raise UnsupportedRolloutShape("an in-kernel actor needs the env's fused tick entry")
         if self.continuous:  # OU / Gaussian around the means, HIPSampler.sample's launch
             fn, args, block, grid, shared = sampler.ou_launch(dm, probabilities[0], _ACTIONS, E * N, *self.ou_params,
                                                               _stream_tag(_ACTIONS))

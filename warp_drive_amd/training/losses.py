@@ -179,3 +179,77 @@ class PPO(A2C):
         surr1 = ratio * advantages
         surr2 = torch.clamp(ratio, 1.0 - self.clip_param, 1.0 + self.clip_param) * advantages
         return -torch.minimum(surr1, surr2).mean()
+
+
+class DDPG:
+    """The DDPG objective (reference warp_drive/training/algorithms/policygradient/ddpg.py): n-step returns over the
+    T - n_step + 1 rows that have n_step rows after them, bootstrapped from the target networks' next values, the
+    critic's MSE against them, and actor_loss = -mean(J) with J = Q(obs, actor(obs)).
+
+    next_value_functions_batch has T - 1 rows: row t = Q'(obs[t + 1], actor'(obs[t + 1])).  With last = i + n_step - 1:
+        last < T - 1:   R = r[last] + (1 - done[last]) * gamma * next_value[last]
+        last == T - 1:  R = done[last] * r[last] + (1 - done[last]) * next_value[-1]
+                        (the final row has no next value: next_value[-1] stands in for its reward and bootstrap)
+        then, for j = 1 .. n_step - 1:  R = r[last - j] + (1 - done[last - j]) * gamma * R.
+    The reference forms this with a Python loop over the rows and the steps (T x n_step small launches); here every row is
+    formed at once, n_step vectorised steps."""
+
+    def __init__(self, discount_factor_gamma=1.0, normalize_advantage=False, normalize_return=False, n_step=1):
+        assert 0 <= discount_factor_gamma <= 1
+        assert n_step >= 1
+        self.discount_factor_gamma = discount_factor_gamma
+        self.normalize_advantage = normalize_advantage
+        self.normalize_return = normalize_return
+        self.n_step = int(n_step)
+
+    def n_step_returns(self, rewards, done_flags, next_values_detached):
+        T, n, gamma = rewards.shape[0], self.n_step, self.discount_factor_gamma
+        V = T - n + 1
+        assert V >= 1 and next_values_detached.shape[0] == T - 1
+        done = (done_flags > 0).to(rewards.dtype)[..., None]  # [T, E, 1]
+        returns = torch.empty_like(rewards[:V])
+        # rows whose last step has a next value, then the one row whose last step is the batch's final row
+        returns[:V - 1] = rewards[n - 1:T - 1] + (1 - done[n - 1:T - 1]) * gamma * next_values_detached[n - 1:]
+        returns[V - 1] = done[-1] * rewards[-1] + (1 - done[-1]) * next_values_detached[-1]
+        for j in range(1, n):
+            lo = n - 1 - j
+            returns = rewards[lo:lo + V] + (1 - done[lo:lo + V]) * gamma * returns
+        return returns
+
+    def compute_loss_and_metrics(self, timestep=None, actions_batch=None, rewards_batch=None, done_flags_batch=None,
+                                 value_functions_batch=None, next_value_functions_batch=None, j_functions_batch=None,
+                                 perform_logging=False):
+        assert timestep is not None and actions_batch is not None and rewards_batch is not None
+        assert done_flags_batch is not None and value_functions_batch is not None
+        assert next_value_functions_batch is not None and j_functions_batch is not None
+        V = rewards_batch.shape[0] - self.n_step + 1
+        returns = self.n_step_returns(rewards_batch, done_flags_batch, next_value_functions_batch.detach())
+        norm_returns = _normalise(returns) if self.normalize_return else returns
+        values = value_functions_batch[:V]
+        critic_loss = nn.functional.mse_loss(norm_returns, values)
+        advantages = norm_returns - values
+        norm_adv = _normalise(advantages) if self.normalize_advantage else advantages
+        j_functions = j_functions_batch[:V]
+        actor_loss = -(_normalise(j_functions) if self.normalize_return else j_functions).mean()
+        metrics = {}
+        if perform_logging:
+            var_explained = torch.clamp(1 - norm_adv.detach().var() / (norm_returns.detach().var() + _EPSILON), min=-1.0)
+            metrics = {
+                "Total loss": actor_loss.item() + critic_loss.item(), "Actor loss": actor_loss.item(),
+                "Critic loss": critic_loss.item(), "Mean rewards": rewards_batch.mean().item(),
+                "Max. rewards": rewards_batch.max().item(), "Min. rewards": rewards_batch.min().item(),
+                "Mean value function": values.mean().item(), "Mean J function": j_functions.mean().item(),
+                "Mean advantages": advantages.mean().item(), "Mean (norm.) advantages": norm_adv.mean().item(),
+                "Mean (discounted) returns": returns.mean().item(), "Mean normalized returns": norm_returns.mean().item(),
+                "Variance explained by the value function": var_explained.item(),
+            }
+            af = actions_batch.float()
+            over_agents, over_time, over_envs = (af.std(dim=d).mean(dim=(0, 1)) for d in (2, 0, 1))
+            hi, lo = torch.amax(actions_batch, dim=(0, 1, 2)), torch.amin(actions_batch, dim=(0, 1, 2))
+            for h in range(af.shape[-1]):
+                metrics[f"Std. of action_{h} over agents"] = over_agents[h].item()
+                metrics[f"Std. of action_{h} over envs"] = over_envs[h].item()
+                metrics[f"Std. of action_{h} over time"] = over_time[h].item()
+                metrics[f"Max of action_{h}"] = hi[h].item()
+                metrics[f"Min of action_{h}"] = lo[h].item()
+        return actor_loss, critic_loss, metrics

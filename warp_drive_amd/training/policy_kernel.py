@@ -291,6 +291,39 @@ def pack_rollout_policy(model, out=None):
     return out
 
 
+def rollout_actor_width(model, obs_size, widths=(32, 64)):
+    """hidden width if `model` (training.models_ddpg.FullyConnectedActor) is a network the in-kernel actors evaluate --
+    two hidden layers of equal width in `widths`, one output -- else None"""
+    fc = [model.fc[str(i)][0] for i in range(len(model.fc))]
+    head = model.action_head
+    if len(fc) != 2 or fc[0].in_features != int(obs_size) or head.out_features != 1:
+        return None
+    w = fc[0].out_features
+    if w not in widths or fc[1].in_features != w or fc[1].out_features != w or head.in_features != w:
+        return None
+    return int(w)
+
+
+@torch.no_grad()
+def pack_rollout_actor(model, out=None):
+    """W0 [H][OP], b0 [H], W1 [H][H], b1 [H], Wa [H], ba [1] as one flat float32 tensor (the layout
+    csrc/kernels/classic_control.hip::cc_actor_mean reads from LDS); OP = the observation size rounded up to even, the
+    pad column zero.  `out`: refill an existing tensor in place (the launch plan holds its address)."""
+    w0 = model.fc["0"][0].weight
+    H, O = w0.shape
+    OP = (O + 1) // 2 * 2
+    w0p = torch.zeros((H, OP), dtype=torch.float32, device=w0.device)
+    w0p[:, :O] = w0.detach().float()
+    parts = [w0p, model.fc["0"][0].bias, model.fc["1"][0].weight, model.fc["1"][0].bias,
+             model.action_head.weight, model.action_head.bias]
+    flat = torch.cat([p.detach().float().reshape(-1) for p in parts])
+    if out is None:
+        return flat.contiguous()
+    assert out.numel() == flat.numel()
+    out.copy_(flat)
+    return out
+
+
 @torch.no_grad()
 def pack_gridworld_policy(model, out=None):
     """One policy of the live-policy TagGridWorld rollout (csrc/kernels/tag_gridworld_n5.hip::gw5_policy_cum): W0

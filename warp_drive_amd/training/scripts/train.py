@@ -4,6 +4,7 @@ warp_drive/training/scripts/example_training_script_pycuda.py:41-225).
 
     python -m warp_drive_amd.training.scripts.train --env tag_continuous [--iters 5]
     python -m warp_drive_amd.training.scripts.train --env single_cartpole --evaluate greedy
+    python -m warp_drive_amd.training.scripts.train --env single_pendulum --evaluate greedy      # DDPG (TrainerDDPG)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
         -m warp_drive_amd.training.scripts.train --env tag_continuous      # 8 x MI355X, RCCL DDP
 """
@@ -21,15 +22,19 @@ import yaml
 from warp_drive_amd import distributed as wdd
 from warp_drive_amd.env_wrapper import EnvWrapper
 from warp_drive_amd.envs.cartpole import CUDAClassicControlCartPoleEnv
-from warp_drive_amd.envs.classic_control import CUDAClassicControlAcrobotEnv, CUDAClassicControlMountainCarEnv
+from warp_drive_amd.envs.classic_control import (CUDAClassicControlAcrobotEnv, CUDAClassicControlContinuousMountainCarEnv,
+                                                CUDAClassicControlMountainCarEnv, CUDAClassicControlPendulumEnv)
 from warp_drive_amd.envs.tag_continuous import TagContinuous
 from warp_drive_amd.envs.tag_gridworld import CUDATagGridWorld
 from warp_drive_amd.training.trainer import Trainer
+from warp_drive_amd.training.trainer_ddpg import TrainerDDPG
 
 _CONFIGS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "run_configs")
 _ENVS = {"tag_continuous": TagContinuous, "tag_gridworld": CUDATagGridWorld,
          "single_cartpole": CUDAClassicControlCartPoleEnv, "single_acrobot": CUDAClassicControlAcrobotEnv,
-         "single_mountain_car": CUDAClassicControlMountainCarEnv}
+         "single_mountain_car": CUDAClassicControlMountainCarEnv,
+         "single_continuous_mountain_car": CUDAClassicControlContinuousMountainCarEnv,
+         "single_pendulum": CUDAClassicControlPendulumEnv}
 
 
 def policy_map_for(name, env):
@@ -54,8 +59,11 @@ def setup_trainer(env_name, overrides=None, results_dir=None, verbose=True):
     env = _ENVS[env_name](**env_cfg)
     wrapper = EnvWrapper(env_obj=env, num_envs=int(config["trainer"]["num_envs"]), env_backend="hip",
                          process_id=device)
-    return Trainer(env_wrapper=wrapper, config=config, policy_tag_to_agent_id_map=policy_map_for(env_name, env),
-                   device_id=device, results_dir=results_dir, verbose=verbose)
+    # the trainer class follows the policies' algorithm: DDPG (the Box envs) has its own
+    algorithms = {str(p.get("algorithm", "A2C")).upper() for p in config["policy"].values()}
+    cls = TrainerDDPG if algorithms == {"DDPG"} else Trainer
+    return cls(env_wrapper=wrapper, config=config, policy_tag_to_agent_id_map=policy_map_for(env_name, env),
+               device_id=device, results_dir=results_dir, verbose=verbose)
 
 
 def main():
