@@ -3,6 +3,8 @@
 // that samples the action, steps and restarts a finished replica `ticks` times per launch with the state in registers.
 // Acrobot and MountainCar also have cc_evaluate_impl (the ...EnvEvaluate_H<H> entries): one episode of every replica in one
 // launch with the policy network inside the kernel, greedy or sampled, writing a reward sum and a step count per replica.
+// ContinuousMountainCar and Pendulum have cc_evaluate_actor_impl (the ...EnvEvaluate_A<H> entries): the same with the
+// deterministic actor of DDPG inside the kernel, noise-free or under the tick's OU draw.
 //
 // Follows the reference's device kernels, example_envs/single_agent/classic_control/{acrobot,mountain_car,
 // continuous_mountain_car,pendulum}/*_step_numba.py.  Numba's type inference is restated expression by expression
@@ -709,6 +711,85 @@ __device__ __forceinline__ void cc_evaluate_impl(const Env &e, const float *stat
   }
 }
 
+// ---- evaluation of the Box envs (the ...EnvEvaluate_A<H> entries, DDPG): cc_evaluate_impl with cc_actor_mean in place
+// of the softmax policy.  Per tick: mean = cc_actor_mean of the observation in registers; the action is the fused
+// tick's own draw around it when scale >= 1e-8 (Philox counter {env, epoch0 + k, stream_tag, 1}, the same Box-Muller
+// expression, ou = (1 - damping) ou + stddev normal, act = mean + scale ou), else the mean itself (greedy = scale 0, as
+// the tick means it: there is no use_argmax); t += 1, Env::step, sum += reward, steps += 1, done = time-out ? 1 :
+// terminal code, stop at the first done (the terminal tick counts).  WRITES: eval_reward_sum / eval_steps / eval_done
+// [n_envs] (eval_done = 0 when `ticks` ran out first), row k of `mean_trace` and of `action_trace` (float [ticks, n_envs],
+// each optional) while the replica runs, and -- only when it drew -- ou_state[env] and the replica's epoch word +=
+// steps.  Nothing else: the env's arrays are read only, there is no restart.  The guard is cc_rollout_actor's.  The
+// loads are consumed before the tick loop and the trace stores are untracked: no wait inside the loop.
+template <int H, class Env>
+__device__ __forceinline__ void cc_evaluate_actor_impl(const Env &e, const float *state_arr,
+                                                       const float *observation_arr, const int *env_timestep_arr,
+                                                       int episode_length, int n_envs, uint32_t *rng_state,
+                                                       int stream_tag, int ticks, float *weights, const float *actor,
+                                                       int hidden, float action_scale, float action_bias,
+                                                       float *ou_state, float damping, float stddev, float scale,
+                                                       float *eval_reward_sum, int *eval_steps, int *eval_done,
+                                                       float *mean_trace, float *action_trace) {
+  static_assert(Env::CONT, "the actor's output is a Box action");
+  if (hidden != H || actor == nullptr) return;  // (uniform)
+  constexpr int S = Env::S, O = Env::O;
+  constexpr int n_w = cc_actor_floats(H, O);
+  for (int i = threadIdx.x; i < n_w; i += blockDim.x) weights[i] = actor[i];
+  __syncthreads();
+  const uint32_t k0 = rng_state[0], k1 = rng_state[1];
+  const bool draw_ou = scale >= 1.0e-8f;  // (uniform)
+  for (int env = blockIdx.x * blockDim.x + threadIdx.x; env < n_envs; env += gridDim.x * blockDim.x) {
+    int t = env_timestep_arr[env];
+    float s[S], o[O];
+    cc_load_row<S>(state_arr, env, s);
+    cc_load_row<O>(observation_arr, env, o);
+    uint32_t epoch0 = rng_state[WD_RNG_HEADER + env];
+    float ou = draw_ou ? ou_state[env] : 0.0f;
+    asm volatile("" : "+v"(t), "+v"(epoch0), "+v"(ou));
+#pragma unroll
+    for (int i = 0; i < S; ++i) asm volatile("" : "+v"(s[i]));
+#pragma unroll
+    for (int i = 0; i < O; ++i) asm volatile("" : "+v"(o[i]));
+    float sum = 0.0f;
+    int steps = 0, done = 0;
+    float *mtrace = mean_trace ? mean_trace + env : nullptr;
+    float *atrace = action_trace ? action_trace + env : nullptr;
+    for (int k = 0; k < ticks; ++k) {
+      const float mean = cc_actor_mean<H, O>(weights, o, action_scale, action_bias);
+      if (mtrace) {
+        wd_store_untracked(mtrace, mean);
+        mtrace += n_envs;
+      }
+      float act = mean;
+      if (draw_ou) {
+        const wd_u4 rnd = wd_philox4x32_10(wd_u4{(uint32_t)env, epoch0 + (uint32_t)k, (uint32_t)stream_tag, 1u}, k0, k1);
+        const float u1 = wd_u01_open_closed(rnd.x), u2 = wd_u01_open_closed(rnd.y);
+        const float normal = sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
+        ou = (1.0f - damping) * ou + stddev * normal;
+        act = mean + scale * ou;
+      }
+      if (atrace) {
+        wd_store_untracked(atrace, act);
+        atrace += n_envs;
+      }
+      t += 1;
+      float rew;
+      const int term = e.step(s, act, o, rew);
+      sum += rew;
+      steps += 1;
+      done = (t == episode_length) ? 1 : term;
+      if (done) break;
+    }
+    eval_reward_sum[env] = sum;
+    eval_steps[env] = steps;
+    eval_done[env] = done;
+    if (draw_ou) {
+      ou_state[env] = ou;
+      rng_state[WD_RNG_HEADER + env] = epoch0 + (uint32_t)steps;
+    }
+  }
+}
+
 }  // namespace
 
 // the arguments of every tick kernel after the env's step arguments
@@ -871,5 +952,37 @@ CC_ACTOR_ENTRIES(64)
   }
 CC_EVALUATE_ENTRIES(32)
 CC_EVALUATE_ENTRIES(64)
+
+// one episode of every replica of a Box env with the deterministic actor inside the kernel (cc_evaluate_actor_impl): the
+// env's step arguments (read only), then what the evaluation takes
+#define CC_EVALUATE_ACTOR_PARAMS                                                                                       \
+  uint32_t *rng_state, int stream_tag, int ticks, const float *actor, int hidden, float action_scale,                  \
+      float action_bias, float *ou_state, float damping, float stddev, float scale, float *eval_reward_sum,            \
+      int *eval_steps, int *eval_done, float *mean_trace, float *action_trace
+#define CC_EVALUATE_ACTOR_CALL(HH, ENV)                                                                                \
+  cc_evaluate_actor_impl<HH>(ENV, state_arr, observation_arr, env_timestep_arr, episode_length, n_envs, rng_state,     \
+                             stream_tag, ticks, cc_lds, actor, hidden, action_scale, action_bias, ou_state, damping,   \
+                             stddev, scale, eval_reward_sum, eval_steps, eval_done, mean_trace, action_trace)
+#define CC_EVALUATE_ACTOR_ENTRIES(HH)                                                                                  \
+  __global__ void __launch_bounds__(256, 2) HipClassicControlContinuousMountainCarEnvEvaluate_A##HH(                   \
+      const float *state_arr, const float *action_arr, const int *done_arr, const float *reward_arr,                   \
+      const float *observation_arr, float min_action, float max_action, float min_position, float max_position,        \
+      float max_speed, float goal_position, float goal_velocity, float power, const int *env_timestep_arr,             \
+      int episode_length, int n_envs, CC_EVALUATE_ACTOR_PARAMS) {                                                      \
+    extern __shared__ __attribute__((aligned(16))) float cc_lds[];                                                     \
+    const CcContinuousMountainCar e{min_action, max_action, min_position, max_position,                                \
+                                    max_speed, goal_position, goal_velocity, power};                                   \
+    CC_EVALUATE_ACTOR_CALL(HH, e);                                                                                     \
+  }                                                                                                                    \
+  __global__ void __launch_bounds__(256, 2) HipClassicControlPendulumEnvEvaluate_A##HH(                                \
+      const float *state_arr, const float *action_arr, const int *done_arr, const float *reward_arr,                   \
+      const float *observation_arr, const int *env_timestep_arr, int episode_length, int n_envs,                       \
+      CC_EVALUATE_ACTOR_PARAMS) {                                                                                      \
+    extern __shared__ __attribute__((aligned(16))) float cc_lds[];                                                     \
+    const CcPendulum e{};                                                                                              \
+    CC_EVALUATE_ACTOR_CALL(HH, e);                                                                                     \
+  }
+CC_EVALUATE_ACTOR_ENTRIES(32)
+CC_EVALUATE_ACTOR_ENTRIES(64)
 
 }  // extern "C"

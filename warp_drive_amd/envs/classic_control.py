@@ -14,7 +14,9 @@ The two discrete envs also have `HipClassicControl<X>EnvRollout_H32 / _H64`: the
 evaluated by the kernel on every tick's observation (`tick_launch(policy=...)`), and
 `HipClassicControl<X>EnvEvaluate_H32 / _H64`: one episode of every replica in one launch, greedy or sampled
 (`evaluate_launch`).  The two Box envs have `HipClassicControl<X>EnvRollout_A32 / _A64`: the tick with a deterministic
-actor network evaluated by the kernel on every tick's observation (`tick_launch(actor=...)`, DDPG).
+actor network evaluated by the kernel on every tick's observation (`tick_launch(actor=...)`, DDPG), and
+`HipClassicControl<X>EnvEvaluate_A32 / _A64`: one episode of every replica in one launch with that actor, noise-free or
+under the tick's exploration draw (`evaluate_actor_launch`).
 """
 import math
 
@@ -424,6 +426,72 @@ class _CUDAClassicControlEnv(CUDAEnvironmentContext):
         args = list(args) + [sampler.rng_state, np.int32(n_act), _stream_tag("tick"), np.int32(T), packed, np.int32(width),
                              np.int32(1 if use_argmax else 0), outputs["reward_sum"], outputs["steps"], outputs["done"],
                              np.uint64(0) if action_trace is None else action_trace]
+        return fm.get_function(name), args, block, grid, 4 * n_w
+
+    def has_live_actor_evaluate(self, width):
+        """does an evaluation kernel exist that runs one episode of every replica with the deterministic actor inside it
+        (...Evaluate_A<width>, TrainerDDPG.evaluate_episodes)?  The widths of the Rollout_A entries; only the Box envs
+        have one."""
+        widths = getattr(self, "ROLLOUT_ACTOR_WIDTHS", ())
+        if not isinstance(self.action_space[0], spaces.Box) or int(width) not in widths:
+            return False
+        name = self.cuda_step.name.replace("Step", f"Evaluate_A{int(width)}")
+        return bool(self.cuda_function_manager.has_function(name))
+
+    def evaluate_actor_launch(self, sampler, actor, ou, outputs, mean_trace=None, action_trace=None, ticks=None):
+        """One episode of every replica of a Box env in ONE launch (HipClassicControl<X>EnvEvaluate_A<width>): from the
+        state, observation and timestep the arrays hold, at most `ticks` (default: episode_length) ticks of actor ->
+        mean -> action -> step, up to the first done.  actor = (packed float32 CUDA tensor, hidden width, action_scale,
+        action_bias) as in `tick_launch(actor=...)`; ou = (damping, stddev, scale): with scale >= 1e-8 the action is the
+        fused tick's OU / Gaussian draw around the mean, else the mean itself (greedy).  outputs = {"reward_sum":
+        float32, "steps": int32, "done": int32}, CUDA tensors of at least n_envs elements; `mean_trace` / `action_trace`
+        (optional) float32 [>= ticks, n_envs]: row k = tick k's means / actions.  The launch writes those, and when it
+        draws the OU state and the sampler's epoch words; the env's arrays are read only.
+        Returns (function, arguments, block, grid, shared bytes)."""
+        from warp_drive_amd.managers.function_manager import _stream_tag
+        from warp_drive_amd.rollout import UnsupportedRolloutShape
+        import torch
+
+        fm, dm = self.cuda_function_manager, self.cuda_data_manager
+        try:
+            packed, width, action_scale, action_bias = actor
+            width, action_scale, action_bias = int(width), float(action_scale), float(action_bias)
+        except (TypeError, ValueError) as err:
+            raise UnsupportedRolloutShape("actor = (packed weights, hidden width, action_scale, action_bias), "
+                                          f"not {actor!r}") from err
+        if not self.has_live_actor_evaluate(width):
+            raise UnsupportedRolloutShape(f"{type(self).__name__} has no in-kernel evaluation of an actor of width {width}")
+        try:
+            damping, stddev, scale = (float(v) for v in ou)
+        except (TypeError, ValueError) as err:
+            raise UnsupportedRolloutShape(f"ou = (damping, stddev, scale), not {ou!r}") from err
+        E = int(dm.meta_info("n_envs"))
+        O = int(dm.get_shape(_OBSERVATIONS)[-1])
+        n_w = rollout_actor_floats(O, width)
+        if not (getattr(packed, "is_cuda", False) and packed.dtype == torch.float32 and packed.is_contiguous()
+                and packed.numel() == n_w):
+            raise UnsupportedRolloutShape(f"the packed actor must be a contiguous float32 CUDA tensor of {n_w} "
+                                          f"elements (observation {O}, width {width})")
+        T = int(self.episode_length if ticks is None else ticks)
+        for key, dtype in (("reward_sum", torch.float32), ("steps", torch.int32), ("done", torch.int32)):
+            t = outputs[key]
+            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and t.numel() >= E):
+                raise UnsupportedRolloutShape(f"outputs[{key!r}] must be a contiguous {dtype} CUDA tensor of at least "
+                                              f"{E} elements")
+        for key, t in (("mean_trace", mean_trace), ("action_trace", action_trace)):
+            if t is not None and not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == torch.float32
+                                      and len(t.shape) >= 2 and t.shape[0] >= T
+                                      and int(np.prod(t.shape[1:])) == E):
+                raise UnsupportedRolloutShape(f"{key} must be a contiguous float32 CUDA tensor [>= {T}, {E}]")
+        name = self.cuda_step.name.replace("Step", f"Evaluate_A{width}")
+        fm.initialize_functions([name])
+        _, args, block, grid, _ = self.step_launch()
+        null = np.uint64(0)
+        args = list(args) + [sampler.rng_state, _stream_tag("tick"), np.int32(T), packed, np.int32(width),
+                             np.float32(action_scale), np.float32(action_bias), dm.device_data(f"{_ACTIONS}_ou_state"),
+                             np.float32(damping), np.float32(stddev), np.float32(scale), outputs["reward_sum"],
+                             outputs["steps"], outputs["done"], null if mean_trace is None else mean_trace,
+                             null if action_trace is None else action_trace]
         return fm.get_function(name), args, block, grid, 4 * n_w
 
     def get_data_dictionary(self):

@@ -69,6 +69,16 @@ class TrainerDDPG:
     with a [32, 32] or [64, 64] actor on an env whose kernel evaluates it (`has_live_actor_rollout`) and T > 1, ONE launch
     of ...Rollout_A<width> records the whole batch; the actor is repacked in place before it.  `rollout_path` says which.
 
+    Evaluation.  `evaluate_episodes` is "per tick" by default.  Under `trainer.fused_evaluation: true` (opt-in; absent =
+    false), when the rollout is "one launch" and the env's kernel evaluates an actor of that width
+    (`has_live_actor_evaluate`), ONE launch of ...Evaluate_A<width> runs the whole episode of every replica; otherwise the
+    per-tick path is used and the reason is logged.  `evaluation_path` says which the last call took.
+    `trainer.evaluator: true` (the reference's key; default false): every logging iteration runs a greedy
+    `evaluate_episodes` -- on whichever path is available -- and adds "Mean episodic reward (test)" and "Mean episodic
+    steps (test)" (the means over the replicas) to the policy's metrics.  As in the reference, that evaluation RESTARTS
+    ALL ENVS at each log (`reset_all_envs()` before and after): the training rollout continues from fresh episodes, and
+    the running per-episode reward accumulators are cleared.
+
     Update.  DELIBERATE DEPARTURE from the reference: it calls `actor_loss.backward()` and `critic_loss.backward()` on one
     graph, so the gradient of -Q(obs, actor(obs)) with respect to the CRITIC's parameters is added to the critic's
     gradient, and the critic is partly trained to raise its own output.  Here the critic's step uses the critic loss
@@ -194,10 +204,14 @@ class TrainerDDPG:
                 self._batch_engine = RolloutEngine(env_wrapper, self.sampler, probabilities=[self.means], reset_done=True,
                                                    rollout_batch=env_batch, rollout_actor=(packed, width, scale, bias),
                                                    ticks_per_launch=self.batch_len, **self.ou_params)
-                self._batch_rollout = {"packed": {pol: packed}, "pack": pack_rollout_actor, "split": None}
+                self._batch_rollout = {"packed": {pol: packed}, "pack": pack_rollout_actor, "split": None,
+                                       "width": width, "range": (scale, bias)}
                 self.rollout_path = "one launch"
             except UnsupportedRolloutShape as err:
                 logging.info(f"whole-batch rollout not available for this shape ({err}); using the per-tick path")
+        if tcfg.get("fused_evaluation", False) and self._one_launch_evaluation() is None:
+            logging.info("trainer.fused_evaluation: no one-launch evaluation for this shape (it needs the one-launch "
+                         "rollout and an Evaluate_A entry of the actor's width); evaluate_episodes uses the per-tick path")
 
         # ---- episodic reward bookkeeping, all on the device (as Trainer)
         self._ep_reward = {pol: torch.zeros((E, N), device=self.device)}
@@ -292,8 +306,19 @@ class TrainerDDPG:
 
     # ----------------------------------------------------------------------------- train
     train = Trainer.train
-    _log_metrics = Trainer._log_metrics
     graceful_close = Trainer.graceful_close
+
+    def _evaluator_metrics(self):
+        """the reference's test evaluator: one greedy (noise-free) `evaluate_episodes`, its means over the replicas"""
+        rewards, steps = self.evaluate_episodes(use_argmax=True)
+        return {pol: {"Mean episodic reward (test)": float(rewards[pol].mean()),
+                      "Mean episodic steps (test)": float(steps[pol].mean())} for pol in self.policies}
+
+    def _log_metrics(self, iteration, metrics):
+        if self.config["trainer"].get("evaluator", False):
+            for pol, test in self._evaluator_metrics().items():
+                metrics[pol].update(test)
+        Trainer._log_metrics(self, iteration, metrics)
 
     # ------------------------------------------------------------------------ checkpoints
     def _networks(self, pol):
@@ -334,16 +359,49 @@ class TrainerDDPG:
     # ------------------------------------------------------------------- evaluate_episodes
     _evaluate_accumulate_launch = Trainer._evaluate_accumulate_launch
 
+    def _one_launch_evaluation(self):
+        """(env, width) when `evaluate_episodes` is one launch: `trainer.fused_evaluation` is true, the training rollout is
+        one launch (so the packed actor and its width exist) and the env has an Evaluate_A entry of that width; else None"""
+        br = self._batch_rollout
+        if not self.config["trainer"].get("fused_evaluation", False) or self.rollout_path != "one launch" or br is None:
+            return None
+        env = self.w.env
+        if not hasattr(env, "has_live_actor_evaluate") or not env.has_live_actor_evaluate(br["width"]):
+            return None
+        return env, br["width"]
+
     @torch.no_grad()
     def evaluate_episodes(self, **sample_params):
-        """Trainer.evaluate_episodes' contract (points 1 to 6 of its docstring, the same return types) on the per-tick
-        path: actor forward -> means, one fused tick, HipEvaluateAccumulate on `rewards` / `_done_`, `episode_length`
-        times, one all-finished check every 32 ticks.  `use_argmax=True` (greedy): the action is the actor's mean -- a
-        second engine built with exploration scale 0, which draws nothing and leaves the sampler's RNG words and the OU
-        state untouched; otherwise the training rollout's exploration noise."""
+        """Trainer.evaluate_episodes' contract (points 1 to 7 of its docstring, the same return types).  `use_argmax=True`
+        (greedy): the action is the actor's mean -- exploration scale 0, which draws nothing and leaves the sampler's RNG
+        words and the OU state untouched; otherwise the training rollout's exploration noise (`ou_params`).
+        "one launch" (`_one_launch_evaluation`): the actor is repacked in place into the tensor the rollout owns and one
+        ...Evaluate_A<width> launch runs every replica's episode; it reads the env's arrays only, so they stay as
+        `reset_all_envs()` left them.  "per tick": actor forward -> means, one fused tick (greedy: a second engine built
+        with scale 0), HipEvaluateAccumulate on `rewards` / `_done_`, `episode_length` times, one all-finished check every
+        32 ticks."""
         use_argmax = bool(sample_params.get("use_argmax", False))
         pol = self.policies[0]
         E, N, T = self.num_envs, self.w.n_agents, int(self.w.episode_length)
+        one = self._one_launch_evaluation()
+        if one is not None:
+            env, width = one
+            br = self._batch_rollout
+            self.w.reset_all_envs()
+            br["pack"](self.actors[pol], out=br["packed"][pol])  # the current weights
+            ou = (self.ou_params["damping"], self.ou_params["stddev"], 0.0 if use_argmax else self.ou_params["scale"])
+            out = {"reward_sum": torch.zeros((E, N), dtype=torch.float32, device=self.device),
+                   "steps": torch.zeros(E, dtype=torch.int32, device=self.device),
+                   "done": torch.zeros(E, dtype=torch.int32, device=self.device)}
+            fn, args, block, grid, shared = env.evaluate_actor_launch(
+                self.sampler, actor=(br["packed"][pol], width, *br["range"]), ou=ou, outputs=out, ticks=T)
+            fn(*args, block=block, grid=grid, shared=shared)
+            steps = out["steps"].cpu().numpy().astype(np.int32)
+            assert (out["done"].cpu().numpy() != 0).all(), "a replica did not finish within episode_length ticks"
+            self.evaluation_path = "one launch"
+            self._ep_reward[pol].zero_()
+            return ({pol: np.ascontiguousarray(out["reward_sum"].cpu().numpy().reshape(E, N), dtype=np.float32)},
+                    {pol: steps.copy()})
         if use_argmax and self._greedy_engine is None:
             self._greedy_engine = RolloutEngine(self.w, self.sampler, probabilities=[self.means], reset_done=True,
                                                 ticks_per_launch=1, **{**self.ou_params, "scale": 0.0})
