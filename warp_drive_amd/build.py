@@ -61,6 +61,8 @@ UNITS = {
     "wd_kernels_gw5.hsaco": ("tag_gridworld_n5.hip", []),
     # ClassicControl Acrobot, MountainCar, ContinuousMountainCar, Pendulum: step + fused tick of each
     "wd_kernels_cc.hsaco": ("classic_control.hip", []),
+    # TrainerDDPG's update (trainer.fused_update): next values, gradients, reduce, clip + Adam + soft update
+    "wd_kernels_ddpg.hsaco": ("ddpg_update.hip", []),
     "wd_kernels_test.hsaco": ("wd_test_kernels.hip", []),
 }
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")

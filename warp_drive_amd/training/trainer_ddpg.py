@@ -1,6 +1,7 @@
 """DDPG for the envs with a one-dimensional `Box` action (ClassicControl Pendulum and ContinuousMountainCar): a sibling of
 training/trainer.py::Trainer that shares its env wrapper, sampler, data placeholders, rollout engine, perf stats and
-metric log, and keeps everything of the update in the framework (no hand-written update kernels).
+metric log.  The update is the framework's by default; `trainer.fused_update: true` runs it as four launches of this
+repository's kernels (training/ddpg_update_kernels.py).
 
 Mirror of the reference's warp_drive/training/trainers/trainer_ddpg.py: a deterministic actor whose output is the mean of
 the OU / Gaussian exploration draw, a critic on cat(obs, action), target copies of both that follow by `tau`, n-step
@@ -17,6 +18,7 @@ import yaml
 from warp_drive_amd import distributed as wdd
 from warp_drive_amd.managers.function_manager import HIPSampler
 from warp_drive_amd.rollout import RolloutEngine, UnsupportedRolloutShape
+from warp_drive_amd.training import ddpg_update_kernels as duk
 from warp_drive_amd.training.data_loader import create_and_push_data_placeholders
 from warp_drive_amd.training.losses import DDPG
 from warp_drive_amd.training.models import flattened_obs_size
@@ -83,7 +85,22 @@ class TrainerDDPG:
     graph, so the gradient of -Q(obs, actor(obs)) with respect to the CRITIC's parameters is added to the critic's
     gradient, and the critic is partly trained to raise its own output.  Here the critic's step uses the critic loss
     alone and the actor's step differentiates -Q(obs, actor(obs)) with respect to the actor's parameters only (standard
-    DDPG).  Values, losses and metrics are otherwise the reference's."""
+    DDPG).  Values, losses and metrics are otherwise the reference's.
+    "framework" (default): autograd, `clip_grad_norm_`, two `torch.optim.Adam`s, `soft_update` -- about 150 small ops.
+    "kernels": under `trainer.fused_update: true` (opt-in; absent from the run's own config = false: the `True` that
+    default_configs.yaml gives the key is Trainer's A2C / PPO default and is not read here), for one agent, an actor and
+    a critic of two hidden layers of one width in {32, 64}, observations of 2 or 3 floats and `normalize_return: false`
+    (`ddpg_update_kernels.admitted_shape`; anything else logs the reason and uses the framework path): FOUR launches --
+    next values; n-step returns + both gradients as per-block partials; reduce; clip + Adam + soft update + the packed
+    actor's refill -- with nothing read back on a non-logging iteration.  The parameters of the actor and the critic, and
+    of the two targets, are then views of one flat buffer each (`FlatNetworks`), which the kernels update in place: the
+    modules stay the source of truth for `state_dict()` and the checkpoints; Adam's moments and step count live on the
+    trainer (`_adam`).  A logging iteration computes the framework path's metrics under `no_grad` from the networks
+    before the step, with the gradient norms from the reduce launch.  Works with either rollout path.  `update_path`
+    says which."""
+
+    update_path = "framework"
+    _update_kernels = None   # training/ddpg_update_kernels.py::DdpgUpdateKernels on the "kernels" path
 
     def __init__(self, env_wrapper=None, config=None, policy_tag_to_agent_id_map=None, device_id=0, results_dir=None,
                  verbose=True):
@@ -94,6 +111,8 @@ class TrainerDDPG:
         if self.world > 1:
             raise NotImplementedError("TrainerDDPG runs in a single process")
         self.device = torch.device("cuda", device_id)
+        # (read before the defaults are merged in: default_configs.yaml's `fused_update: True` is Trainer's A2C / PPO key)
+        wants_update_kernels = bool(config["trainer"].get("fused_update", False))
         defaults = yaml.safe_load(open(_DEFAULT_CONFIG))
         for key, default in defaults.items():
             if key == "policy":
@@ -173,12 +192,32 @@ class TrainerDDPG:
                 p.requires_grad_(False)
         actor_lr, critic_lr = _pair(pcfg["lr"], "lr")
         self.lr_schedules = {pol: (ParamScheduler(actor_lr), ParamScheduler(critic_lr))}
+        # (on the "kernels" update path these two are never stepped and their state stays empty: Adam's moments and step
+        # count are then `self._adam`)
         self.actor_optimizers = {pol: torch.optim.Adam(self.actors[pol].parameters(),
                                                        lr=self.lr_schedules[pol][0].get_param_value(0))}
         self.critic_optimizers = {pol: torch.optim.Adam(self.critics[pol].parameters(),
                                                         lr=self.lr_schedules[pol][1].get_param_value(0))}
         self.trainers = {pol: DDPG(discount_factor_gamma=pcfg["gamma"], normalize_advantage=pcfg["normalize_advantage"],
                                    normalize_return=pcfg["normalize_return"], n_step=self.n_step)}
+
+        # ---- update: the framework's ops, or -- when asked for and the shape is admitted -- the four update launches
+        if wants_update_kernels:
+            ok, why = duk.admitted_shape(len(self.policies), N, obs_size, int(np.prod(space.shape)), actor_cfg["fc_dims"],
+                                         critic_cfg["fc_dims"], bool(pcfg["normalize_return"]))
+            if ok and self.batch_len < max(self.n_step, 2):
+                ok, why = False, f"a batch of {self.batch_len} rows has no valid row for n_step {self.n_step}"
+            if ok:
+                self._flat = duk.FlatNetworks(self.actors[pol], self.critics[pol])
+                self._flat_target = duk.FlatNetworks(self.target_actors[pol], self.target_critics[pol])
+                self._adam = {"step": 0, "exp_avg": torch.zeros_like(self._flat.flat),
+                              "exp_avg_sq": torch.zeros_like(self._flat.flat)}
+                self._update_kernels = duk.DdpgUpdateKernels(env_wrapper.cuda_function_manager, E, self.batch_len,
+                                                             self.n_step, self._flat.H, obs_size, self.device)
+                self._actor_range = (scale, bias)
+                self.update_path = "kernels"
+            else:
+                duk.log_refusal(why)
 
         # ---- rollout: the means the tick reads, the single-tick engine, and -- when asked for -- the one-launch engine
         params = dict((config.get("sampler") or {}).get("params") or {})
@@ -255,6 +294,8 @@ class TrainerDDPG:
 
     # ---------------------------------------------------------------------------- update
     def _update_model_params(self, iteration, log):
+        if self._update_kernels is not None:
+            return self._update_with_kernels(log)
         pol = self.policies[0]
         pcfg = self.config["policy"][pol]
         T = self.batch_len
@@ -296,12 +337,52 @@ class TrainerDDPG:
             if log:
                 metrics[pol] = m
         if log:
-            cnt = float(self._ep_cnt.sum().item())
-            metrics[pol].update({
-                "Current timestep": self.current_timestep[pol], "Gradient norm (Actor)": actor_norm,
-                "Gradient norm (Critic)": critic_norm, "Learning rate (Actor)": actor_lr,
-                "Learning rate (Critic)": critic_lr,
-                "Mean episodic reward": float(self._ep_sum[pol].sum().item()) / cnt if cnt > 0 else float("nan")})
+            self._add_common_metrics(metrics[pol], pol, actor_norm, critic_norm, actor_lr, critic_lr)
+        return metrics
+
+    def _add_common_metrics(self, m, pol, actor_norm, critic_norm, actor_lr, critic_lr):
+        cnt = float(self._ep_cnt.sum().item())
+        m.update({
+            "Current timestep": self.current_timestep[pol], "Gradient norm (Actor)": actor_norm,
+            "Gradient norm (Critic)": critic_norm, "Learning rate (Actor)": actor_lr,
+            "Learning rate (Critic)": critic_lr,
+            "Mean episodic reward": float(self._ep_sum[pol].sum().item()) / cnt if cnt > 0 else float("nan")})
+
+    def _update_with_kernels(self, log):
+        """`_update_model_params` as four launches (see the class docstring); a non-logging iteration reads nothing back"""
+        pol = self.policies[0]
+        pcfg = self.config["policy"][pol]
+        T, k = self.batch_len, self._update_kernels
+        metrics = {pol: {"Total loss": float("nan")}} if log else {}
+        actor_lr = critic_lr = actor_norm = critic_norm = 0.0
+        if pcfg["to_train"] and T >= max(self.n_step, 2):
+            assert self._flat.bound() and self._flat_target.bound(), "a parameter's .data was re-assigned"
+            obs, actions = self.batch[pol]["obs"][:T], self.batch[pol]["actions"][:T]
+            rewards, done = self.batch[pol]["rewards"][:T], self.done_batch[:T]
+            self.current_timestep[pol] += self.train_batch_size
+            if log:  # the framework path's metrics, from the networks before the step
+                with torch.no_grad():
+                    next_values = self.target_critics[pol](obs[1:], self.target_actors[pol](obs[1:]))
+                    values = self.critics[pol](obs, actions)
+                    j_values = self.critics[pol](obs, self.actors[pol](obs))
+                    _, _, metrics[pol] = self.trainers[pol].compute_loss_and_metrics(
+                        self.current_timestep[pol], actions, rewards, done, values, next_values, j_values,
+                        perform_logging=True)
+            actor_lr = self.lr_schedules[pol][0].get_param_value(self.current_timestep[pol])
+            critic_lr = self.lr_schedules[pol][1].get_param_value(self.current_timestep[pol])
+            scale, bias = self._actor_range
+            k.targets(obs, self._flat_target.flat, scale, bias)
+            k.gradients(obs, actions, rewards, done, k.next_values, self._flat.flat, pcfg["gamma"], scale, bias)
+            k.reduce()
+            if log:
+                actor_norm, critic_norm = k.gradient_norms()
+            self._adam["step"] += 1
+            packed = self._batch_rollout["packed"][pol] if self._batch_rollout is not None else None
+            k.apply(self._flat.flat, self._flat_target.flat, self._adam["exp_avg"], self._adam["exp_avg_sq"],
+                    self._adam["step"], actor_lr, critic_lr, self.tau,
+                    max_norm=pcfg["max_grad_norm"] if pcfg["clip_grad_norm"] else None, packed=packed)
+        if log:
+            self._add_common_metrics(metrics[pol], pol, actor_norm, critic_norm, actor_lr, critic_lr)
         return metrics
 
     # ----------------------------------------------------------------------------- train
@@ -333,7 +414,10 @@ class TrainerDDPG:
             out[pol] = {}
             for name, net in self._networks(pol).items():
                 path = os.path.join(self.save_dir, f"{pol}_{name}_{self.current_timestep[pol]}.state_dict")
-                torch.save(net.state_dict(), path)
+                state = net.state_dict()
+                if self.update_path == "kernels":  # (views of the flat buffer: save each tensor's own floats only)
+                    state = type(state)((key, v.detach().clone()) for key, v in state.items())
+                torch.save(state, path)
                 out[pol][name] = path
         return out
 
