@@ -63,6 +63,9 @@ UNITS = {
     "wd_kernels_cc.hsaco": ("classic_control.hip", []),
     # TrainerDDPG's update (trainer.fused_update): next values, gradients, reduce, clip + Adam + soft update
     "wd_kernels_ddpg.hsaco": ("ddpg_update.hip", []),
+    # Trainer's A2C / PPO update for the in-kernel policies (trainer.fused_update: "all"): values, gradients, reduce,
+    # clip + Adam + the packed policy's refill
+    "wd_kernels_pg.hsaco": ("pg_update.hip", []),
     "wd_kernels_test.hsaco": ("wd_test_kernels.hip", []),
 }
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")

@@ -30,6 +30,7 @@ from warp_drive_amd.rollout import RolloutEngine, UnsupportedRolloutShape
 from warp_drive_amd.training.data_loader import create_and_push_data_placeholders
 from warp_drive_amd.training.grad_bucket import GradientBucket
 from warp_drive_amd.training.losses import A2C, PPO
+from warp_drive_amd.training import pg_update_kernels as pguk
 from warp_drive_amd.training import update_kernels
 from warp_drive_amd.training.models import FullyConnected, action_head_sizes, flattened_obs_size
 from warp_drive_amd.training.policy_kernel import (FusedPolicyForward, FusedRolloutTick, pack_gridworld_policy, pack_rollout_policy,
@@ -88,11 +89,17 @@ class Trainer:
             else:
                 config[key] = recursive_merge_config_dicts(config.get(key, {}), default)
         self.config = config
+        # (refused here, before anything touches the device)
+        if isinstance(config["trainer"].get("fused_update", True), str) and config["trainer"]["fused_update"] != "all":
+            raise ValueError(f"trainer.fused_update: True, False or \"all\", not {config['trainer']['fused_update']!r}")
         E = env_wrapper.n_envs
         if policy_tag_to_agent_id_map is None:
             policy_tag_to_agent_id_map = {"shared": list(range(env_wrapper.n_agents))}
         self.policy_map = {k: list(v) for k, v in policy_tag_to_agent_id_map.items()}
         self.policies = list(self.policy_map)
+        # {policy: "kernels" | "framework"}: which update a policy takes (`_setup_pg_update` decides)
+        self.update_path = {pol: "framework" for pol in self.policies}
+        self._pg_flat, self._pg_adam, self._pg_kernels, self._pg_stale_forward = {}, {}, {}, set()
         assert set(self.policies) == set(config["policy"]), "every policy needs a config entry"
         tcfg = config["trainer"]
         self.num_envs = E
@@ -298,6 +305,7 @@ class Trainer:
         # the single launch only with `trainer.fused_rollout_policy: "all"`.
         self._batch_rollout = None
         self._setup_batch_rollout(env_wrapper, tcfg)
+        self._setup_pg_update(env_wrapper, tcfg)
 
     def _setup_batch_rollout(self, env_wrapper, tcfg):
         env = env_wrapper.env
@@ -355,6 +363,40 @@ class Trainer:
         self._batch_rollout = {"packed": packed, "pack": pack, "split": split, "owners": owners, "width": width,
                                "all": wanted == "all"}
         self._want_graph = False
+
+    def _setup_pg_update(self, env_wrapper, tcfg):
+        """`trainer.fused_update: "all"` (opt-in): the update of every trained policy that
+        training/pg_update_kernels.py::admitted_shape accepts -- one [32, 32] / [64, 64] float32 policy with one head on the
+        one-launch rollout, A2C / PPO without the normalisations -- runs as FIVE launches (values, returns, gradients,
+        reduce, clip + Adam + the packed policy's refill) with nothing read back on a non-logging iteration.  Its
+        parameters become views of one flat buffer (`FlatPolicy`); Adam's moments and step count are flat buffers here
+        (`_pg_adam`; `self.optimizers[pol]` is then never stepped).  Any other policy logs the reason once and stays on
+        today's path.  `update_path` says which."""
+        if tcfg.get("fused_update", True) != "all" or self.device.type != "cuda":
+            return
+        for pol in self.policies:
+            pcfg = self.config["policy"][pol]
+            if not pcfg["to_train"]:
+                continue
+            ids = self.policy_map[pol]
+            obs_size = flattened_obs_size(env_wrapper.env.observation_space[ids[0]])
+            dtype = next(self.models[pol].parameters()).dtype if self._update_dtype is None else self._update_dtype
+            ok, why = pguk.admitted_shape(self._batch_rollout is not None, len(self.policies), len(ids), self.head_sizes,
+                                          pcfg["model"]["fc_dims"], obs_size, dtype, bool(pcfg["normalize_return"]),
+                                          bool(pcfg["normalize_advantage"]), self.neg_pos_env_ratio, self.world,
+                                          pcfg["algorithm"])
+            if ok and self._batch_rollout["pack"] is not pack_rollout_policy:
+                ok, why = False, "the rollout's packed policy is not pack_rollout_policy's layout"
+            if not ok:
+                if self.rank == 0:
+                    pguk.log_refusal(pol, why)
+                continue
+            flat = pguk.FlatPolicy(self.models[pol])
+            self._pg_flat[pol] = flat
+            self._pg_adam[pol] = {"step": 0, "exp_avg": torch.zeros_like(flat.flat), "exp_avg_sq": torch.zeros_like(flat.flat)}
+            self._pg_kernels[pol] = pguk.PgUpdateKernels(env_wrapper.cuda_function_manager, self.num_envs, self.batch_len,
+                                                         flat.H, flat.O, flat.A, self.device)
+            self.update_path[pol] = "kernels"
 
     # --------------------------------------------------------------------------- rollout
     def _inference_model(self, pol):
@@ -467,6 +509,12 @@ class Trainer:
         reward bookkeeping of `_tick`, vectorised over the recorded rows"""
         br = self._batch_rollout
         for pol in self.policies:
+            # (an Apply launch of the update kernels refilled the packed tensor from the parameters it wrote; while the
+            # parameters' version counters are what they were then, nothing on the framework's side has changed them and
+            # the repack would write the same bytes)
+            if br.get("refilled", {}).get(pol) == parameter_versions(self.models[pol]):
+                continue
+            br.get("refilled", {}).pop(pol, None)
             br["pack"](self.models[pol], out=br["packed"][pol])  # the weights of this iteration
         self.engine.run(1)
         T = self.batch_len
@@ -537,8 +585,15 @@ class Trainer:
         trained = [pol for pol in self.policies if self.config["policy"][pol]["to_train"]]
         if not trained:
             return metrics
-        self.grad_bucket.zero()  # (the .grad views stay attached to the bucket: no zero_grad(set_to_none))
-        for pol in trained:
+        on_kernels = [pol for pol in trained if self.update_path.get(pol) == "kernels"]
+        framework = [pol for pol in trained if pol not in on_kernels]
+        for pol in on_kernels:
+            m = self._update_with_pg_kernels(pol, log)
+            if log:
+                metrics[pol] = m
+        if framework:
+            self.grad_bucket.zero()  # (the .grad views stay attached to the bucket: no zero_grad(set_to_none))
+        for pol in framework:
             batch = self.batch[pol]
             if self._fused_update and self.neg_pos_env_ratio <= 0:
                 # the objective and its gradient with respect to the network's output as ONE kernel, the ReLU masks and
@@ -573,15 +628,17 @@ class Trainer:
         # the stored activations belonged to the weights that are about to change: a second update on the same batch (or
         # anything else before the next rollout) recomputes its forward pass
         self._stored_for = {}
-        self.grad_bucket.all_reduce_mean()  # ONE collective for all policies (RCCL over xGMI at N > 1)
+        if framework:
+            self.grad_bucket.all_reduce_mean()  # ONE collective for all policies (RCCL over xGMI at N > 1)
         for pol in trained:
             pcfg = self.config["policy"][pol]
-            if pcfg["clip_grad_norm"]:
-                torch.nn.utils.clip_grad_norm_(self.models[pol].parameters(), pcfg["max_grad_norm"])
-            self.optimizers[pol].step()
-            if self._fused_forward[pol] is not None:
-                self._fused_forward[pol].pack()  # the rollout kernel reads re-packed weights
-            self.models[pol].refresh_inference_cache()
+            if pol in framework:
+                if pcfg["clip_grad_norm"]:
+                    torch.nn.utils.clip_grad_norm_(self.models[pol].parameters(), pcfg["max_grad_norm"])
+                self.optimizers[pol].step()
+                if self._fused_forward[pol] is not None:
+                    self._fused_forward[pol].pack()  # the rollout kernel reads re-packed weights
+                self.models[pol].refresh_inference_cache()
             self.current_timestep[pol] += self.train_batch_size
             if log:
                 m = metrics[pol]
@@ -590,6 +647,58 @@ class Trainer:
                 cnt = float(self._ep_cnt.sum().item())
                 m["Mean episodic reward"] = float(self._ep_sum[pol].sum().item()) / cnt if cnt > 0 else float("nan")
         return metrics
+
+    def _update_with_pg_kernels(self, pol, log):
+        """one policy's gradient and optimizer step as five launches (`_setup_pg_update`); returns its metric dict on a
+        logging iteration -- formed from what the launches left on the device -- and reads nothing back otherwise"""
+        pcfg, k, flat, adam = self.config["policy"][pol], self._pg_kernels[pol], self._pg_flat[pol], self._pg_adam[pol]
+        assert flat.bound(), "a parameter's .data was re-assigned"
+        T, batch, objective = self.batch_len, self.batch[pol], self.trainers[pol]
+        obs, actions, rewards, done = batch["obs"][:T], batch["actions"][:T], batch["rewards"][:T], self.done_batch[:T]
+        vf_c = objective.vf_loss_coeff_schedule.get_param_value(self.current_timestep[pol])
+        ent_c = objective.entropy_coeff_schedule.get_param_value(self.current_timestep[pol])
+        k.compute_values(obs, flat.flat)
+        k.discounted_returns(rewards, done, objective.discount_factor_gamma)
+        k.gradients(obs, actions, flat.flat, ent_c, vf_c)
+        k.reduce()
+        metrics = k.metrics(rewards, actions, vf_coeff=vf_c, ent_coeff=ent_c, ppo=objective.clip_param is not None) if log else None
+        adam["step"] += 1
+        packed = self._batch_rollout["packed"][pol]
+        k.apply(flat.flat, adam["exp_avg"], adam["exp_avg_sq"], adam["step"], pcfg["lr"],
+                max_norm=pcfg["max_grad_norm"] if pcfg["clip_grad_norm"] else None, packed=packed)
+        # the launch wrote the parameters behind the framework's back (no version counter moved): the rollout's packed copy
+        # is current as long as the counters stay where they are, and forward_inference's cached copies are dropped (host
+        # work only; they are rebuilt by whoever calls it next)
+        self._batch_rollout.setdefault("refilled", {})[pol] = parameter_versions(self.models[pol])
+        self.models[pol]._inference_cache.clear()
+        # ... and the per-tick forward kernel's packed copy (it exists for a [64, 64] policy on enough rows; evaluation
+        # per tick and fetch_episode_states read it) is marked: `_policy_probabilities` repacks it before its next use
+        if self._fused_forward[pol] is not None:
+            self._pg_stale_forward.add(pol)
+        return metrics
+
+    def _current_fused_forward(self, pol):
+        """the per-tick forward kernel of `pol` (or None), its packed weights brought up to date first if an Apply launch
+        of the update kernels has written the parameters since they were packed"""
+        fw = self._fused_forward[pol]
+        if fw is not None and pol in self._pg_stale_forward:
+            fw.pack()
+            self._pg_stale_forward.discard(pol)
+        return fw
+
+    def mark_parameters_changed(self, pol=None):
+        """Tell the trainer that the parameters of `pol` (default: every policy) were written WITHOUT moving their version
+        counters -- through `p.data`, through `FlatPolicy.flat`, by a kernel of one's own.  In-place operations on the
+        Parameter itself (`p.add_()`, `p.copy_()`, `load_state_dict`, an optimizer step) move the counters and need no
+        call.  The next one-launch rollout repacks the policy, `forward_inference` rebuilds its copies and the per-tick
+        forward kernel is repacked here (in place: a captured tick goes on reading the same addresses)."""
+        for p in self.policies if pol is None else [pol]:
+            if self._batch_rollout is not None:
+                self._batch_rollout.get("refilled", {}).pop(p, None)
+            self.models[p]._inference_cache.clear()
+            if self._fused_forward[p] is not None:
+                self._fused_forward[p].pack()
+                self._pg_stale_forward.discard(p)
 
     # ----------------------------------------------------------------------------- train
     def train(self, num_iters=None):
@@ -645,7 +754,10 @@ class Trainer:
             return
         for pol in self.policies:
             path = os.path.join(self.save_dir, f"{pol}_{self.current_timestep[pol]}.state_dict")
-            torch.save(self._unwrap(self.models[pol]).state_dict(), path)
+            state = self._unwrap(self.models[pol]).state_dict()
+            if self.update_path.get(pol) == "kernels":  # (views of the flat buffer: save each tensor's own floats only)
+                state = type(state)((key, v.detach().clone()) for key, v in state.items())
+            torch.save(state, path)
 
     def load_model_checkpoint(self, ckpts_dict, models=None):
         """resume from `{policy}_{timestep}.state_dict`; the timestep is parsed from the name
@@ -673,7 +785,7 @@ class Trainer:
         out = {}
         for pol in self.policies:
             ids = self.ids[pol]
-            if self._fused_forward[pol] is not None:
+            if self._current_fused_forward(pol) is not None:
                 # the same kernel as the training rollout, so that evaluation (use_argmax at near-ties
                 # included) picks what the rollout would pick
                 self._fused_forward[pol](flat_obs, self._ids32[pol], self.probs)

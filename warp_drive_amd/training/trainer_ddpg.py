@@ -25,7 +25,7 @@ from warp_drive_amd.training.models import flattened_obs_size
 from warp_drive_amd.training.models_ddpg import (FullyConnectedActionValueCritic, FullyConnectedActor,
                                                  actor_output_range)
 from warp_drive_amd.training.param_scheduler import ParamScheduler
-from warp_drive_amd.training.policy_kernel import pack_rollout_actor, rollout_actor_width
+from warp_drive_amd.training.policy_kernel import pack_rollout_actor, parameter_versions, rollout_actor_width
 from warp_drive_amd.training.trainer import _DEFAULT_CONFIG, PerfStats, Trainer, recursive_merge_config_dicts
 from warp_drive_amd.utils.constants import Constants
 
@@ -95,7 +95,9 @@ class TrainerDDPG:
     actor's refill -- with nothing read back on a non-logging iteration.  The parameters of the actor and the critic, and
     of the two targets, are then views of one flat buffer each (`FlatNetworks`), which the kernels update in place: the
     modules stay the source of truth for `state_dict()` and the checkpoints; Adam's moments and step count live on the
-    trainer (`_adam`).  A logging iteration computes the framework path's metrics under `no_grad` from the networks
+    trainer (`_adam`).  `fused_update: "all"` (Trainer's opt-in for its own kernels path) means `true` here.  After the
+    Apply launch has refilled the packed actor the one-launch rollout skips its framework-side repack for as long as the
+    actor's version counters stand.  A logging iteration computes the framework path's metrics under `no_grad` from the networks
     before the step, with the gradient norms from the reduce launch.  Works with either rollout path.  `update_path`
     says which."""
 
@@ -112,7 +114,10 @@ class TrainerDDPG:
             raise NotImplementedError("TrainerDDPG runs in a single process")
         self.device = torch.device("cuda", device_id)
         # (read before the defaults are merged in: default_configs.yaml's `fused_update: True` is Trainer's A2C / PPO key)
-        wants_update_kernels = bool(config["trainer"].get("fused_update", False))
+        wants_update_kernels = config["trainer"].get("fused_update", False)
+        if isinstance(wants_update_kernels, str) and wants_update_kernels != "all":
+            raise ValueError(f"trainer.fused_update: True, False or \"all\", not {wants_update_kernels!r}")
+        wants_update_kernels = bool(wants_update_kernels)   # ("all" = true here)
         defaults = yaml.safe_load(open(_DEFAULT_CONFIG))
         for key, default in defaults.items():
             if key == "policy":
@@ -381,6 +386,8 @@ class TrainerDDPG:
             k.apply(self._flat.flat, self._flat_target.flat, self._adam["exp_avg"], self._adam["exp_avg_sq"],
                     self._adam["step"], actor_lr, critic_lr, self.tau,
                     max_norm=pcfg["max_grad_norm"] if pcfg["clip_grad_norm"] else None, packed=packed)
+            if packed is not None:  # (the rollout skips its repack while the actor's version counters stay as they are)
+                self._batch_rollout.setdefault("refilled", {})[pol] = parameter_versions(self.actors[pol])
         if log:
             self._add_common_metrics(metrics[pol], pol, actor_norm, critic_norm, actor_lr, critic_lr)
         return metrics
