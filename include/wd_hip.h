@@ -101,7 +101,9 @@ int wd_plan_run(void *plan, int repeats, void *stream);
  * 0 .. C-1 (C >= 2) are set for every entry, wd_plan_run with repeats >= 2 forks: cohort 0 runs on `stream`, cohort c
  * on a plan-owned non-blocking stream that waits on an event recorded on `stream`; each cohort runs all `repeats`
  * repetitions of its launches, and `stream` then waits on every side stream (work enqueued on `stream` afterwards
- * is ordered after every cohort).  repeats == 1 and the graph calls below run the whole-range entries on `stream`.
+ * is ordered after every cohort; when a call fails after the fork, the side streams that wait on it are still joined
+ * into `stream` before the first error is returned).  repeats == 1 and the graph calls below run the whole-range
+ * entries on `stream`.
  * Cohorts must be added before the plan's first cohort run. */
 int wd_plan_add_cohort(void *plan, int entry_index, int cohort, void *function, uint32_t grid_x,
                        uint32_t grid_y, uint32_t grid_z, uint32_t block_x, uint32_t block_y,

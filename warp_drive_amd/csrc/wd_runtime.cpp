@@ -409,19 +409,22 @@ bool cohorts_complete(const Plan *p) {
 // afterwards is ordered after every cohort.
 int plan_run_cohorts(Plan *p, int repeats, hipStream_t s) {
   const int C = static_cast<int>(p->cohorts.size());
-  if (p->side.empty()) {
+  // (created on the first cohort run; a run that could not make all of them leaves what it made to the next one, every
+  // side stream together with its join event)
+  if (!p->fork)
     if (int rc = check(g_hip.hipEventCreateWithFlags(&p->fork, hipEventDisableTiming), "hipEventCreateWithFlags"))
       return rc;
-    for (int c = 1; c < C; ++c) {
-      hipStream_t st = nullptr;
-      hipEvent_t ej = nullptr;
-      if (int rc = check(g_hip.hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreateWithFlags"))
-        return rc;
-      p->side.push_back(st);
-      if (int rc = check(g_hip.hipEventCreateWithFlags(&ej, hipEventDisableTiming), "hipEventCreateWithFlags"))
-        return rc;
-      p->join.push_back(ej);
+  while (static_cast<int>(p->side.size()) < C - 1) {
+    hipStream_t st = nullptr;
+    hipEvent_t ej = nullptr;
+    if (int rc = check(g_hip.hipStreamCreateWithFlags(&st, hipStreamNonBlocking), "hipStreamCreateWithFlags"))
+      return rc;
+    if (int rc = check(g_hip.hipEventCreateWithFlags(&ej, hipEventDisableTiming), "hipEventCreateWithFlags")) {
+      (void)g_hip.hipStreamDestroy(st);
+      return rc;
     }
+    p->side.push_back(st);
+    p->join.push_back(ej);
   }
   // timing: one bracket on the caller's stream around the whole group of cohorts (every tick of the timed entry)
   const bool timed = p->timed_entry >= 0 && (p->open || p->used < p->max_samples);
@@ -430,20 +433,25 @@ int plan_run_cohorts(Plan *p, int repeats, hipStream_t s) {
     p->open = true;
   }
   if (int rc = check(g_hip.hipEventRecord(p->fork, s), "hipEventRecord(fork)")) return rc;
-  for (int c = 1; c < C; ++c)
-    if (int rc = check(g_hip.hipStreamWaitEvent(p->side[c - 1], p->fork, 0), "hipStreamWaitEvent(fork)")) return rc;
+  // From here on an error does not return at once: a side stream that waits on the fork may already hold launches, so
+  // it is joined back into `s` first (whoever catches the error and goes on using `s` is ordered after them).
+  int rc = 0, forked = 0;  // side streams that wait on the fork
+  for (int c = 1; c < C && !rc; ++c)
+    if (!(rc = check(g_hip.hipStreamWaitEvent(p->side[c - 1], p->fork, 0), "hipStreamWaitEvent(fork)"))) ++forked;
   // tick-major: the host enqueues tick r of every cohort before tick r + 1 of any (enqueuing one cohort's ticks
   // after the other's would leave the later cohorts waiting for the host while the first one runs alone)
-  for (int r = 0; r < repeats; ++r)
-    for (int c = 0; c < C; ++c) {
+  for (int r = 0; r < repeats && !rc; ++r)
+    for (int c = 0; c < C && !rc; ++c) {
       hipStream_t st = c == 0 ? s : p->side[c - 1];
       for (auto &e : p->cohorts[c])
-        if (int rc = launch_packed(e.fn, e.g, e.b, e.shmem, st, e.args.data(), e.args.size())) return rc;
+        if ((rc = launch_packed(e.fn, e.g, e.b, e.shmem, st, e.args.data(), e.args.size()))) break;
     }
-  for (int c = 1; c < C; ++c) {
-    if (int rc = check(g_hip.hipEventRecord(p->join[c - 1], p->side[c - 1]), "hipEventRecord(join)")) return rc;
-    if (int rc = check(g_hip.hipStreamWaitEvent(s, p->join[c - 1], 0), "hipStreamWaitEvent(join)")) return rc;
+  for (int c = 1; c <= forked; ++c) {
+    int rj = check(g_hip.hipEventRecord(p->join[c - 1], p->side[c - 1]), "hipEventRecord(join)");
+    if (!rj) rj = check(g_hip.hipStreamWaitEvent(s, p->join[c - 1], 0), "hipStreamWaitEvent(join)");
+    if (!rc) rc = rj;  // the first error is the one returned
   }
+  if (rc) return rc;
   p->run_counter += repeats;
   if (timed) {
     p->pending += repeats;
@@ -606,8 +614,10 @@ int wd_plan_instantiate_graph(void *plan, int reps, void *stream) {
   int rc = plan_run_single(p, reps, s);  // the whole-range entries on one stream: no cohorts in a graph
   hipGraph_t graph = nullptr;
   int rc2 = check(g_hip.hipStreamEndCapture(s, &graph), "hipStreamEndCapture");
-  if (rc) return rc;
-  if (rc2) return rc2;
+  if (rc || rc2) {  // a failed launch still ends the capture, and what was captured is not kept
+    if (graph) (void)g_hip.hipGraphDestroy(graph);
+    return rc ? rc : rc2;
+  }
   rc = check(g_hip.hipGraphInstantiate(&p->exec, graph, nullptr, nullptr, 0), "hipGraphInstantiate");
   (void)g_hip.hipGraphDestroy(graph);
   if (!rc) p->reps_in_graph = reps;
