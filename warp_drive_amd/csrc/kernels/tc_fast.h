@@ -15,10 +15,11 @@ namespace {
 
 // EXACTK: K == KMAX, known at compile time (row offsets become immediates, the K-dependent selects fold away)
 // LOOP: called as the body of the multi-tick entry (tc_fast_rollout below) for trip `tick` of a launch; the replica-independent tables
-// are built on trip 0 and stay (`n_taggers` carries their length); the probes stamp the one trip the harness chose
+// are built on trip 0 and stay (`n_taggers` carries their length); the thread's own state arrives in `cy` and leaves in it
+// (TcCarry: read from memory on the trips `cy->reload` names only); the probes stamp the one trip the harness chose
 template <int KMAX, bool FUSED, bool EXACTK, int IDB, bool SAMPLE = FUSED, bool LOOP = false>
 __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, unsigned char *smem, int n_acc,
-                                            int n_turn, int tick = 0, int n_taggers_in = 0) {
+                                            int n_turn, int tick = 0, int n_taggers_in = 0, TcCarry *cy = nullptr) {
   WD_TC_PROBE_TICK(LOOP, tick);
   const int N = a.N, K = EXACTK ? KMAX : a.K;
   const int F = 7 * K + 1;
@@ -81,7 +82,20 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   __builtin_amdgcn_s_setprio(3);
   WD_TC_PROBE_RT(16); WD_TC_PROBE(0); WD_TC_PROBE_HW(21);
   TcIn in;
-  tc_issue_loads<FUSED, SAMPLE>(in, a, fz, env0, epb, N, n_acc, n_turn, tid, slab_acc, slab_turn, true);
+  bool reloaded = false;  // LOOP: block-uniform
+  if constexpr (LOOP) {
+    // The steady-state trip loads nothing but the slabs: the state is what this thread stored on the trip before.  Trip 0
+    // of a launch and the trip after a restore read it from memory (all of it: which arrays a restore rewrites is the
+    // host's choice), and wait for it, BEFORE the slabs are issued.
+    in = cy->in;
+    reloaded = cy->reload != 0;
+    if (reloaded) {
+      tc_load_state(in, a, fz, env0, epb, N, n_acc, n_turn, tid, tick == 0);
+      cy->in.type = in.type; cy->in.skill = in.skill; cy->in.step_reward = in.step_reward;  // (no trip writes these)
+    }
+  } else {
+    tc_issue_loads<FUSED, SAMPLE>(in, a, fz, env0, epb, N, n_acc, n_turn, tid, slab_acc, slab_turn, true);
+  }
   const bool tab_in_lds = (n_acc <= WD_TC_TAB) && (n_turn <= WD_TC_TAB);
   int n_taggers_ = n_taggers_in;
   if constexpr (LOOP) {
@@ -91,20 +105,35 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   }
   const int n_taggers = n_taggers_;
   if (env0 >= a.E) return n_taggers;  // whole block (no barrier is skipped by part of a block; the same on every trip)
-  WD_TC_PROBE(1);
+  if constexpr (!LOOP) WD_TC_PROBE(1);  // (LOOP: behind the slab issue below, so that the phase holds the same work)
 
   const int env = env0 + el;
   const bool active = (el < epb) && (env < a.E);
   const int gi = env * N + ag;  // index into [E, N] arrays
   const int li = tid;           // index into LDS arrays (= el * N + ag)
   const int agents_here = min(epb, a.E - env0) * N;
+  if constexpr (LOOP) {
+    // (a store between the slab issue and the slab wait would be waited for with the slabs: this one goes first)
+    if (active && ag == 0) a.done[env] = 0;  // a replica that finished (and was reset) last tick
+    // the slabs alias the work area: issued here, after the trip-end barrier, never earlier
+    tc_fetch_slab(slab_acc, fz.probs_acc, a, env0, epb, N, n_acc, tid);
+    tc_fetch_slab(slab_turn, fz.probs_turn, a, env0, epb, N, n_turn, tid);
+    WD_TC_PROBE(1);
+  }
   int2 sampled = in.sampled;
   const unsigned long long live_mask = __ballot(active && in.sg != 0);
-  if (compact && lane == 0) tb.live_cnt[wave] = __popcll(live_mask);
+  if constexpr (!LOOP) {
+    if (compact && lane == 0) tb.live_cnt[wave] = __popcll(live_mask);
+  }
   if constexpr ((IDB != 7) && (KMAX <= 12)) {  // (the cell-sorted packing's counters, see below)
     if (compact && tid < 64) tb.cell_cnt[tid] = 0;
   }
-  if (FUSED) {
+  if constexpr (LOOP) {
+    // (two slabs side by side, no tc_one_slab path: replicas of at most 128 agents, which is what the 7-bit ids mean)
+    static_assert(!LOOP || IDB == 7, "tc_sample_heads_carried samples from two slabs: replicas of at most 128 agents");
+    sampled = tc_sample_heads_carried(fz, in.epoch, cy->k0, cy->k1, active, gi, li, slab_acc, slab_turn, n_acc, n_turn);
+    if (compact && lane == 0) tb.live_cnt[wave] = __popcll(live_mask);  // (no LDS access between slab issue and slab wait)
+  } else if (FUSED) {
     if (active && ag == 0) a.done[env] = 0;  // a replica that finished (and was reset) last tick
     if (SAMPLE) sampled = tc_sample_heads(a, fz, in, active, gi, li, slab_acc, slab_turn, n_acc, n_turn, env0, epb);
   }
@@ -153,8 +182,12 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   const int sg = in.sg;
   const bool is_runner = active && (in.type == 0) && (sg != 0);  // member of self.runners
   if (active) {
-    const TcMoved m = tc_move(a, tb, in, sampled, gi, tab_in_lds);
+    const TcMoved m = tc_move(a, tb, in, sampled, gi, tab_in_lds, LOOP ? cy : nullptr);
     edge_pen = m.edge_pen; my_x = m.x; my_y = m.y;
+    if constexpr (LOOP) {  // what the next trip would read back
+      cy->in.x = m.x; cy->in.y = m.y;
+      cy->in.cleared = (sg == 0) ? 1 : 0;
+    }
     // agents out of the game are pushed to +BIG for the neighbour search only; every other
     // consumer (taggers are never out of the game) reads real positions
     // (with the prefilter on: NaN -- only its bound reads the entry of an agent that is out of the game then)
@@ -199,7 +232,12 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
       a.timestep[env] = t;
       tb.tstep[el] = t;
       tb.tfrac[el] = (float)((double)t / (double)a.T);  // float(t) / episode_length, :474
-      tb.nrun[el] = in.nrun;
+      if constexpr (LOOP) {
+        cy->in.tstep = t;
+        if (reloaded) tb.nrun[el] = in.nrun;  // (otherwise the count the last trip left there: the tables survive the trip)
+      } else {
+        tb.nrun[el] = in.nrun;
+      }
     }
   }
   WD_TC_PROBE(4);
@@ -621,10 +659,24 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
     __syncthreads();  // doneflag
     bool any = false;
     for (int e = 0; e < min(epb, a.E - env0); ++e) any = any || (tb.doneflag[e] != 0);
+    if constexpr (LOOP) {
+      if (active) {
+        cy->in.sg = (tagged && a.runner_exits) ? 0 : sg;
+        cy->in.epoch = in.epoch + 1u;
+      }
+      cy->reload = __builtin_amdgcn_readfirstlane(any ? 1 : 0);  // the next trip reads the restored rows from memory
+    }
     if (any) {  // block-uniform, rare (once per episode)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wavefront's stores are complete ...
       __syncthreads();                                  // ... before any wavefront rewrites the rows
       tc_reset_finished(a, fz, tb, env0, epb);
+      if constexpr (LOOP) {
+        // (Redundant TODAY: tc_fast_rollout's trip-end drain and barrier follow at once.  The pair is here so that the
+        // restore is safe by itself -- the reload does not depend on the trip-end drain, which the steady-state trip no
+        // longer needs and a later change may drop.  One barrier per episode.)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the rows this wavefront restored are complete ...
+        __syncthreads();                                  // ... before any thread of the block reads its state again
+      }
     }
   }
   WD_TC_PROBE(15); WD_TC_PROBE_RT(17);
@@ -634,22 +686,38 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
 // `ticks` ticks of the block's replicas in ONE launch (one replica per block; the fused, sampling tick).  The replicas of a
 // launch are independent, so nothing but the kernel boundary made replica r's tick t + 1 wait for replica s's tick t: here
 // every block runs on at its own pace and the blocks of a CU drift out of phase (one block's fetch and row flush under
-// another's search).  Every trip is the whole one-tick kernel: all inputs are read again from memory, both slabs are
-// fetched again, every output of every tick is stored.  Between two trips each wavefront waits for its own stores
+// another's search).  Every trip computes and STORES what the one-tick kernel stores, and fetches both slabs again (the
+// probabilities change every tick).  What a trip does not do is read back the state its own threads stored on the trip
+// before: sg, heading, acceleration, speed, position, RNG epoch, the cleared flag and the time step travel in registers
+// (TcCarry; the runner count stays in tb.nrun), the Philox key is read once per launch.  A steady-state trip is: done = 0,
+// slab issue, Philox in the shadow of the fetch, slab wait, both inverse-CDF scans, move ... -- no other load, and no
+// store, LDS access or second vmcnt wait between the slab issue and the slab wait.  The state is read from memory on trip 0
+// of a launch (the host may have written anything in between) and on the trip after a restore (tc_reset_finished,
+// block-uniform, once per episode: everything is reloaded, the reset table is the host's choice of arrays), in both cases
+// with its wait BEFORE the slabs are issued.  Between two trips each wavefront waits for its own stores
 // (s_waitcnt vmcnt(0)) and the block meets at a barrier:
-//   * the next trip reads what this one stored -- state, time step, RNG words, and, once per episode, the rows OTHER
-//     threads of the block restored (tc_reset_finished).  All wavefronts of a block share their CU's vector L1, which
+//   * the trip after a restore reads what this one stored and the rows OTHER threads of the block restored; the restore
+//     is followed by a drain and a barrier of its own.  All wavefronts of a block share their CU's vector L1, which
 //     the stores write through, and every such read is a vector load issued after the barrier: it cannot return a line
-//     older than the stores (the tables read with scalar loads -- the RNG key, the reset table -- are never written);
+//     older than the stores (the reset table, read with scalar loads, is never written);
 //   * the probability slabs alias the work area: the next trip's global_load_lds may only go out once every wavefront
 //     is done with this trip's staging buffers and tables.
+// (Replacing the trip-end vmcnt(0) by the lgkmcnt(0) the LDS reuse needs was measured in round 21: correct -- every address
+// is stored by the same wavefront on every trip, same-wavefront stores to one address complete in program order, the
+// restore keeps its drains -- but no faster, docs/rounds/r21.md; the drain stays.)
 // No barrier across blocks, no communication between them.
 template <int KMAX, bool EXACTK, int IDB>
 __device__ __forceinline__ void tc_fast_rollout(const TcArgs &a, const TcFuse &fz, unsigned char *smem, int n_acc,
                                                 int n_turn, int ticks) {
   int n_taggers = 0;
+  TcCarry cy;
+  cy.in = TcIn{};
+  cy.reload = 1;
+  // the Philox key never changes: read once per launch, kept in scalar registers
+  cy.k0 = __builtin_amdgcn_readfirstlane(fz.rng_state[0]);
+  cy.k1 = __builtin_amdgcn_readfirstlane(fz.rng_state[1]);
   for (int tick = 0; tick < ticks; ++tick) {
-    n_taggers = tc_fast_impl<KMAX, true, EXACTK, IDB, true, true>(a, fz, smem, n_acc, n_turn, tick, n_taggers);
+    n_taggers = tc_fast_impl<KMAX, true, EXACTK, IDB, true, true>(a, fz, smem, n_acc, n_turn, tick, n_taggers, &cy);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }

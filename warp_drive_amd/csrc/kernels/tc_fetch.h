@@ -1,4 +1,5 @@
 // tc_fetch.h -- fetch: every global load of a tick issued up front, probability slabs straight into LDS; the replica-independent tables.
+// (The multi-tick entry loads its state through tc_load_state on the trips that need it only, and issues the slabs itself.)
 // Part of the TagContinuous translation unit (tag_continuous.hip, which holds the design notes, the probe macros
 // and the kernel entries); split by phase in round 6 with every shipped code object byte-identical before / after.
 #pragma once
@@ -66,6 +67,50 @@ __device__ __forceinline__ void tc_issue_loads(TcIn &in, const TcArgs &a, const 
     tc_fetch_slab(slab_acc, fz.probs_acc, a, env0, epb, N, n_acc, tid);
     if (!tc_one_slab(N)) tc_fetch_slab(slab_turn, fz.probs_turn, a, env0, epb, N, n_turn, tid);
   }
+}
+
+// Multi-tick entry only: the state loads of tc_issue_loads WITHOUT the slabs, for the trips that read their state from
+// memory (trip 0 of a launch, the trip after a restore); every other trip carries it in registers (TcCarry).  Ends with
+// the wait for all of them, taken once behind the whole block of loads (the opaque asm reads every loaded value, so
+// nothing that depends on one -- the `tstep + 1` of the move -- can be pulled up between the loads) and BEFORE the caller
+// issues the slabs: the counter returns in order, a state load behind the slabs would wait for them.
+__device__ __forceinline__ void tc_load_state(TcIn &in, const TcArgs &a, const TcFuse &fz, int env0, int epb, int N,
+                                              int n_acc, int n_turn, int tid, bool want_tables) {
+  const int el = tid / N, ag = tid - el * N;
+  const int env = env0 + el;
+  const bool active = (el < epb) && (env < a.E);
+  const int gi = env * N + ag;
+  in.sg = 0; in.type = 0; in.dir = in.acc = in.speed = in.x = in.y = in.skill = 0.f;
+  in.sampled = make_int2(0, 0);
+  in.epoch = 0u;
+  in.step_reward = 0.f;
+  in.tstep = in.nrun = 0;
+  in.tab_acc = in.tab_turn = 0.f;
+  in.cleared = 0;
+  if (want_tables && n_acc <= WD_TC_TAB && n_turn <= WD_TC_TAB) {
+    if (tid < n_acc) in.tab_acc = a.acc_actions[tid];
+    if (tid < n_turn) in.tab_turn = a.turn_actions[tid];
+  }
+  if (active) {
+    in.sg = a.sig_arr[gi];
+    in.dir = a.direction[gi];
+    in.acc = a.acceleration[gi];
+    in.speed = a.speed[gi];
+    in.x = a.loc_x[gi];
+    in.y = a.loc_y[gi];
+    in.skill = a.skill_levels[ag];
+    in.type = a.agent_types[ag];
+    in.step_reward = a.step_rewards[ag];
+    in.cleared = a.obs_rows_cleared[gi];
+    in.epoch = fz.rng_state[WD_RNG_HEADER + gi];
+    if (ag == 0) {
+      in.tstep = a.timestep[env];
+      in.nrun = a.num_runners[env];
+    }
+  }
+  asm volatile("" : "+v"(in.sg), "+v"(in.dir), "+v"(in.acc), "+v"(in.speed), "+v"(in.x), "+v"(in.y), "+v"(in.skill),
+                    "+v"(in.type), "+v"(in.step_reward), "+v"(in.cleared), "+v"(in.epoch), "+v"(in.tstep), "+v"(in.nrun),
+                    "+v"(in.tab_acc), "+v"(in.tab_turn));
 }
 
 // ---- replica-independent tables: ascending tagger list, action tables.

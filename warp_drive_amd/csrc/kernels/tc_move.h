@@ -27,8 +27,9 @@ struct TcMoved {
   float x, y, edge_pen;
   TcFeat ft;
 };
+// `cy` (the multi-tick entry only): the stored heading, acceleration and speed also go to the thread's carry
 __device__ __forceinline__ TcMoved tc_move(const TcArgs &a, const TcTables &tb, const TcIn &in, int2 act, int gi,
-                                           bool tab_in_lds) {
+                                           bool tab_in_lds, TcCarry *cy = nullptr) {
   const float two_pi = 6.2831854820251465f;            // float32(2*pi), :356
   const float L = a.grid_length;
   const double diag = (double)L * 1.4142135623730951;  // float32 L * np.sqrt(2) -> f64, :146
@@ -64,6 +65,7 @@ __device__ __forceinline__ TcMoved tc_move(const TcArgs &a, const TcTables &tb, 
   a.edge_pen_arr[gi] = m.edge_pen;
   m.x = px;
   m.y = py;
+  if (cy != nullptr) { cy->in.dir = dir; cy->in.acc = acc; cy->in.speed = v; }
   m.ft.nx = (double)px / diag;    // :462 (float64 division)
   m.ft.ny = (double)py / diag;
   m.ft.nsp = v / sp_div;          // float32 division (:456-458)

@@ -43,4 +43,35 @@ __device__ __forceinline__ int2 tc_sample_heads(const TcArgs &a, const TcFuse &f
   return sampled;
 }
 
+// s_waitcnt immediate of gfx9 (vmcnt [3:0] and [15:14], expcnt [6:4], lgkmcnt [11:8]; a field of all ones does not wait).
+// Through the BUILTIN, not inline asm: the compiler's own counter bookkeeping sees it, so it does not put a second
+// vmcnt(0) -- which would also wait for every store issued since -- in front of the next LDS access for the sake of a
+// global_load_lds it believes to be in flight.
+#define WD_WAIT_VMCNT0 0x0F70
+
+// Multi-tick entry only (two slabs side by side, no tc_one_slab path: replicas of at most 128 agents, asserted at the
+// call site).  The caller has issued both slabs and NOTHING else since; between that and the wait there is only register work: the ten Philox rounds, on the epoch the thread carries
+// and the key the launch read once, run in the shadow of the fetch.  No load, no store (its acknowledgement would be
+// waited for in order with the slabs' data) and no LDS access lies in between.  The epoch word goes out with the actions.
+__device__ __forceinline__ int2 tc_sample_heads_carried(const TcFuse &fz, uint32_t epoch, uint32_t k0, uint32_t k1,
+                                                        bool active, int gi, int li, const float *slab_acc,
+                                                        const float *slab_turn, int n_acc, int n_turn) {
+  uint32_t e = epoch;
+  asm volatile("" : "+v"(e));  // (opaque, ordered after the slab issue: the rounds are not hoisted in front of it ...)
+  wd_u4 rnd = wd_philox4x32_10(wd_u4{(uint32_t)gi, e, (uint32_t)fz.stream_tag, 3u}, k0, k1);  // (every lane: no branch)
+  asm volatile("" : "+v"(rnd.x), "+v"(rnd.y));  // (... and not sunk behind the wait)
+  // every global_load_lds of this wavefront has landed once its vmcnt drains; the rows a lane reads were all fetched by
+  // its own wavefront
+  __builtin_amdgcn_s_waitcnt(WD_WAIT_VMCNT0);
+  __builtin_amdgcn_wave_barrier();
+  int2 sampled = make_int2(0, 0);
+  if (active) {
+    sampled.x = wd_slab_sample(slab_acc + (size_t)li * n_acc, n_acc, wd_u01_open_closed(rnd.x));
+    sampled.y = wd_slab_sample(slab_turn + (size_t)li * n_turn, n_turn, wd_u01_open_closed(rnd.y));
+    ((int2 *)fz.actions_out)[gi] = sampled;
+    fz.rng_state[WD_RNG_HEADER + gi] = epoch + 1u;
+  }
+  return sampled;
+}
+
 }  // namespace

@@ -140,4 +140,14 @@ struct TcIn {
   int cleared;              // obs_rows_cleared[agent] (fast path)
 };
 
+// Multi-tick entry only (tc_fast_rollout): what a thread keeps in registers from one trip to the next instead of reading back
+// what it stored a few thousand cycles earlier.  `in` holds, after a trip, exactly the values that trip stored (sg, dir, acc,
+// speed, x, y, epoch, cleared, the time step in the lane of agent 0) next to the ones that never change (type, skill, step
+// reward); `nrun` is not carried here: tb.nrun lies behind the slab area and survives the trip.
+struct TcCarry {
+  TcIn in;
+  int reload;        // block-uniform: this trip reads its state from memory (trip 0 of a launch; the trip after a restore)
+  uint32_t k0, k1;   // the Philox key rng_state[0..1], read once per launch
+};
+
 }  // namespace
