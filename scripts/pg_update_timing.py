@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Trainer's A2C update on its two paths -- "framework" (framework GEMMs, FusedObjective, autograd, clip_grad_norm_,
 torch.optim.Adam, the repack) and "kernels" (`trainer.fused_update: "all"`: five launches,
-training/pg_update_kernels.py) -- in ONE process on the one-launch rollout, at four shapes: Cartpole E = 100 000 with
-T = 10 (the shipped shape) and T = 50, single_acrobot as shipped (E = 100, T = 500), and the learning test's Acrobot
-E = 1000, T = 50.
+training/pg_update_kernels.py) -- in ONE process on the one-launch rollout, at seven shapes: Cartpole E = 100 000 with
+T = 10 (the shipped shape) and T = 50, single_acrobot as shipped (E = 100, T = 500), the learning test's Acrobot
+E = 1000, T = 50, and TagGridWorld (training/pg_update_gridworld_kernels.py: five launches PER trained policy) at
+tag_gridworld.yaml's E = 1000, T = 100 with [32, 32] and with [64, 64] policies, both trained, and at the learning test's
+E = 600, T = 100 on a 20 x 20 grid with the taggers alone trained.
 
 Per shape: two trainers, same seed.  Per repeat and path: `--warmup` iterations, then `--iterations` iterations; every
 iteration is rollout, synchronise, device event, `_update_model_params(it, False)`, device event.  The paths alternate
@@ -12,7 +14,7 @@ repeats, of the update and of the whole iteration (rollout + update, host clock 
 kernels path also the device time of each of the five launches.  A last line per shape says whether the slowest repeat
 of the kernels path is faster than the fastest repeat of the framework path.
 
-    python scripts/pg_update_timing.py [--iterations 200] [--warmup 20] [--repeats 5] [--shapes 0,1,2,3]
+    python scripts/pg_update_timing.py [--iterations 200] [--warmup 20] [--repeats 5] [--shapes 0,1,2,3,4,5,6]
 """
 import argparse
 import json
@@ -26,19 +28,30 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-SHAPES = (("cartpole", 100000, 10), ("cartpole", 100000, 50), ("acrobot", 100, 500), ("acrobot", 1000, 50))
+# (env, replicas, ticks[, TagGridWorld: hidden width, trained policies, grid length])
+SHAPES = (("cartpole", 100000, 10), ("cartpole", 100000, 50), ("acrobot", 100, 500), ("acrobot", 1000, 50),
+          ("tag_gridworld", 1000, 100, 32, ("tagger", "runner"), 10), ("tag_gridworld", 1000, 100, 64, ("tagger", "runner"), 10),
+          ("tag_gridworld", 600, 100, 32, ("tagger",), 20))
 
 
-def build(env, E, T, fused, results_dir):
+def build(env, E, T, fused, results_dir, width=None, trained=("shared",), grid_length=None):
     from warp_drive_amd.training.scripts.train import setup_trainer
 
     trainer = {"num_envs": E, "train_batch_size": E * T, "num_episodes": 10 ** 6, "seed": 1, "fused_rollout_policy": "all"}
     if fused:
         trainer["fused_update"] = "all"
     ov = {"trainer": trainer, "saving": {"metrics_log_freq": 10 ** 9, "model_params_save_freq": 0}}
+    name = f"single_{env}"
+    if env == "tag_gridworld":
+        name = env
+        ov["env"] = {"grid_length": grid_length}
+        ov["policy"] = {p: {"to_train": p in trained, "algorithm": "A2C", "vf_loss_coeff": 1, "entropy_coeff": 0.05, "gamma": 0.98,
+                            "lr": 0.001, "model": {"type": "fully_connected", "fc_dims": [width, width], "model_ckpt_filepath": ""}}
+                        for p in ("runner", "tagger")}
     torch.manual_seed(1)
-    tr = setup_trainer(f"single_{env}", ov, results_dir=results_dir, verbose=False)
-    assert tr._batch_rollout is not None and tr.update_path == {"shared": "kernels" if fused else "framework"}
+    tr = setup_trainer(name, ov, results_dir=results_dir, verbose=False)
+    assert tr._batch_rollout is not None
+    assert all(tr.update_path[p] == ("kernels" if fused else "framework") for p in trained), tr.update_path
     return tr
 
 
@@ -60,9 +73,8 @@ def run(tr, first, count):
     return [1e3 * a.elapsed_time(b) for a, b in events], whole
 
 
-def per_launch(tr, count):
-    """device microseconds of each of the five launches (medians), on the trainer's current batch"""
-    pol = tr.policies[0]
+def per_launch(tr, count, pol):
+    """device microseconds of each of the five launches of `pol` (medians), on the trainer's current batch"""
     k, T, pcfg = tr._pg_kernels[pol], tr.batch_len, tr.config["policy"][pol]
     b, flat, adam = tr.batch[pol], tr._pg_flat[pol], tr._pg_adam[pol]
     packed = tr._batch_rollout["packed"][pol]
@@ -103,9 +115,10 @@ def main():
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this measures the device: no GPU, no number"
     paths = ("framework", "kernels")
-    for env, E, T in [SHAPES[int(i)] for i in args.shapes.split(",")]:
+    for env, E, T, *more in [SHAPES[int(i)] for i in args.shapes.split(",")]:
+        trained = more[1] if more else ("shared",)
         with tempfile.TemporaryDirectory() as tmp:
-            trainers = {p: build(env, E, T, p == "kernels", os.path.join(tmp, p)) for p in paths}
+            trainers = {p: build(env, E, T, p == "kernels", os.path.join(tmp, p), *more) for p in paths}
             update = {p: [] for p in paths}
             whole = {p: [] for p in paths}
             it = 0
@@ -118,14 +131,18 @@ def main():
                 it += args.warmup + args.iterations
             records = {}
             for p in paths:
-                records[p] = {"env": env, "envs": E, "ticks": T, "rows": E * T, "path": p, "iterations": args.iterations,
+                rows = {pol: E * T * len(trainers[p].policy_map[pol]) for pol in trained}
+                records[p] = {"env": env, "envs": E, "ticks": T, "rows": sum(rows.values()), "path": p, "iterations": args.iterations,
                               "warmup": args.warmup, "repeats": args.repeats, "update": summary(update[p]),
                               "iteration": summary(whole[p])}
+                if more:
+                    records[p].update({"hidden": more[0], "trained": {pol: rows[pol] for pol in trained}})
                 if p == "kernels":
-                    records[p]["launch_us"] = per_launch(trainers[p], 50)
+                    launches = {pol: per_launch(trainers[p], 50, pol) for pol in trained}
+                    records[p]["launch_us"] = launches if more else launches["shared"]
                 print(json.dumps(records[p]), flush=True)
             k, f = records["kernels"]["update"], records["framework"]["update"]
-            print(json.dumps({"env": env, "envs": E, "ticks": T, "kernels_slowest_repeat_us": k["max_us"],
+            print(json.dumps({"env": env, "envs": E, "ticks": T, **({"hidden": more[0]} if more else {}), "kernels_slowest_repeat_us": k["max_us"],
                               "framework_fastest_repeat_us": f["min_us"], "kernels_faster": k["max_us"] < f["min_us"],
                               "ratio_of_medians": round(f["median_us"] / k["median_us"], 2)}), flush=True)
             for tr in trainers.values():

@@ -66,6 +66,8 @@ UNITS = {
     # Trainer's A2C / PPO update for the in-kernel policies (trainer.fused_update: "all"): values, gradients, reduce,
     # clip + Adam + the packed policy's refill
     "wd_kernels_pg.hsaco": ("pg_update.hip", []),
+    # the same update for the two policies of the one-launch TagGridWorld rollout (21 inputs, five actions, n agents)
+    "wd_kernels_pg_gw.hsaco": ("pg_update_gridworld.hip", []),
     "wd_kernels_test.hsaco": ("wd_test_kernels.hip", []),
 }
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")

@@ -30,6 +30,7 @@ from warp_drive_amd.rollout import RolloutEngine, UnsupportedRolloutShape
 from warp_drive_amd.training.data_loader import create_and_push_data_placeholders
 from warp_drive_amd.training.grad_bucket import GradientBucket
 from warp_drive_amd.training.losses import A2C, PPO
+from warp_drive_amd.training import pg_update_gridworld_kernels as pggk
 from warp_drive_amd.training import pg_update_kernels as pguk
 from warp_drive_amd.training import update_kernels
 from warp_drive_amd.training.models import FullyConnected, action_head_sizes, flattened_obs_size
@@ -336,6 +337,13 @@ class Trainer:
         if len(widths) != 1 or None in widths:
             return
         width = widths.pop()
+        # (RolloutEngine's own question, asked before the policies are packed: TagGridWorld with another number of agents has
+        # no such kernel, and pack_gridworld_policy is written for its 21 observation floats)
+        has = getattr(env, "has_live_policy_rollout", None)
+        if has is None or not has(width, int(self.head_sizes[0])):
+            logging.info(f"whole-batch rollout not available for this shape ({type(env).__name__} has no rollout kernel that "
+                         f"evaluates a policy of hidden width {width} for this shape); using the per-tick path")
+            return
         pack = pack_gridworld_policy if getattr(env, "ROLLOUT_POLICY_PACKING", "") == "gridworld" else pack_rollout_policy
         packed = {pol: pack(self.models[pol]).to(self.device) for pol in self.policies}
         E, N, T = self.num_envs, env_wrapper.n_agents, self.batch_len
@@ -370,8 +378,11 @@ class Trainer:
         one-launch rollout, A2C / PPO without the normalisations -- runs as FIVE launches (values, returns, gradients,
         reduce, clip + Adam + the packed policy's refill) with nothing read back on a non-logging iteration.  Its
         parameters become views of one flat buffer (`FlatPolicy`); Adam's moments and step count are flat buffers here
-        (`_pg_adam`; `self.optimizers[pol]` is then never stepped).  Any other policy logs the reason once and stays on
-        today's path.  `update_path` says which."""
+        (`_pg_adam`; `self.optimizers[pol]` is then never stepped).  A policy that rule refuses is offered to
+        training/pg_update_gridworld_kernels.py::admitted_gridworld_shape -- the policies of the one-launch TagGridWorld
+        rollout: any number of them, n agents each, the same five launches per trained policy on its own batch tensors, the
+        refill in pack_gridworld_policy's layout.  Any other policy logs the reason once and stays on today's path;
+        `update_path` says which, per policy (it may be mixed)."""
         if tcfg.get("fused_update", True) != "all" or self.device.type != "cuda":
             return
         for pol in self.policies:
@@ -387,15 +398,31 @@ class Trainer:
                                           pcfg["algorithm"])
             if ok and self._batch_rollout["pack"] is not pack_rollout_policy:
                 ok, why = False, "the rollout's packed policy is not pack_rollout_policy's layout"
+            gridworld = False
             if not ok:
+                # ... or one of the policies of the one-launch TagGridWorld rollout (training/pg_update_gridworld_kernels.py:
+                # any number of policies, n agents each, 21 observation floats, five actions)
+                gridworld, gw_why = pggk.admitted_gridworld_shape(
+                    self._batch_rollout is not None,
+                    self._batch_rollout is not None and self._batch_rollout["pack"] is pack_gridworld_policy,
+                    len(self.policies), len(ids), self.head_sizes, pcfg["model"]["fc_dims"], obs_size, dtype,
+                    bool(pcfg["normalize_return"]), bool(pcfg["normalize_advantage"]), self.neg_pos_env_ratio, self.world,
+                    pcfg["algorithm"])
+                if not gridworld and self._batch_rollout is not None and self._batch_rollout["pack"] is pack_gridworld_policy:
+                    why = gw_why   # (a gridworld policy is told what the gridworld kernels miss, not that it has 5 agents)
+            if not ok and not gridworld:
                 if self.rank == 0:
                     pguk.log_refusal(pol, why)
                 continue
             flat = pguk.FlatPolicy(self.models[pol])
             self._pg_flat[pol] = flat
             self._pg_adam[pol] = {"step": 0, "exp_avg": torch.zeros_like(flat.flat), "exp_avg_sq": torch.zeros_like(flat.flat)}
-            self._pg_kernels[pol] = pguk.PgUpdateKernels(env_wrapper.cuda_function_manager, self.num_envs, self.batch_len,
-                                                         flat.H, flat.O, flat.A, self.device)
+            if gridworld:
+                self._pg_kernels[pol] = pggk.PgGridworldUpdateKernels(env_wrapper.cuda_function_manager, self.num_envs,
+                                                                      self.batch_len, len(ids), flat.H, self.device)
+            else:
+                self._pg_kernels[pol] = pguk.PgUpdateKernels(env_wrapper.cuda_function_manager, self.num_envs, self.batch_len,
+                                                             flat.H, flat.O, flat.A, self.device)
             self.update_path[pol] = "kernels"
 
     # --------------------------------------------------------------------------- rollout
