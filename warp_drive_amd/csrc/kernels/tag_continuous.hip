@@ -181,7 +181,9 @@ __global__ void __launch_bounds__(512, 4) WD_TC_SHAPE_NAME(HipTagContinuousRollo
   WD_TC_PACK();
   WD_TC_FUSE_PACK();
   a.N = WD_TC_SHAPE_N; a.K = WD_TC_KM;
-  tc_fast_rollout<WD_TC_KM, true, 7>(a, fz, tc_smem, WD_TC_SHAPE_A, WD_TC_SHAPE_A, kNumTicks);
+  // (the shape once more as template arguments: the loop's slab issue is written for constants, tc_fetch_slabs_straight)
+  tc_fast_rollout<WD_TC_KM, true, 7, WD_TC_SHAPE_N, WD_TC_SHAPE_A, WD_TC_SHAPE_THREADS>(a, fz, tc_smem, WD_TC_SHAPE_A,
+                                                                                        WD_TC_SHAPE_A, kNumTicks);
 }
 #else
 __global__ void __launch_bounds__(512, 4) WD_TC_SHAPE_NAME(HipTagContinuousStep_K)(WD_TC_PARAMS) {

@@ -17,7 +17,9 @@ namespace {
 // LOOP: called as the body of the multi-tick entry (tc_fast_rollout below) for trip `tick` of a launch; the replica-independent tables
 // are built on trip 0 and stay (`n_taggers` carries their length); the thread's own state arrives in `cy` and leaves in it
 // (TcCarry: read from memory on the trips `cy->reload` names only); the probes stamp the one trip the harness chose
-template <int KMAX, bool FUSED, bool EXACTK, int IDB, bool SAMPLE = FUSED, bool LOOP = false>
+// SN, SA, ST (LOOP only): the shape's agents, head size and block size as constants, for the straight-line slab issue
+template <int KMAX, bool FUSED, bool EXACTK, int IDB, bool SAMPLE = FUSED, bool LOOP = false, int SN = 0, int SA = 0,
+          int ST = 0>
 __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, unsigned char *smem, int n_acc,
                                             int n_turn, int tick = 0, int n_taggers_in = 0, TcCarry *cy = nullptr) {
   WD_TC_PROBE_TICK(LOOP, tick);
@@ -116,8 +118,10 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
     // (a store between the slab issue and the slab wait would be waited for with the slabs: this one goes first)
     if (active && ag == 0) a.done[env] = 0;  // a replica that finished (and was reset) last tick
     // the slabs alias the work area: issued here, after the trip-end barrier, never earlier
-    tc_fetch_slab(slab_acc, fz.probs_acc, a, env0, epb, N, n_acc, tid);
-    tc_fetch_slab(slab_turn, fz.probs_turn, a, env0, epb, N, n_turn, tid);
+    // (straight-line code: the shape is a constant of this object -- a.N == SN, n_acc == n_turn == SA, one replica per
+    // block, all set by the entry -- and so is where the slabs lie)
+    static_assert(!LOOP || (SN > 0 && SA > 0 && ST == WD_TC_BLOCKDIM), "the multi-tick entry is built for one shape");
+    tc_fetch_slabs_straight<SN, SA, ST>(slab_acc, slab_turn, fz.probs_acc, fz.probs_turn, env0, wave, lane);
     WD_TC_PROBE(1);
   }
   int2 sampled = in.sampled;
@@ -706,7 +710,7 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
 // is stored by the same wavefront on every trip, same-wavefront stores to one address complete in program order, the
 // restore keeps its drains -- but no faster, docs/rounds/r21.md; the drain stays.)
 // No barrier across blocks, no communication between them.
-template <int KMAX, bool EXACTK, int IDB>
+template <int KMAX, bool EXACTK, int IDB, int SN, int SA, int ST>
 __device__ __forceinline__ void tc_fast_rollout(const TcArgs &a, const TcFuse &fz, unsigned char *smem, int n_acc,
                                                 int n_turn, int ticks) {
   int n_taggers = 0;
@@ -717,7 +721,7 @@ __device__ __forceinline__ void tc_fast_rollout(const TcArgs &a, const TcFuse &f
   cy.k0 = __builtin_amdgcn_readfirstlane(fz.rng_state[0]);
   cy.k1 = __builtin_amdgcn_readfirstlane(fz.rng_state[1]);
   for (int tick = 0; tick < ticks; ++tick) {
-    n_taggers = tc_fast_impl<KMAX, true, EXACTK, IDB, true, true>(a, fz, smem, n_acc, n_turn, tick, n_taggers, &cy);
+    n_taggers = tc_fast_impl<KMAX, true, EXACTK, IDB, true, true, SN, SA, ST>(a, fz, smem, n_acc, n_turn, tick, n_taggers, &cy);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }

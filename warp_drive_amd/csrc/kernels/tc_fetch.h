@@ -17,6 +17,76 @@ __device__ __forceinline__ void tc_fetch_slab(float *slab, const float *probs, c
   wd_slab_fetch(slab + (size_t)r0 * n_actions, probs + ((long)env0 * N + r0) * n_actions, wrows * n_actions, lane);
 }
 
+// ---- Multi-tick entry only: the slab issue as straight-line code, for a shape whose sizes are compile-time constants
+// (N agents = ONE replica per block of T threads, A-way heads).  tc_fetch_slab above derives the wavefront's row count from
+// `tid >> 6` in vector registers, so each slab is compiled as a divergent exec-mask loop of 17 instructions per
+// global_load_lds (docs/rounds/r23.md); here the wavefront index is a scalar, the counts below are constants, and a
+// wavefront's pieces of a slab are consecutive loads off ONE per-lane global address and ONE LDS base: the instruction's
+// immediate offset advances both alike (1 KiB per piece).  The immediate reaches 4095, so every WD_TC_SLAB_REACH pieces take
+// a new base pair.  Only the last, partial vector piece and the < 4 trailing floats are exec-masked.  The LDS image is
+// wd_slab_fetch's, byte for byte.
+constexpr int WD_TC_SLAB_REACH = 4;  // pieces of 64 lanes x 16 bytes that one base pair reaches: 1024 * 3 <= 4095
+constexpr int tc_slab_rows(int N, int wave) { return N - 64 * wave >= 64 ? 64 : N - 64 * wave > 0 ? N - 64 * wave : 0; }
+constexpr int tc_slab_vecs(int N, int A, int wave) { return tc_slab_rows(N, wave) * A / 4; }       // 16-byte vectors
+constexpr int tc_slab_full(int N, int A, int wave) { return tc_slab_vecs(N, A, wave) / 64; }       // unmasked pieces
+constexpr int tc_slab_last(int N, int A, int wave) { return tc_slab_vecs(N, A, wave) % 64; }       // lanes of the last piece
+constexpr int tc_slab_tail(int N, int A, int wave) { return tc_slab_rows(N, wave) * A % 4; }       // trailing floats
+
+// pieces [C, END) of a wavefront's part of one slab.  s = the part's first byte in memory, vo = 16 * lane, l = the part's
+// first byte in LDS (an LDS address, a constant of the kernel)
+template <int C, int END>
+__device__ __forceinline__ void tc_slab_pieces(const char *s, unsigned vo, unsigned l) {
+  if constexpr (C < END) {
+    constexpr unsigned B = (C / WD_TC_SLAB_REACH) * WD_TC_SLAB_REACH * 1024u;  // bytes from piece 0 to this piece's base pair
+    __builtin_amdgcn_global_load_lds(WD_GLOBAL_PTR(s + (vo + B)), (__attribute__((address_space(3))) void *)(l + B), 16,
+                                     1024 * (C % WD_TC_SLAB_REACH), 0);
+    tc_slab_pieces<C + 1, END>(s, vo, l);
+  }
+}
+
+// rows [64 * WAVE, ...) of both heads: pa, pt = the replica's first row in memory; la, lt = the slabs' LDS addresses
+template <int N, int A, int WAVE>
+__device__ __forceinline__ void tc_fetch_slabs_wave(unsigned la, unsigned lt, const float *pa, const float *pt, int lane) {
+  constexpr int NVEC = tc_slab_vecs(N, A, WAVE), FULL = tc_slab_full(N, A, WAVE), LAST = tc_slab_last(N, A, WAVE),
+                TAIL = tc_slab_tail(N, A, WAVE);
+  constexpr unsigned PART = 4u * 64 * WAVE * A;  // bytes of a slab in front of this wavefront's rows
+  const char *const sa = (const char *)pa + PART, *const st = (const char *)pt + PART;
+  const unsigned vo = 16u * (unsigned)lane;
+  tc_slab_pieces<0, FULL>(sa, vo, la + PART);
+  tc_slab_pieces<0, FULL>(st, vo, lt + PART);
+  if constexpr (LAST != 0) {
+    if (lane < LAST) {
+      tc_slab_pieces<FULL, FULL + 1>(sa, vo, la + PART);
+      tc_slab_pieces<FULL, FULL + 1>(st, vo, lt + PART);
+    }
+  }
+  if constexpr (TAIL != 0) {  // (one dword per lane: an address of its own, the base pair of the piece it follows)
+    constexpr unsigned B = (NVEC / (64 * WD_TC_SLAB_REACH)) * WD_TC_SLAB_REACH * 1024u;
+    static_assert(16 * NVEC - B <= 4095, "the trailing floats are within reach of the last base pair");
+    if (lane < TAIL) {
+      const unsigned v1 = 4u * (unsigned)lane + B;
+      __builtin_amdgcn_global_load_lds(WD_GLOBAL_PTR(sa + v1), (__attribute__((address_space(3))) void *)(la + PART + B), 4,
+                                       16 * NVEC - B, 0);
+      __builtin_amdgcn_global_load_lds(WD_GLOBAL_PTR(st + v1), (__attribute__((address_space(3))) void *)(lt + PART + B), 4,
+                                       16 * NVEC - B, 0);
+    }
+  }
+}
+
+// both slabs of the block's replica `env`; `wave` is the wavefront's index in a scalar register (readfirstlane)
+template <int N, int A, int T>
+__device__ __forceinline__ void tc_fetch_slabs_straight(float *slab_acc, float *slab_turn, const float *probs_acc,
+                                                        const float *probs_turn, int env, int wave, int lane) {
+  static_assert(N > 64 && N <= 128 && T == 128, "one replica per block of two wavefronts, at most 128 agents");
+  static_assert(tc_slab_rows(N, 0) + tc_slab_rows(N, 1) == N, "the two wavefronts' rows are the replica's");
+  static_assert(64 * A % 4 == 0, "wavefront 1's rows start on a 16-byte boundary of the slab");
+  const float *const pa = probs_acc + (size_t)env * (N * A), *const pt = probs_turn + (size_t)env * (N * A);
+  // (an LDS pointer, not the low half of the generic one: that conversion carries a null check per use)
+  const unsigned la = (unsigned)(size_t)WD_LDS_PTR(slab_acc), lt = (unsigned)(size_t)WD_LDS_PTR(slab_turn);
+  if (wave == 0) tc_fetch_slabs_wave<N, A, 0>(la, lt, pa, pt, lane);
+  else tc_fetch_slabs_wave<N, A, 1>(la, lt, pa, pt, lane);
+}
+
 // Replicas of more than 256 agents sample the two heads one after the other from ONE slab (the second head's rows
 // are fetched into the same LDS after the first head was sampled: wave-private rows, no block barrier): both slabs
 // of a 1005-agent replica with 21-way heads are 169 KB, and at ~510 agents half the LDS means two blocks per CU.
