@@ -59,6 +59,8 @@ UNITS = {
     "wd_kernels_mlp.hsaco": ("policy_mlp.hip", ["-DWD_MLP_PART=1"]),
     "wd_kernels_update.hsaco": ("policy_mlp.hip", ["-DWD_MLP_PART=2"]),
     "wd_kernels_gw5.hsaco": ("tag_gridworld_n5.hip", []),
+    # the same rollout for the env with a reset pool: 256 coordinate quotients, the pool row drawn inside the kernel
+    "wd_kernels_gw5_pool.hsaco": ("tag_gridworld_n5_pool.hip", []),
     # ClassicControl Acrobot, MountainCar, ContinuousMountainCar, Pendulum: step + fused tick of each
     "wd_kernels_cc.hsaco": ("classic_control.hip", []),
     # TrainerDDPG's update (trainer.fused_update): next values, gradients, reduce, clip + Adam + soft update

@@ -89,6 +89,8 @@ class EnvWrapper:
         self.env_resetter = HIPEnvironmentReset(function_manager=self.cuda_function_manager)
         self.env_resetter.register_custom_reset_function(self.cuda_data_manager,
                                                          reset_function_name=f"Hip{self.name}Reset")
+        # an env whose rollout kernel draws from the reset pool itself asks the resetter whether its generator is ready
+        self.env.cuda_env_resetter = self.env_resetter
 
     # ------------------------------------------------------------------------- reset
     def _push_initial_data(self):

@@ -474,3 +474,177 @@ class CUDATagGridWorldWithResetPool(_DeviceStepMixin, TagGridWorld):
         pool.add_pool_for_reset(name=f"{_LOC_X}_reset_pool", data=np.stack(xs), reset_target=_LOC_X)
         pool.add_pool_for_reset(name=f"{_LOC_Y}_reset_pool", data=np.stack(ys), reset_target=_LOC_Y)
         return pool
+
+    # ------------------------------------------------------------------ the one-launch rollout (tag_gridworld_n5_pool.hip)
+    # HipTagGridWorldRollout_N5P / _N5P_H<width> run T ticks per launch and draw the pool row of a finished replica
+    # themselves, HipTagGridWorldEvaluate_N5P_H<width> runs one episode per replica.  There is no fused SINGLE tick for this
+    # env: without the batch tensors RolloutEngine builds sample, step, table reset, two pool launches, undo.
+    ROLLOUT_POOL_RESET = True      # RolloutEngine: the T-tick entries restart from the pool inside the kernel
+    ROLLOUT_POLICY_OPT_IN = True   # Trainer: the one launch only under `trainer.fused_rollout_policy: "all"`
+    POOL_MAX_COORD = 255           # GW5P_MAX_COORD: the quotient table has 256 entries
+
+    def _pools(self):
+        """(name of the x pool, name of the y pool, rows) when the pools are exactly loc_x's and loc_y's, [rows, 5] each
+        with the same number of rows; else None"""
+        dm = self.cuda_data_manager
+        pools = dict(dm.reset_target_to_pool)
+        if sorted(pools) != sorted([_LOC_X, _LOC_Y]):
+            return None
+        sx, sy = tuple(dm.get_shape(pools[_LOC_X])), tuple(dm.get_shape(pools[_LOC_Y]))
+        if sx != sy or len(sx) != 2 or sx[1] != self.num_agents or sx[0] < 1:
+            return None
+        return pools[_LOC_X], pools[_LOC_Y], int(sx[0])
+
+    def _pool_generator(self):
+        """the resetter's pool generator words (HIPEnvironmentReset.init_reset_pool), None before that call"""
+        return getattr(getattr(self, "cuda_env_resetter", None), "_pool_rng", None)
+
+    def pool_rollout_lds_bytes(self, width=0, cache_dwords=None, n_pool=None):
+        """dynamic LDS of the N5P entries (the layout of gw5p_rollout in tag_gridworld_n5_pool.hip): the image and the
+        restore cache of 12 replicas, 256 coordinate quotients, the time table, the two pools and the two packed policies
+        (width 0, the fixed-probability entry: none), every part a whole number of 16-byte vectors.  The evaluation
+        entries have neither cache nor pools (cache_dwords = 0, n_pool = 0)."""
+        N, F = self.num_agents, 4 * self.num_agents + 1
+        if cache_dwords is None:   # the reset arrays of the shape the kernel is admitted for: the observations
+            cache_dwords = N * F
+        if n_pool is None:
+            pools = self._pools()
+            n_pool = pools[2] if pools else 0
+        up4 = lambda n: (int(n) + 3) // 4 * 4   # noqa: E731
+        dwords = (12 * N * F + 12 * int(cache_dwords) + 256 + up4(int(self.episode_length) + 1) + 2 * up4(N * int(n_pool))
+                  + (2 * gridworld_policy_floats(width) if int(width) else 0))
+        return (4 * dwords + 15) // 16 * 16
+
+    def _pool_rollout_shape(self):
+        """the shape the N5P entries are written for: 5 agents, full observations, coordinates within the 256-entry
+        table, the registered reset arrays exactly the observations (the kernel restores those rows from LDS and the
+        positions from the pools), the pools exactly loc_x / loc_y with equal row counts"""
+        dm = self.cuda_data_manager
+        return (self.num_agents == 5 and bool(self.use_full_observation) and len(self.step_actions) == 5
+                and 1 <= int(self.grid_length) <= self.POOL_MAX_COORD and 1 <= int(self.episode_length) <= 4095
+                and sorted(dm.reset_data_list) == [_OBSERVATIONS] and self._pools() is not None)
+
+    def has_pool_rollout(self, n_actions=5):
+        """HipTagGridWorldRollout_N5P (fixed probabilities) for this shape?"""
+        return bool(1 <= int(n_actions) <= 8 and self._pool_rollout_shape() and self._pool_generator() is not None
+                    and self.pool_rollout_lds_bytes(0) <= self.ROLLOUT_POLICY_MAX_LDS
+                    and self.cuda_function_manager.has_function("HipTagGridWorldRollout_N5P"))
+
+    def has_live_policy_rollout(self, width, n_actions):
+        """HipTagGridWorldRollout_N5P_H<width> for this shape?  5 agents, full observations, 5 actions, width 32 / 64,
+        grid_length <= 255, episode_length <= 4095, reset arrays = {observations}, pools = loc_x / loc_y with equal row
+        counts, the pool generator initialised, the LDS within ROLLOUT_POLICY_MAX_LDS, the entry in the manifest"""
+        return bool(int(width) in self.ROLLOUT_POLICY_WIDTHS and int(n_actions) == 5 and self._pool_rollout_shape()
+                    and self._pool_generator() is not None
+                    and self.pool_rollout_lds_bytes(width) <= self.ROLLOUT_POLICY_MAX_LDS
+                    and self.cuda_function_manager.has_function(f"HipTagGridWorldRollout_N5P_H{int(width)}"))
+
+    def live_policy_evaluate_lds_bytes(self, width):
+        return self.pool_rollout_lds_bytes(width, cache_dwords=0, n_pool=0)
+
+    def has_live_policy_evaluate(self, width, n_actions):
+        return bool(self.has_live_policy_rollout(width, n_actions)
+                    and self.live_policy_evaluate_lds_bytes(width) <= self.ROLLOUT_POLICY_MAX_LDS
+                    and self.cuda_function_manager.has_function(f"HipTagGridWorldEvaluate_N5P_H{int(width)}"))
+
+    def _pool_args(self):
+        dm = self.cuda_data_manager
+        x_pool, y_pool, n_pool = self._pools()
+        return [self._pool_generator(), dm.device_data(x_pool), dm.device_data(y_pool), np.int32(n_pool)]
+
+    def tick_launch(self, sampler, probabilities, resetter, env_range=None, batch=None, policy=None):
+        """The T-tick rollout in ONE launch (`ticks_per_launch` > 1 and `batch`, as `CUDATagGridWorld.tick_launch`):
+        HipTagGridWorldRollout_N5P on `probabilities`, or, with `policy` = ((packed tagger policy, packed runner policy),
+        hidden width) -- a shared policy is the same tensor twice -- HipTagGridWorldRollout_N5P_H<width>.  Arguments: the
+        N5 entry's, then the pool generator's words, the two pools and their row count."""
+        from warp_drive_amd.managers.function_manager import _stream_tag
+        from warp_drive_amd.rollout import UnsupportedRolloutShape
+        import torch
+
+        assert env_range is None, "replica ranges are a TagContinuous experiment"
+        assert len(probabilities) == 1
+        fm, dm = self.cuda_function_manager, self.cuda_data_manager
+        if batch is None or int(self.ticks_per_launch) <= 1:
+            raise UnsupportedRolloutShape("the env with a reset pool has no fused single tick: its one-launch rollout needs "
+                                          "ticks_per_launch > 1 and the batch tensors")
+        if getattr(resetter, "_pool_rng", None) is None or self._pool_generator() is None:
+            raise RuntimeError("the env has a reset pool: call init_reset_pool() before building the rollout")
+        n_actions = int(probabilities[0].shape[-1])
+        if policy is None:
+            width, name = 0, "HipTagGridWorldRollout_N5P"
+            if not self.has_pool_rollout(n_actions):
+                raise UnsupportedRolloutShape("the one-launch rollout with a reset pool exists for 5 agents with full "
+                                              "observations, grid_length <= 255 and the loc_x / loc_y pools only")
+            pol_args = []
+        else:
+            try:
+                (tagger, runner), width = policy
+                width = int(width)
+            except (TypeError, ValueError) as err:
+                raise UnsupportedRolloutShape("policy = ((packed tagger policy, packed runner policy), hidden width), "
+                                              f"not {policy!r}") from err
+            if not self.has_live_policy_rollout(width, n_actions):
+                raise UnsupportedRolloutShape("the live-policy rollout with a reset pool exists for 5 agents with full "
+                                              "observations, 5 actions, grid_length <= 255 and hidden widths 32 / 64 only")
+            n_w = gridworld_policy_floats(width)
+            for t in (tagger, runner):
+                if not (getattr(t, "is_cuda", False) and t.dtype == torch.float32 and t.is_contiguous()
+                        and t.numel() == n_w):
+                    raise UnsupportedRolloutShape(f"a packed policy must be a contiguous float32 CUDA tensor of {n_w} "
+                                                  f"elements (width {width})")
+            name, pol_args = f"HipTagGridWorldRollout_N5P_H{width}", [tagger, runner]
+        fm.initialize_functions([name])
+        _, reset_args, _, _ = resetter.fused_launch(dm, 0, 0)  # builds / refreshes the descriptor table
+        E, N, T = int(dm.meta_info("n_envs")), self.num_agents, int(self.ticks_per_launch)
+        F = 4 * N + 1
+        want = {"obs": ((E, N, F), torch.float32), "actions": ((E, N, 1), torch.int32),
+                "rewards": ((E, N), torch.float32), "done": ((E,), torch.int32)}
+        for key, (shape, dtype) in want.items():
+            t = batch[key]
+            assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.shape[0] >= T and \
+                tuple(t.shape[1:]) == shape, (key, tuple(t.shape), t.dtype)
+        cache_dwords = N * F   # the registered reset arrays are exactly the observations (_pool_rollout_shape)
+        args = self._step_args() + [
+            sampler.rng_state, probabilities[0], np.int32(n_actions), reset_args[0], reset_args[1], _stream_tag("tick"),
+            np.int32(T), batch["obs"], batch["actions"], batch["rewards"], batch["done"], np.int32(cache_dwords),
+            fm.global_address("kIndexToActionArr")] + pol_args + self._pool_args()
+        return fm.get_function(name), args, (64, 1, 1), ((E + 11) // 12, 1), self.pool_rollout_lds_bytes(width)
+
+    def evaluate_launch(self, sampler, policy, use_argmax, outputs, action_trace=None, ticks=None):
+        """`CUDATagGridWorld.evaluate_launch` for this env: HipTagGridWorldEvaluate_N5P_H<width>, the N5 entry's
+        arguments followed by the pool's four (an evaluation never restarts: the kernel leaves the pool alone)."""
+        from warp_drive_amd.managers.function_manager import _stream_tag
+        from warp_drive_amd.rollout import UnsupportedRolloutShape
+        import torch
+
+        fm, dm = self.cuda_function_manager, self.cuda_data_manager
+        try:
+            (tagger, runner), width = policy
+            width = int(width)
+        except (TypeError, ValueError) as err:
+            raise UnsupportedRolloutShape("policy = ((packed tagger policy, packed runner policy), hidden width), "
+                                          f"not {policy!r}") from err
+        if not self.has_live_policy_evaluate(width, len(self.step_actions)):
+            raise UnsupportedRolloutShape("the in-kernel evaluation with a reset pool exists for 5 agents with full "
+                                          "observations, 5 actions, grid_length <= 255 and hidden widths 32 / 64 only")
+        n_w = gridworld_policy_floats(width)
+        for t in (tagger, runner):
+            if not (getattr(t, "is_cuda", False) and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n_w):
+                raise UnsupportedRolloutShape(f"a packed policy must be a contiguous float32 CUDA tensor of {n_w} "
+                                              f"elements (width {width})")
+        E, N = int(dm.meta_info("n_envs")), self.num_agents
+        T = int(self.episode_length if ticks is None else ticks)
+        for key, dtype, n in (("reward_sum", torch.float32, E * N), ("steps", torch.int32, E), ("done", torch.int32, E)):
+            t = outputs[key]
+            assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.numel() >= n, (key, tuple(t.shape), t.dtype)
+        if action_trace is not None:
+            t = action_trace
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and t.shape[0] >= T and \
+                int(np.prod(t.shape[1:])) == E * N, ("action_trace", tuple(t.shape), t.dtype)
+        name = f"HipTagGridWorldEvaluate_N5P_H{width}"
+        fm.initialize_functions([name])
+        args = self._step_args() + [
+            sampler.rng_state, _stream_tag("tick"), np.int32(T), fm.global_address("kIndexToActionArr"), tagger, runner,
+            np.int32(1 if use_argmax else 0), outputs["reward_sum"], outputs["steps"], outputs["done"],
+            np.uint64(0) if action_trace is None else action_trace] + self._pool_args()
+        return fm.get_function(name), args, (64, 1, 1), ((E + 11) // 12, 1), self.live_policy_evaluate_lds_bytes(width)

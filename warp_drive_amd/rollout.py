@@ -124,9 +124,13 @@ class RolloutEngine:
         # an env class that offers tick_launch() fuses sampling, step and reset in its own kernel
         # (restarts from a reset pool draw random members: that stays with the pool reset kernel, unless the env's tick
         # kernel draws them itself -- TICK_POOL_RESET)
+        # ... or its T-tick rollout entries do while its single tick does not (ROLLOUT_POOL_RESET: TagGridWorld with a
+        # reset pool) and this engine is such a rollout: the batch tensors and more than one tick per launch
+        pool_rollout = bool(getattr(env_wrapper.env, "ROLLOUT_POOL_RESET", False) and rollout_batch is not None
+                            and int(getattr(env_wrapper.env, "ticks_per_launch", 1)) > 1)
         self.fused = bool(fused and reset_done and hasattr(env_wrapper.env, "tick_launch")
                           and H == getattr(env_wrapper.env, "TICK_HEADS", 2)
-                          and (not pools or getattr(env_wrapper.env, "TICK_POOL_RESET", False))
+                          and (not pools or getattr(env_wrapper.env, "TICK_POOL_RESET", False) or pool_rollout)
                           and getattr(env_wrapper.env, "can_fuse_tick", lambda: True)())
         # env ticks per launch (> 1 only for envs whose fused kernel loops over ticks, fixed policy)
         self.ticks_per_launch = int(getattr(env_wrapper.env, "ticks_per_launch", 1)) if self.fused else 1

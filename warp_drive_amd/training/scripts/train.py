@@ -25,12 +25,13 @@ from warp_drive_amd.envs.cartpole import CUDAClassicControlCartPoleEnv
 from warp_drive_amd.envs.classic_control import (CUDAClassicControlAcrobotEnv, CUDAClassicControlContinuousMountainCarEnv,
                                                 CUDAClassicControlMountainCarEnv, CUDAClassicControlPendulumEnv)
 from warp_drive_amd.envs.tag_continuous import TagContinuous
-from warp_drive_amd.envs.tag_gridworld import CUDATagGridWorld
+from warp_drive_amd.envs.tag_gridworld import CUDATagGridWorld, CUDATagGridWorldWithResetPool
 from warp_drive_amd.training.trainer import Trainer
 from warp_drive_amd.training.trainer_ddpg import TrainerDDPG
 
 _CONFIGS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "run_configs")
 _ENVS = {"tag_continuous": TagContinuous, "tag_gridworld": CUDATagGridWorld,
+         "tag_gridworld_with_reset_pool": CUDATagGridWorldWithResetPool,
          "single_cartpole": CUDAClassicControlCartPoleEnv, "single_acrobot": CUDAClassicControlAcrobotEnv,
          "single_mountain_car": CUDAClassicControlMountainCarEnv,
          "single_continuous_mountain_car": CUDAClassicControlContinuousMountainCarEnv,

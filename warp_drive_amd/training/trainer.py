@@ -315,7 +315,10 @@ class Trainer:
             raise ValueError(f"trainer.fused_rollout_policy: True, False or \"all\", not {wanted!r}")
         if getattr(env, "ROLLOUT_POLICY_OPT_IN", False) and wanted != "all":
             return
-        if not (bool(wanted) and self.engine.fused and self._rollout_dtype is None
+        # (an env with a reset pool has no fused single tick, so `self.engine` is not fused; its T-tick rollout entries
+        # draw from the pool themselves: ROLLOUT_POOL_RESET)
+        if not (bool(wanted) and (self.engine.fused or getattr(env, "ROLLOUT_POOL_RESET", False))
+                and self._rollout_dtype is None
                 and hasattr(env, "ROLLOUT_POLICY_WIDTHS") and self.batch_len > 1 and len(self.head_sizes) == 1
                 and self.head_sizes[0] <= 8):
             return

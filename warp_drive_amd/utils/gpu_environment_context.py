@@ -14,6 +14,7 @@ class CUDAEnvironmentContext:
         self.cuda_function_manager = None
         self.cuda_step = None
         self.cuda_step_function_feed = None
+        self.cuda_env_resetter = None  # EnvWrapper's HIPEnvironmentReset (the reset pool's generator lives there)
 
     def initialize_step_function_context(self, cuda_data_manager, cuda_function_manager,
                                          cuda_step_function_feed, step_function_name):
