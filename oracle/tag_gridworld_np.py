@@ -140,7 +140,7 @@ class TagGridWorldOracle:
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# The live-policy rollout kernel (csrc/kernels/tag_gridworld_n5.hip, HipTagGridWorldRollout_N5_H32 / _H64) evaluates a
+# The live-policy rollout kernel (csrc/kernels/tag_gridworld_n5_common.h, HipTagGridWorldRollout_N5_H32 / _H64) evaluates a
 # small two-hidden-layer policy per agent and tick.  Float32 restatement of that forward on the PACKED weights
 # (training/policy_kernel.py::pack_gridworld_policy), test infrastructure like cartpole_np.py::policy_probabilities.
 POLICY_IN, POLICY_IN_STRIDE, POLICY_ACTIONS = 21, 24, 5
@@ -149,7 +149,7 @@ POLICY_IN, POLICY_IN_STRIDE, POLICY_ACTIONS = 21, 24, 5
 def policy_probabilities(packed, hidden, obs):
     """obs [R, 21] float32 -> probabilities [R, 5] float32: acc = bias, one fused multiply-add per input in index
     order (emulated in float64: the product of two float32 is exact there), ReLU, softmax with the maximum
-    subtracted, float32 running sum of the exponentials, one division per action -- what gw5_policy_cum computes"""
+    subtracted, float32 running sum of the exponentials, one division per action -- what gw5_policy_probs computes"""
     f32, H = np.float32, int(hidden)
     w = np.asarray(packed, dtype=f32)
     o = 0

@@ -1,6 +1,6 @@
 """Cases, start states and a host replay for the TagGridWorld evaluation kernels HipTagGridWorldEvaluate_N5_H<32|64>
 (one episode of every replica in one launch with the tagger and runner networks inside the kernel, greedy or sampled;
-csrc/kernels/tag_gridworld_n5.hip).  Shared by tests/test_gridworld_evaluate_host.py (every case replayed on the host
+csrc/kernels/tag_gridworld_n5.hip, gw5_evaluate in tag_gridworld_n5_common.h).  Shared by tests/test_gridworld_evaluate_host.py (every case replayed on the host
 alone must reach the coverage it is there for) and tests/test_gpu_gridworld_evaluate.py (the same cases on the device).
 Nothing here touches a GPU.
 

@@ -1,5 +1,5 @@
 """Cases and a numpy model for the TagGridWorld rollout with a reset pool in one launch: HipTagGridWorldRollout_N5P /
-_N5P_H<32|64> and HipTagGridWorldEvaluate_N5P_H<32|64> (csrc/kernels/tag_gridworld_n5_pool.hip).  Shared by
+_N5P_H<32|64> and HipTagGridWorldEvaluate_N5P_H<32|64> (csrc/kernels/tag_gridworld_n5_pool.hip, the pooled variant of tag_gridworld_n5_common.h).  Shared by
 tests/test_gridworld_pool_rollout_host.py (the model against single oracle ticks; every GPU case sized from the model
 alone) and tests/test_gpu_gridworld_pool_rollout.py (the same cases on the device).  Nothing here touches a GPU.
 

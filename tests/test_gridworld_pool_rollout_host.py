@@ -195,6 +195,78 @@ def test_the_env_without_a_pool_answers_as_before():
         assert env.live_policy_lds_bytes(width) == n5_eval_lds(width, 23) + 4 * 12 * (2 * 5 + 105)
 
 
+# dynamic LDS bytes the three separate formulas of the host gave before they became `n5_lds_bytes`, computed with that
+# version of envs/tag_gridworld.py.  Plain env, episode length -> width -> (live_policy_lds_bytes(w), (w, 0), (w, 105),
+# live_policy_evaluate_lds_bytes(w)); "fixed": the shared bytes of the HipTagGridWorldRollout_N5 launch.  Episode lengths
+# 1, 2 and 3 fill the same four-entry time table.
+_SHORT_PLAIN = {0: (10896, 5376, 10416, 5376), 32: (27024, 21504, 26544, 21504), 64: (59536, 54016, 59056, 54016),
+                "fixed": 10832}
+PLAIN_LDS = {
+    1: _SHORT_PLAIN, 2: _SHORT_PLAIN, 3: _SHORT_PLAIN,
+    100: {0: (11296, 5776, 10816, 5776), 32: (27424, 21904, 26944, 21904), 64: (59936, 54416, 59456, 54416), "fixed": 11232},
+    4095: {0: (27264, 21744, 26784, 21744), 32: (43392, 37872, 42912, 37872), 64: (75904, 70384, 75424, 70384),
+           "fixed": 27200},
+}
+# env with a reset pool, (episode length, pool rows) -> width -> (pool_rollout_lds_bytes(w), (w, cache_dwords=0),
+# (w, cache_dwords=115, n_pool=rows), (w, n_pool=0), live_policy_evaluate_lds_bytes(w), the inherited live_policy_lds_bytes(w))
+_SHORT_POOLED = {
+    1: {0: (11184, 6144, 11664, 11120, 6080, 10896), 32: (27376, 22336, 27856, 27312, 22272, 27024),
+        64: (59888, 54848, 60368, 59824, 54784, 59536)},
+    5: {0: (11344, 6304, 11824, 11120, 6080, 10896), 32: (27536, 22496, 28016, 27312, 22272, 27024),
+        64: (60048, 55008, 60528, 59824, 54784, 59536)},
+    7: {0: (11408, 6368, 11888, 11120, 6080, 10896), 32: (27600, 22560, 28080, 27312, 22272, 27024),
+        64: (60112, 55072, 60592, 59824, 54784, 59536)},
+}
+POOLED_LDS = {
+    **{(T, rows): _SHORT_POOLED[rows] for T in (1, 2, 3) for rows in (1, 5, 7)},
+    (100, 1): {0: (11584, 6544, 12064, 11520, 6480, 11296), 32: (27776, 22736, 28256, 27712, 22672, 27424),
+               64: (60288, 55248, 60768, 60224, 55184, 59936)},
+    (100, 5): {0: (11744, 6704, 12224, 11520, 6480, 11296), 32: (27936, 22896, 28416, 27712, 22672, 27424),
+               64: (60448, 55408, 60928, 60224, 55184, 59936)},
+    (100, 7): {0: (11808, 6768, 12288, 11520, 6480, 11296), 32: (28000, 22960, 28480, 27712, 22672, 27424),
+               64: (60512, 55472, 60992, 60224, 55184, 59936)},
+    (4095, 1): {0: (27552, 22512, 28032, 27488, 22448, 27264), 32: (43744, 38704, 44224, 43680, 38640, 43392),
+                64: (76256, 71216, 76736, 76192, 71152, 75904)},
+    (4095, 5): {0: (27712, 22672, 28192, 27488, 22448, 27264), 32: (43904, 38864, 44384, 43680, 38640, 43392),
+                64: (76416, 71376, 76896, 76192, 71152, 75904)},
+    (4095, 7): {0: (27776, 22736, 28256, 27488, 22448, 27264), 32: (43968, 38928, 44448, 43680, 38640, 43392),
+                64: (76480, 71440, 76960, 76192, 71152, 75904)},
+}
+
+
+def test_one_lds_formula_gives_the_bytes_of_the_three_it_replaces():
+    """`n5_lds_bytes` (table entries, cache dwords, pool rows, width, time table rounded up or not) and the four callers
+    that were formulas of their own reproduce the recorded numbers; both 5-agent units include the shared header"""
+    from tests.test_gridworld_shapes_logic import _env, _tick_launch
+    from warp_drive_amd import build as wd_build
+
+    assert sorted(PLAIN_LDS) == [1, 2, 3, 100, 4095]
+    assert sorted(POOLED_LDS) == [(T, rows) for T in (1, 2, 3, 100, 4095) for rows in (1, 5, 7)]
+    for T, want in PLAIN_LDS.items():
+        env = _env(5, True, episode_length=T)
+        for w in (0, 32, 64):
+            assert (env.live_policy_lds_bytes(w), env.live_policy_lds_bytes(w, 0), env.live_policy_lds_bytes(w, 105),
+                    env.live_policy_evaluate_lds_bytes(w)) == want[w], (T, w)
+            assert (env.n5_lds_bytes(64, 115, 0, w), env.n5_lds_bytes(64, 0, 0, w), env.n5_lds_bytes(64, 105, 0, w),
+                    env.n5_lds_bytes(64, 0, 0, w)) == want[w], (T, w)
+        assert _tick_launch(_env(5, True, episode_length=T), 1000, 4)[4] == want["fixed"], T
+        assert env.n5_lds_bytes(64, 115, 0, None, round_time_table=False) == want["fixed"], T
+    for (T, rows), want in POOLED_LDS.items():
+        env = _fake_pool_env(300, {}, episode_length=T, rows=(rows, rows))
+        for w in (0, 32, 64):
+            assert (env.pool_rollout_lds_bytes(w), env.pool_rollout_lds_bytes(w, cache_dwords=0),
+                    env.pool_rollout_lds_bytes(w, cache_dwords=115, n_pool=rows), env.pool_rollout_lds_bytes(w, n_pool=0),
+                    env.live_policy_evaluate_lds_bytes(w), env.live_policy_lds_bytes(w)) == want[w], (T, rows, w)
+            assert env.pool_rollout_lds_bytes(w, n_pool=rows) == env.pool_rollout_lds_bytes(w, 105, rows) == want[w][0]
+            pw = w or None   # the fixed-probability N5P entry has no policies behind its tables
+            assert (env.n5_lds_bytes(256, 105, rows, pw), env.n5_lds_bytes(256, 0, rows, pw),
+                    env.n5_lds_bytes(256, 115, rows, pw), env.n5_lds_bytes(256, 105, 0, pw),
+                    env.n5_lds_bytes(256, 0, 0, pw), env.n5_lds_bytes(64, 115, 0, w)) == want[w], (T, rows, w)
+    header = os.path.join(wd_build.KDIR, "tag_gridworld_n5_common.h")
+    for unit in ("tag_gridworld_n5.hip", "tag_gridworld_n5_pool.hip"):
+        assert header in wd_build.unit_sources(unit) and os.path.exists(header), unit
+
+
 @pytest.mark.parametrize("width", [0, 32, 64])
 def test_tick_launch(width):
     """entry name; the N5 entry's arguments, then (for the live entries) the two policies, then the four pool arguments;

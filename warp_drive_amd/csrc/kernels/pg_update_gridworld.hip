@@ -17,10 +17,10 @@
 //
 // The network FLAT, in the order of the module's parameters (the parameters are views of it: FlatPolicy): W0 [H][21]
 // (unpadded), b0 [H], W1 [H][H], b1 [H], Wp [5][H], bp [5], Wv [H], bv [1].  In LDS the rows of W0 are GW_IN_STRIDE = 24
-// floats apart (tag_gridworld_n5.hip's GW5_IN_STRIDE: every row starts on a 16-byte boundary), the three pad columns
+// floats apart (tag_gridworld_n5_common.h's GW5_IN_STRIDE: every row starts on a 16-byte boundary), the three pad columns
 // zero, and the value head starts on a 16-byte boundary behind eight bias slots.
 //
-// Forward arithmetic is gw5_policy_cum's: acc = bias, then one fmaf per input in index order, fmaxf(acc, 0).  relu'(0) = 0.
+// Forward arithmetic is gw5_policy_probs' (the same header): acc = bias, then one fmaf per input in index order, fmaxf(acc, 0).  relu'(0) = 0.
 // The probabilities are not claimed bit-identical to the rollout's.
 //
 // Stage 3 keeps pg_update.hip's structure: a tile of 128 rows per 128-thread block, activations and deltas staged

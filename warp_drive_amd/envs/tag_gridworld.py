@@ -130,10 +130,44 @@ class TagGridWorld:
 
 
 def gridworld_policy_floats(hidden):
-    """floats of one packed policy of the live-policy rollout kernel (gw5_policy_floats in tag_gridworld_n5.hip):
+    """floats of one packed policy of the live-policy rollout kernel (gw5_policy_floats in tag_gridworld_n5_common.h):
     W0 [H][24], b0 [H], W1 [H][H], b1 [H], Wp [5][H], bp [5], rounded up to whole 16-byte vectors"""
     H = int(hidden)
     return (H * 24 + H + H * H + H + 5 * H + 5 + 3) // 4 * 4
+
+
+def _unpack_policy(policy):
+    """((packed tagger policy, packed runner policy), hidden width) -> tagger, runner, width"""
+    from warp_drive_amd.rollout import UnsupportedRolloutShape
+
+    try:
+        (tagger, runner), width = policy
+        return tagger, runner, int(width)
+    except (TypeError, ValueError) as err:
+        raise UnsupportedRolloutShape("policy = ((packed tagger policy, packed runner policy), hidden width), "
+                                      f"not {policy!r}") from err
+
+
+def _check_packed_policies(tensors, width, error):
+    """every packed policy is a contiguous float32 CUDA tensor of gridworld_policy_floats(width) elements, else `error`"""
+    import torch
+
+    n_w = gridworld_policy_floats(width)
+    for t in tensors:
+        if not (getattr(t, "is_cuda", False) and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n_w):
+            raise error(f"a packed policy must be a contiguous float32 CUDA tensor of {n_w} elements (width {width})")
+
+
+def _check_batch(batch, E, N, F, T):
+    """the env-level batch tensors of a T-tick rollout: at least T rows of the shapes `tick_launch` documents"""
+    import torch
+
+    want = {"obs": ((E, N, F), torch.float32), "actions": ((E, N, 1), torch.int32),
+            "rewards": ((E, N), torch.float32), "done": ((E,), torch.int32)}
+    for key, (shape, dtype) in want.items():
+        t = batch[key]
+        assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.shape[0] >= T and \
+            tuple(t.shape[1:]) == shape, (key, tuple(t.shape), t.dtype)
 
 
 _STEP_ARGS = [
@@ -206,16 +240,26 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
 
     ROLLOUT_POLICY_MAX_LDS = 160 * 1024   # dynamic LDS the live-policy rollout may ask for: a gfx950 workgroup's
 
+    def n5_lds_bytes(self, table_entries, cache_dwords, pool_rows, width, round_time_table=True):
+        """dynamic LDS of a 5-agent entry, the layout of tag_gridworld_n5_common.h in dwords: the image and the restore
+        cache of 12 replicas, `table_entries` coordinate quotients (64, with a reset pool 256), the time table, the two
+        pools of `pool_rows` rows, the two packed policies (width None: an entry without policies); times 4 bytes,
+        rounded up to 16.  Every part is a whole number of 16-byte vectors -- but for the time table of the plain
+        fixed-probability entry, which has nothing behind it (round_time_table=False)."""
+        N, F = self.num_agents, 4 * self.num_agents + 1
+        up4 = lambda n: (int(n) + 3) // 4 * 4   # noqa: E731
+        time_table = int(self.episode_length) + 1
+        dwords = (12 * N * F + 12 * int(cache_dwords) + int(table_entries)
+                  + (up4(time_table) if round_time_table else time_table) + 2 * up4(N * int(pool_rows))
+                  + (0 if width is None else 2 * gridworld_policy_floats(width)))
+        return (4 * dwords + 15) // 16 * 16
+
     def live_policy_lds_bytes(self, width, cache_dwords=None):
-        """dynamic LDS of HipTagGridWorldRollout_N5_H<width> (the layout of gw5_rollout in tag_gridworld_n5.hip): the
-        image and the restore cache of 12 replicas, 64 coordinate quotients, the time table rounded up to 16 bytes,
-        the two packed policies"""
+        """dynamic LDS of HipTagGridWorldRollout_N5_H<width>: the restore cache, 64 coordinate quotients, no pools"""
         N, F = self.num_agents, 4 * self.num_agents + 1
         if cache_dwords is None:   # the reset arrays of the shape the kernel is admitted for: positions + observations
             cache_dwords = 2 * N + N * F
-        lds5 = 4 * (12 * N * F + 12 * cache_dwords + 64 + (int(self.episode_length) + 1 + 3) // 4 * 4
-                    + 2 * gridworld_policy_floats(width))
-        return (lds5 + 15) // 16 * 16
+        return self.n5_lds_bytes(64, cache_dwords, 0, width)
 
     def has_live_policy_rollout(self, width, n_actions):
         """does a rollout kernel exist that evaluates the two policy networks itself (HipTagGridWorldRollout_N5_H<width>)
@@ -230,24 +274,32 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
     # Trainer.evaluate_episodes takes the one-launch evaluation of this env only under
     # `trainer.fused_rollout_policy: "all"`: the shipped configs keep the per-tick path they evaluate on
     EVALUATE_POLICY_OPT_IN = True
+    _EVALUATE_SHAPES = ("the in-kernel evaluation exists for 5 agents with full observations, 5 actions and hidden "
+                        "widths 32 / 64 only")
+
+    def _evaluate_entry(self, width):
+        return f"HipTagGridWorldEvaluate_N5_H{int(width)}"
+
+    def _extra_launch_args(self):
+        """what the 5-agent entries of this env take behind the common arguments"""
+        return []
 
     def live_policy_evaluate_lds_bytes(self, width):
-        """dynamic LDS of HipTagGridWorldEvaluate_N5_H<width> (the layout of gw5_evaluate in tag_gridworld_n5.hip): the
-        rollout's without the restore cache -- the image of 12 replicas, 64 coordinate quotients, the time table
-        rounded up to 16 bytes, the two packed policies"""
-        return self.live_policy_lds_bytes(width, cache_dwords=0)
+        """dynamic LDS of HipTagGridWorldEvaluate_N5_H<width>: the rollout's without the restore cache"""
+        return self.n5_lds_bytes(64, 0, 0, width)
 
     def has_live_policy_evaluate(self, width, n_actions):
         """does an evaluation kernel exist that runs one episode of every replica with the two policy networks inside
-        it (HipTagGridWorldEvaluate_N5_H<width>, Trainer.evaluate_episodes)?  The shapes of the live-policy rollout,
-        with the evaluation's own (smaller) tables within ROLLOUT_POLICY_MAX_LDS and its entry in the manifest."""
+        it (`_evaluate_entry(width)`, Trainer.evaluate_episodes)?  The shapes of the live-policy rollout, with the
+        evaluation's own (smaller) tables within ROLLOUT_POLICY_MAX_LDS and its entry in the manifest."""
         return bool(self.has_live_policy_rollout(width, n_actions)
                     and self.live_policy_evaluate_lds_bytes(width) <= self.ROLLOUT_POLICY_MAX_LDS
-                    and self.cuda_function_manager.has_function(f"HipTagGridWorldEvaluate_N5_H{int(width)}"))
+                    and self.cuda_function_manager.has_function(self._evaluate_entry(width)))
 
     def evaluate_launch(self, sampler, policy, use_argmax, outputs, action_trace=None, ticks=None):
-        """One episode of every replica in ONE launch (HipTagGridWorldEvaluate_N5_H<width>): from the positions,
-        observation rows and time step the arrays hold, at most `ticks` (default: episode_length) ticks of policy
+        """One episode of every replica in ONE launch (HipTagGridWorldEvaluate_N5_H<width>; with a reset pool _N5P_H<width>,
+        which takes the pool's four arguments last and leaves the pool alone: an evaluation never restarts): from the
+        positions, observation rows and time step the arrays hold, at most `ticks` (default: episode_length) ticks of policy
         networks -> action (use_argmax: the first maximum of the probabilities; else the counting draw of the rollout)
         -> step, up to the replica's first done.  policy = ((packed tagger policy, packed runner policy), hidden width)
         as in `tick_launch`.  outputs = {"reward_sum": float32 [E * 5] or [E, 5], "steps": int32 [E], "done": int32
@@ -259,20 +311,10 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
         import torch
 
         fm, dm = self.cuda_function_manager, self.cuda_data_manager
-        try:
-            (tagger, runner), width = policy
-            width = int(width)
-        except (TypeError, ValueError) as err:
-            raise UnsupportedRolloutShape("policy = ((packed tagger policy, packed runner policy), hidden width), "
-                                          f"not {policy!r}") from err
+        tagger, runner, width = _unpack_policy(policy)
         if not self.has_live_policy_evaluate(width, len(self.step_actions)):
-            raise UnsupportedRolloutShape("the in-kernel evaluation exists for 5 agents with full observations, "
-                                          "5 actions and hidden widths 32 / 64 only")
-        n_w = gridworld_policy_floats(width)
-        for t in (tagger, runner):
-            if not (getattr(t, "is_cuda", False) and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n_w):
-                raise UnsupportedRolloutShape(f"a packed policy must be a contiguous float32 CUDA tensor of {n_w} "
-                                              f"elements (width {width})")
+            raise UnsupportedRolloutShape(self._EVALUATE_SHAPES)
+        _check_packed_policies((tagger, runner), width, UnsupportedRolloutShape)
         E, N = int(dm.meta_info("n_envs")), self.num_agents
         T = int(self.episode_length if ticks is None else ticks)
         for key, dtype, n in (("reward_sum", torch.float32, E * N), ("steps", torch.int32, E), ("done", torch.int32, E)):
@@ -282,12 +324,12 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
             t = action_trace
             assert t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and t.shape[0] >= T and \
                 int(np.prod(t.shape[1:])) == E * N, ("action_trace", tuple(t.shape), t.dtype)
-        name = f"HipTagGridWorldEvaluate_N5_H{width}"
+        name = self._evaluate_entry(width)
         fm.initialize_functions([name])
         args = self._step_args() + [
             sampler.rng_state, _stream_tag("tick"), np.int32(T), fm.global_address("kIndexToActionArr"), tagger, runner,
             np.int32(1 if use_argmax else 0), outputs["reward_sum"], outputs["steps"], outputs["done"],
-            np.uint64(0) if action_trace is None else action_trace]
+            np.uint64(0) if action_trace is None else action_trace] + self._extra_launch_args()
         return fm.get_function(name), args, (64, 1, 1), ((E + 11) // 12, 1), self.live_policy_evaluate_lds_bytes(width)
 
     def image_fits(self, epb):
@@ -344,18 +386,11 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
             sampler.rng_state, probabilities[0], np.int32(probabilities[0].shape[-1]), reset_args[0], reset_args[1],
             _stream_tag("tick")]
         if rollout:
-            import torch
-
             E, N, T = int(dm.meta_info("n_envs")), self.num_agents, int(self.ticks_per_launch)
             F = 4 * N + 1 if self.use_full_observation else 6
             assert int(probabilities[0].shape[-1]) <= 8 and self.image_fits(epb) and len(self.step_actions) == 5, \
                 "the rollout kernel needs the LDS observation image and at most 8 actions"
-            want = {"obs": ((E, N, F), torch.float32), "actions": ((E, N, 1), torch.int32),
-                    "rewards": ((E, N), torch.float32), "done": ((E,), torch.int32)}
-            for key, (shape, dtype) in want.items():
-                t = batch[key]
-                assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.shape[0] >= T and \
-                    tuple(t.shape[1:]) == shape, (key, tuple(t.shape), t.dtype)
+            _check_batch(batch, E, N, F, T)
             # the rows finished replicas are restored from are kept in LDS for the whole launch (no loads inside the
             # tick loop): the sum of the registered arrays' row lengths per replica, 0 = no room
             lds = self.lds_bytes(epb)
@@ -372,9 +407,7 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
                 if special is None or not self.has_live_policy_rollout(width, int(probabilities[0].shape[-1])):
                     raise UnsupportedRolloutShape("the live-policy rollout exists for 5 agents with full observations, "
                                                   "5 actions and hidden widths 32 / 64 only")
-                n_w = gridworld_policy_floats(width)
-                for t in (tagger, runner):
-                    assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n_w
+                _check_packed_policies((tagger, runner), width, AssertionError)
                 special = f"{special}_H{width}"
                 fm.initialize_functions([special])
                 # the fixed-policy kernel's LDS with the time table rounded up to 16 bytes, then the two policies
@@ -386,9 +419,8 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
                 # the kernel specialised for this shape (csrc/kernels/tag_gridworld_n5.hip, its own code object):
                 # same arguments + the device address of the action table the host uploads into the main code object
                 fm.initialize_functions([special])
-                lds5 = 4 * (epb * N * F + epb * cache_dwords + 64 + int(self.episode_length) + 1)
                 return (fm.get_function(special), args + [fm.global_address("kIndexToActionArr")], block, grid,
-                        (lds5 + 15) // 16 * 16)
+                        self.n5_lds_bytes(64, cache_dwords, 0, None, round_time_table=False))
             return fm.get_function(name), args, block, grid, lds
         if policy is not None:
             from warp_drive_amd.rollout import UnsupportedRolloutShape
@@ -481,7 +513,7 @@ class CUDATagGridWorldWithResetPool(_DeviceStepMixin, TagGridWorld):
     # env: without the batch tensors RolloutEngine builds sample, step, table reset, two pool launches, undo.
     ROLLOUT_POOL_RESET = True      # RolloutEngine: the T-tick entries restart from the pool inside the kernel
     ROLLOUT_POLICY_OPT_IN = True   # Trainer: the one launch only under `trainer.fused_rollout_policy: "all"`
-    POOL_MAX_COORD = 255           # GW5P_MAX_COORD: the quotient table has 256 entries
+    POOL_MAX_COORD = 255           # Gw5Pooled::MAX_COORD: the quotient table has 256 entries
 
     def _pools(self):
         """(name of the x pool, name of the y pool, rows) when the pools are exactly loc_x's and loc_y's, [rows, 5] each
@@ -500,20 +532,15 @@ class CUDATagGridWorldWithResetPool(_DeviceStepMixin, TagGridWorld):
         return getattr(getattr(self, "cuda_env_resetter", None), "_pool_rng", None)
 
     def pool_rollout_lds_bytes(self, width=0, cache_dwords=None, n_pool=None):
-        """dynamic LDS of the N5P entries (the layout of gw5p_rollout in tag_gridworld_n5_pool.hip): the image and the
-        restore cache of 12 replicas, 256 coordinate quotients, the time table, the two pools and the two packed policies
-        (width 0, the fixed-probability entry: none), every part a whole number of 16-byte vectors.  The evaluation
-        entries have neither cache nor pools (cache_dwords = 0, n_pool = 0)."""
-        N, F = self.num_agents, 4 * self.num_agents + 1
+        """dynamic LDS of the N5P entries: `n5_lds_bytes` with 256 coordinate quotients, the two pools and the two packed
+        policies (width 0, the fixed-probability entry: none).  The evaluation entries have neither cache nor pools
+        (cache_dwords = 0, n_pool = 0)."""
         if cache_dwords is None:   # the reset arrays of the shape the kernel is admitted for: the observations
-            cache_dwords = N * F
+            cache_dwords = self.num_agents * (4 * self.num_agents + 1)
         if n_pool is None:
             pools = self._pools()
             n_pool = pools[2] if pools else 0
-        up4 = lambda n: (int(n) + 3) // 4 * 4   # noqa: E731
-        dwords = (12 * N * F + 12 * int(cache_dwords) + 256 + up4(int(self.episode_length) + 1) + 2 * up4(N * int(n_pool))
-                  + (2 * gridworld_policy_floats(width) if int(width) else 0))
-        return (4 * dwords + 15) // 16 * 16
+        return self.n5_lds_bytes(256, cache_dwords, n_pool, int(width) or None)
 
     def _pool_rollout_shape(self):
         """the shape the N5P entries are written for: 5 agents, full observations, coordinates within the 256-entry
@@ -542,12 +569,14 @@ class CUDATagGridWorldWithResetPool(_DeviceStepMixin, TagGridWorld):
     def live_policy_evaluate_lds_bytes(self, width):
         return self.pool_rollout_lds_bytes(width, cache_dwords=0, n_pool=0)
 
-    def has_live_policy_evaluate(self, width, n_actions):
-        return bool(self.has_live_policy_rollout(width, n_actions)
-                    and self.live_policy_evaluate_lds_bytes(width) <= self.ROLLOUT_POLICY_MAX_LDS
-                    and self.cuda_function_manager.has_function(f"HipTagGridWorldEvaluate_N5P_H{int(width)}"))
+    _EVALUATE_SHAPES = ("the in-kernel evaluation with a reset pool exists for 5 agents with full observations, 5 actions, "
+                        "grid_length <= 255 and hidden widths 32 / 64 only")
 
-    def _pool_args(self):
+    def _evaluate_entry(self, width):
+        return f"HipTagGridWorldEvaluate_N5P_H{int(width)}"
+
+    def _extra_launch_args(self):
+        """the pool generator's words, the two pools and their row count: the last four arguments of every N5P entry"""
         dm = self.cuda_data_manager
         x_pool, y_pool, n_pool = self._pools()
         return [self._pool_generator(), dm.device_data(x_pool), dm.device_data(y_pool), np.int32(n_pool)]
@@ -559,7 +588,6 @@ class CUDATagGridWorldWithResetPool(_DeviceStepMixin, TagGridWorld):
         N5 entry's, then the pool generator's words, the two pools and their row count."""
         from warp_drive_amd.managers.function_manager import _stream_tag
         from warp_drive_amd.rollout import UnsupportedRolloutShape
-        import torch
 
         assert env_range is None, "replica ranges are a TagContinuous experiment"
         assert len(probabilities) == 1
@@ -577,74 +605,20 @@ class CUDATagGridWorldWithResetPool(_DeviceStepMixin, TagGridWorld):
                                               "observations, grid_length <= 255 and the loc_x / loc_y pools only")
             pol_args = []
         else:
-            try:
-                (tagger, runner), width = policy
-                width = int(width)
-            except (TypeError, ValueError) as err:
-                raise UnsupportedRolloutShape("policy = ((packed tagger policy, packed runner policy), hidden width), "
-                                              f"not {policy!r}") from err
+            tagger, runner, width = _unpack_policy(policy)
             if not self.has_live_policy_rollout(width, n_actions):
                 raise UnsupportedRolloutShape("the live-policy rollout with a reset pool exists for 5 agents with full "
                                               "observations, 5 actions, grid_length <= 255 and hidden widths 32 / 64 only")
-            n_w = gridworld_policy_floats(width)
-            for t in (tagger, runner):
-                if not (getattr(t, "is_cuda", False) and t.dtype == torch.float32 and t.is_contiguous()
-                        and t.numel() == n_w):
-                    raise UnsupportedRolloutShape(f"a packed policy must be a contiguous float32 CUDA tensor of {n_w} "
-                                                  f"elements (width {width})")
+            _check_packed_policies((tagger, runner), width, UnsupportedRolloutShape)
             name, pol_args = f"HipTagGridWorldRollout_N5P_H{width}", [tagger, runner]
         fm.initialize_functions([name])
         _, reset_args, _, _ = resetter.fused_launch(dm, 0, 0)  # builds / refreshes the descriptor table
         E, N, T = int(dm.meta_info("n_envs")), self.num_agents, int(self.ticks_per_launch)
         F = 4 * N + 1
-        want = {"obs": ((E, N, F), torch.float32), "actions": ((E, N, 1), torch.int32),
-                "rewards": ((E, N), torch.float32), "done": ((E,), torch.int32)}
-        for key, (shape, dtype) in want.items():
-            t = batch[key]
-            assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.shape[0] >= T and \
-                tuple(t.shape[1:]) == shape, (key, tuple(t.shape), t.dtype)
+        _check_batch(batch, E, N, F, T)
         cache_dwords = N * F   # the registered reset arrays are exactly the observations (_pool_rollout_shape)
         args = self._step_args() + [
             sampler.rng_state, probabilities[0], np.int32(n_actions), reset_args[0], reset_args[1], _stream_tag("tick"),
             np.int32(T), batch["obs"], batch["actions"], batch["rewards"], batch["done"], np.int32(cache_dwords),
-            fm.global_address("kIndexToActionArr")] + pol_args + self._pool_args()
+            fm.global_address("kIndexToActionArr")] + pol_args + self._extra_launch_args()
         return fm.get_function(name), args, (64, 1, 1), ((E + 11) // 12, 1), self.pool_rollout_lds_bytes(width)
-
-    def evaluate_launch(self, sampler, policy, use_argmax, outputs, action_trace=None, ticks=None):
-        """`CUDATagGridWorld.evaluate_launch` for this env: HipTagGridWorldEvaluate_N5P_H<width>, the N5 entry's
-        arguments followed by the pool's four (an evaluation never restarts: the kernel leaves the pool alone)."""
-        from warp_drive_amd.managers.function_manager import _stream_tag
-        from warp_drive_amd.rollout import UnsupportedRolloutShape
-        import torch
-
-        fm, dm = self.cuda_function_manager, self.cuda_data_manager
-        try:
-            (tagger, runner), width = policy
-            width = int(width)
-        except (TypeError, ValueError) as err:
-            raise UnsupportedRolloutShape("policy = ((packed tagger policy, packed runner policy), hidden width), "
-                                          f"not {policy!r}") from err
-        if not self.has_live_policy_evaluate(width, len(self.step_actions)):
-            raise UnsupportedRolloutShape("the in-kernel evaluation with a reset pool exists for 5 agents with full "
-                                          "observations, 5 actions, grid_length <= 255 and hidden widths 32 / 64 only")
-        n_w = gridworld_policy_floats(width)
-        for t in (tagger, runner):
-            if not (getattr(t, "is_cuda", False) and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n_w):
-                raise UnsupportedRolloutShape(f"a packed policy must be a contiguous float32 CUDA tensor of {n_w} "
-                                              f"elements (width {width})")
-        E, N = int(dm.meta_info("n_envs")), self.num_agents
-        T = int(self.episode_length if ticks is None else ticks)
-        for key, dtype, n in (("reward_sum", torch.float32, E * N), ("steps", torch.int32, E), ("done", torch.int32, E)):
-            t = outputs[key]
-            assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.numel() >= n, (key, tuple(t.shape), t.dtype)
-        if action_trace is not None:
-            t = action_trace
-            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and t.shape[0] >= T and \
-                int(np.prod(t.shape[1:])) == E * N, ("action_trace", tuple(t.shape), t.dtype)
-        name = f"HipTagGridWorldEvaluate_N5P_H{width}"
-        fm.initialize_functions([name])
-        args = self._step_args() + [
-            sampler.rng_state, _stream_tag("tick"), np.int32(T), fm.global_address("kIndexToActionArr"), tagger, runner,
-            np.int32(1 if use_argmax else 0), outputs["reward_sum"], outputs["steps"], outputs["done"],
-            np.uint64(0) if action_trace is None else action_trace] + self._pool_args()
-        return fm.get_function(name), args, (64, 1, 1), ((E + 11) // 12, 1), self.live_policy_evaluate_lds_bytes(width)

@@ -21,7 +21,7 @@ from warp_drive_amd.training.pg_update_kernels import (APPLY_THREADS, LD, LDS_LI
 HIDDEN = (32, 64)          # widths the code object has entries for
 OBS = 21                   # observation floats of a TagGridWorld row at 5 agents (full observations)
 ACTIONS = 5
-IN_STRIDE = 24             # floats per row of W0 in LDS and in the packed policy (tag_gridworld_n5.hip: GW5_IN_STRIDE)
+IN_STRIDE = 24             # floats per row of W0 in LDS and in the packed policy (tag_gridworld_n5_common.h: GW5_IN_STRIDE)
 BIAS_SLOTS = 8             # the value head's LDS copy starts behind eight bias slots: a 16-byte boundary
 CODE_OBJECT = "wd_kernels_pg_gw.hsaco"
 

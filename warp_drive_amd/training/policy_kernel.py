@@ -326,7 +326,7 @@ def pack_rollout_actor(model, out=None):
 
 @torch.no_grad()
 def pack_gridworld_policy(model, out=None):
-    """One policy of the live-policy TagGridWorld rollout (csrc/kernels/tag_gridworld_n5.hip::gw5_policy_cum): W0
+    """One policy of the live-policy TagGridWorld rollout (csrc/kernels/tag_gridworld_n5_common.h::gw5_policy_probs): W0
     [H][24] (the 21 inputs of a row padded to 24 floats: every row starts on a 16-byte boundary), b0 [H], W1 [H][H],
     b1 [H], Wp [5][H], bp [5], float32, the block padded to a multiple of four floats.  `out`: refill in place."""
     from warp_drive_amd.envs.tag_gridworld import gridworld_policy_floats
