@@ -61,6 +61,9 @@ UNITS = {
     "wd_kernels_gw5.hsaco": ("tag_gridworld_n5.hip", []),
     # the same rollout for the env with a reset pool: 256 coordinate quotients, the pool row drawn inside the kernel
     "wd_kernels_gw5_pool.hsaco": ("tag_gridworld_n5_pool.hip", []),
+    # Cartpole's T-tick rollout for the env with a reset pool: the pool row drawn inside the kernel (the main object's
+    # Cartpole entries stay as they are: both include cartpole_common.h)
+    "wd_kernels_cp_pool.hsaco": ("cartpole_pool.hip", []),
     # ClassicControl Acrobot, MountainCar, ContinuousMountainCar, Pendulum: step + fused tick of each
     "wd_kernels_cc.hsaco": ("classic_control.hip", []),
     # TrainerDDPG's update (trainer.fused_update): next values, gradients, reduce, clip + Adam + soft update

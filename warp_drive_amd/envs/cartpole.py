@@ -144,9 +144,88 @@ class CUDAClassicControlCartPoleEnv(CUDAEnvironmentContext, ClassicControlCartPo
 
     ROLLOUT_POLICY_WIDTHS = (32, 64)   # HipClassicControlCartPoleEnvRollout_H<width>
 
+    # ------------------------------------------------------------------ with a reset pool (csrc/kernels/cartpole_pool.hip)
+    # HipClassicControlCartPoleEnvRollout_P / _P_H<width> run T ticks per launch and draw the pool row of a finished
+    # replica inside the kernel.  There is no fused SINGLE tick for the pooled env: without the batch tensors
+    # RolloutEngine builds sample, step, table reset, pool launch, undo.
+    @property
+    def ROLLOUT_POOL_RESET(self):
+        """RolloutEngine: the T-tick entries restart from the pool inside the kernel (True with a pool; without one the
+        question does not arise and every answer stays as it was)"""
+        return self._has_pool()
+
+    POOL_ROLLOUT_MAX_LDS = 64 * 1024   # LDS a plain launch may ask for, static + dynamic (two such blocks fit a CU's 160 KB)
+    POOL_ROLLOUT_STATIC_LDS = 256      # the entries' own static LDS (the block's vote on the pool rows' angles)
+    # "auto" stages the pool in LDS when that fits the limit (1000 rows with a [64, 64] policy: 35 KB) and else reads it
+    # from global memory (10 000 rows are 160 KB); "lds" / "global" force one (a forced "lds" beyond the limit is refused)
+    pool_placement = "auto"
+
+    @property
+    def ROLLOUT_POLICY_OPT_IN(self):
+        """Trainer: with a reset pool the one launch only under `trainer.fused_rollout_policy: "all"` (a pooled Cartpole
+        trained today keeps today's per-tick path and its draws); without a pool it is the default, as before"""
+        return self._has_pool()
+
+    def _has_pool(self):
+        dm = getattr(self, "cuda_data_manager", None)
+        if dm is not None and getattr(dm, "reset_target_to_pool", None) is not None:
+            return len(dm.reset_target_to_pool) > 0
+        return self.reset_pool_size >= 2
+
+    @staticmethod
+    def pool_rollout_lds_bytes(width, n_actions, n_pool, staged):
+        """dynamic LDS of the ..._P entries: the packed policy (width 0, the fixed-probability entry: none) rounded up
+        to whole float4, then -- staged -- the pool's rows of 16 bytes"""
+        width, n_actions = int(width), int(n_actions)
+        n_w = 4 * width + width + width * width + width + n_actions * width + n_actions if width else 0
+        return 4 * (-(-n_w // 4) * 4) + (16 * int(n_pool) if staged else 0)
+
+    def _pool_rollout(self, width, n_actions):
+        """(pool array's name, rows, staged) when the pooled rollout of this width (0: fixed probabilities) serves the env as
+        it stands, else the reason it does not (a str)"""
+        dm = self.cuda_data_manager
+        pools = dict(dm.reset_target_to_pool)
+        if sorted(pools) != ["state"]:
+            return f"the pooled rollout restarts `state` from its pool and nothing else, not {sorted(pools)}"
+        shape = tuple(dm.get_shape(pools["state"]))
+        if len(shape) != 3 or shape[0] < 1 or shape[1:] != (1, 4):
+            return f"the pool of `state` must be [n, 1, 4], not {shape}"
+        dtype = getattr(dm, "get_dtype", lambda name: "float32")(pools["state"])
+        if "float32" not in str(dtype):
+            return f"the pool of `state` must be float32, not {dtype}"
+        if sorted(dm.reset_data_list) != [_OBSERVATIONS]:
+            return f"the pooled rollout restores the observations and nothing else, not {sorted(dm.reset_data_list)}"
+        if getattr(getattr(self, "cuda_env_resetter", None), "_pool_rng", None) is None:
+            return "the pool generator is not initialised: call init_reset_pool() before building the rollout"
+        if int(width) not in (0,) + tuple(self.ROLLOUT_POLICY_WIDTHS):
+            return f"no in-kernel policy of width {width}"
+        if not 1 <= int(n_actions) <= 8:
+            return f"the pooled rollout draws 1 .. 8 actions, not {n_actions}"
+        name = self.cuda_step.name.replace("Step", f"Rollout_P_H{int(width)}" if int(width) else "Rollout_P")
+        if not self.cuda_function_manager.has_function(name):
+            return f"{name} is not in the kernel manifest"
+        n_pool = int(shape[0])
+        placement = self.pool_placement
+        if placement not in ("auto", "lds", "global"):
+            return f"pool_placement: \"auto\", \"lds\" or \"global\", not {placement!r}"
+        staged_bytes = self.pool_rollout_lds_bytes(width, n_actions, n_pool, True) + self.POOL_ROLLOUT_STATIC_LDS
+        staged = placement == "lds" or (placement == "auto" and staged_bytes <= self.POOL_ROLLOUT_MAX_LDS)
+        need = self.pool_rollout_lds_bytes(width, n_actions, n_pool, staged) + self.POOL_ROLLOUT_STATIC_LDS
+        if need > self.POOL_ROLLOUT_MAX_LDS:
+            return f"{need} bytes of LDS for a pool of {n_pool} rows exceed the workgroup's {self.POOL_ROLLOUT_MAX_LDS}"
+        return pools["state"], n_pool, staged
+
+    def has_pool_rollout(self, n_actions=2):
+        """with a reset pool: does HipClassicControlCartPoleEnvRollout_P (fixed probabilities) serve this env?"""
+        return bool(self._has_pool() and not isinstance(self._pool_rollout(0, n_actions), str))
+
     def has_live_policy_rollout(self, width, n_actions):
-        """does a rollout kernel exist that evaluates the policy network itself (…Rollout_H<width>)?  (RolloutEngine asks
-        before it calls `tick_launch(policy=...)`)"""
+        """does a rollout kernel exist that evaluates the policy network itself (…Rollout_H<width>; with a reset pool
+        …Rollout_P_H<width>, which serves pools == {state: [n, 1, 4] float32}, reset arrays == {observations}, an
+        initialised pool generator, and a staging whose LDS fits)?  (RolloutEngine asks before it calls
+        `tick_launch(policy=...)`)"""
+        if self._has_pool():
+            return bool(int(width) in self.ROLLOUT_POLICY_WIDTHS and not isinstance(self._pool_rollout(width, n_actions), str))
         name = self.cuda_step.name.replace("Step", f"Rollout_H{int(width)}")
         return int(width) in self.ROLLOUT_POLICY_WIDTHS and int(n_actions) <= 8 and self.cuda_function_manager.has_function(name)
 
@@ -210,11 +289,13 @@ class CUDAClassicControlCartPoleEnv(CUDAEnvironmentContext, ClassicControlCartPo
         their row k (what trainer_base.py:392-426 records per tick).  `policy` (optional) = (packed float32
         CUDA tensor from training.policy_kernel.pack_rollout_policy, hidden width): the launch evaluates the
         policy network on every tick's observation itself (HipClassicControlCartPoleEnvRollout_H<width>)
-        instead of reading `probabilities`."""
+        instead of reading `probabilities`.  An env with a reset pool: `_pool_tick_launch` (the ..._P entries)."""
         from warp_drive_amd.managers.function_manager import _stream_tag
 
         assert env_range is None and len(probabilities) == 1
         fm, dm = self.cuda_function_manager, self.cuda_data_manager
+        if self._has_pool():
+            return self._pool_tick_launch(sampler, probabilities, resetter, batch, policy)
         name = self.cuda_step.name.replace("Step", "Tick")
         shared, pol_args = 0, [np.uint64(0), np.int32(0)]
         if policy is not None:
@@ -231,24 +312,74 @@ class CUDAClassicControlCartPoleEnv(CUDAEnvironmentContext, ClassicControlCartPo
         fm.initialize_functions([name])
         _, reset_args, _, _ = resetter.fused_launch(dm, 0, 0)  # builds / refreshes the descriptor table
         _, args, block, grid, _ = self.step_launch()
-        null = np.uint64(0)
-        if batch is not None:
-            import torch
-
-            E, T = int(dm.meta_info("n_envs")), int(self.ticks_per_launch)
-            want = {"obs": ((E, 1, 4), torch.float32), "actions": ((E, 1, 1), torch.int32),
-                    "rewards": ((E, 1), torch.float32), "done": ((E,), torch.int32)}
-            for key, (shape, dtype) in want.items():
-                t = batch[key]
-                assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.shape[0] >= T and \
-                    tuple(t.shape[1:]) == shape, (key, tuple(t.shape), t.dtype)
-            batch_args = [batch["obs"], batch["actions"], batch["rewards"], batch["done"]]
-        else:
-            batch_args = [null, null, null, null]
         args = list(args) + [sampler.rng_state, probabilities[0], np.int32(probabilities[0].shape[-1]), reset_args[0],
-                             reset_args[1], _stream_tag("tick"), np.int32(self.ticks_per_launch)] + batch_args + pol_args + \
-            [np.int32(self.invariant_divide_ok())]
+                             reset_args[1], _stream_tag("tick"), np.int32(self.ticks_per_launch)] + \
+            self._batch_arguments(batch) + pol_args + [np.int32(self.invariant_divide_ok())]
         return fm.get_function(name), args, block, grid, shared
+
+    def _batch_arguments(self, batch):
+        """the four `*_batch` arguments of a tick / rollout entry (nulls without batch tensors), their shapes checked"""
+        null = np.uint64(0)
+        if batch is None:
+            return [null, null, null, null]
+        import torch
+
+        E, T = int(self.cuda_data_manager.meta_info("n_envs")), int(self.ticks_per_launch)
+        want = {"obs": ((E, 1, 4), torch.float32), "actions": ((E, 1, 1), torch.int32),
+                "rewards": ((E, 1), torch.float32), "done": ((E,), torch.int32)}
+        for key, (shape, dtype) in want.items():
+            t = batch[key]
+            assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.shape[0] >= T and \
+                tuple(t.shape[1:]) == shape, (key, tuple(t.shape), t.dtype)
+        return [batch["obs"], batch["actions"], batch["rewards"], batch["done"]]
+
+    def _pool_tick_launch(self, sampler, probabilities, resetter, batch, policy):
+        """`tick_launch` for the env with a reset pool: HipClassicControlCartPoleEnvRollout_P (fixed probabilities) or
+        ..._P_H<width> (`policy`), T = ticks_per_launch > 1 ticks with the batch tensors.  Arguments: the unpooled
+        entry's, then the pool generator's words, the pool, its row count and 1 / 0 = the kernel stages the pool in LDS /
+        reads it from global memory (`pool_placement`).  Whatever the entries do not serve raises
+        UnsupportedRolloutShape with the reason."""
+        from warp_drive_amd.managers.function_manager import _stream_tag
+        from warp_drive_amd.rollout import UnsupportedRolloutShape
+
+        fm, dm = self.cuda_function_manager, self.cuda_data_manager
+        if batch is None or int(self.ticks_per_launch) < 2:
+            raise UnsupportedRolloutShape("Cartpole with a reset pool has no fused single tick: its one-launch rollout "
+                                          "needs the batch tensors and ticks_per_launch > 1")
+        n_act = int(probabilities[0].shape[-1])
+        width, packed = 0, None
+        if policy is not None:
+            try:
+                packed, width = policy
+                width = int(width)
+            except (TypeError, ValueError) as err:
+                raise UnsupportedRolloutShape(f"policy = (packed weights, hidden width), not {policy!r}") from err
+            if width not in self.ROLLOUT_POLICY_WIDTHS:
+                raise UnsupportedRolloutShape(f"no in-kernel policy of width {width} with {n_act} actions")
+        shape = self._pool_rollout(width, n_act)
+        if isinstance(shape, str):
+            raise UnsupportedRolloutShape(shape)
+        pool_name, n_pool, staged = shape
+        if getattr(resetter, "_pool_rng", None) is None:
+            raise UnsupportedRolloutShape("the pool generator is not initialised: call init_reset_pool() before "
+                                          "building the rollout")
+        pol_args = [np.uint64(0), np.int32(0)]
+        if policy is not None:
+            n_w = 4 * width + width + width * width + width + n_act * width + n_act
+            if not (getattr(packed, "is_cuda", False) and packed.dtype.is_floating_point and packed.is_contiguous()
+                    and packed.numel() == n_w):
+                raise UnsupportedRolloutShape(f"the packed policy must be a contiguous float32 CUDA tensor of {n_w} "
+                                              f"elements (width {width}, {n_act} actions)")
+            pol_args = [packed, np.int32(width)]
+        name = self.cuda_step.name.replace("Step", f"Rollout_P_H{width}" if width else "Rollout_P")
+        fm.initialize_functions([name])
+        _, reset_args, _, _ = resetter.fused_launch(dm, 0, 0)  # builds / refreshes the descriptor table
+        _, args, block, grid, _ = self.step_launch()
+        args = list(args) + [sampler.rng_state, probabilities[0], np.int32(n_act), reset_args[0], reset_args[1],
+                             _stream_tag("tick"), np.int32(self.ticks_per_launch)] + self._batch_arguments(batch) + \
+            pol_args + [np.int32(self.invariant_divide_ok()), resetter._pool_rng, dm.device_data(pool_name),
+                        np.int32(n_pool), np.int32(1 if staged else 0)]
+        return fm.get_function(name), args, block, grid, self.pool_rollout_lds_bytes(width, n_act, n_pool, staged)
 
     def invariant_divide_ok(self):
         """1 when the device PROVED, exhaustively, that the tick kernels' three-instruction division by this env's total mass

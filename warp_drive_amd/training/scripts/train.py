@@ -32,7 +32,8 @@ from warp_drive_amd.training.trainer_ddpg import TrainerDDPG
 _CONFIGS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "run_configs")
 _ENVS = {"tag_continuous": TagContinuous, "tag_gridworld": CUDATagGridWorld,
          "tag_gridworld_with_reset_pool": CUDATagGridWorldWithResetPool,
-         "single_cartpole": CUDAClassicControlCartPoleEnv, "single_acrobot": CUDAClassicControlAcrobotEnv,
+         "single_cartpole": CUDAClassicControlCartPoleEnv,
+         "single_cartpole_with_reset_pool": CUDAClassicControlCartPoleEnv, "single_acrobot": CUDAClassicControlAcrobotEnv,
          "single_mountain_car": CUDAClassicControlMountainCarEnv,
          "single_continuous_mountain_car": CUDAClassicControlContinuousMountainCarEnv,
          "single_pendulum": CUDAClassicControlPendulumEnv}

@@ -302,7 +302,8 @@ class Trainer:
         # csrc/kernels/cartpole.hip; TagGridWorld with 5 agents and full observations: tag_gridworld_n5.hip -- two hidden
         # layers of 32 / 64 units, one head) run all `batch_len` ticks of a training batch -- policy forward, sampling,
         # step, reset, recording of the batch rows -- in a single launch.  `trainer.fused_rollout_policy: False` keeps
-        # the per-tick path.  Envs that say ROLLOUT_POLICY_OPT_IN (Acrobot, MountainCar: envs/classic_control.py) take
+        # the per-tick path.  Envs that say ROLLOUT_POLICY_OPT_IN (Acrobot, MountainCar: envs/classic_control.py;
+        # TagGridWorld and Cartpole WITH A RESET POOL: their ..._N5P / ..._P entries draw the pool row themselves) take
         # the single launch only with `trainer.fused_rollout_policy: "all"`.
         self._batch_rollout = None
         self._setup_batch_rollout(env_wrapper, tcfg)
