@@ -44,6 +44,22 @@ def test_the_new_entries_are_in_a_code_object_of_their_own(built):
     assert not set(names) & set(pguk.all_kernel_names())
 
 
+def test_the_update_units_and_the_two_classes_share_one_source():
+    from warp_drive_amd import build as wd_build
+
+    header = os.path.join(wd_build.KDIR, "pg_update_common.h")
+    for unit in ("pg_update.hip", "pg_update_gridworld.hip", "ddpg_update.hip"):
+        assert header in wd_build.unit_sources(unit), unit
+    base = pguk._PgUpdateLaunches
+    for cls in (pguk.PgUpdateKernels, pggk.PgGridworldUpdateKernels):
+        assert issubclass(cls, base)
+        for method in ("compute_values", "discounted_returns", "gradients", "reduce", "apply", "gradient_norm", "metrics",
+                       "_check_batch"):
+            assert method not in vars(cls) and getattr(cls, method) is getattr(base, method), (cls.__name__, method)
+        own = {name for name in vars(cls) if name == "__init__" or not name.startswith("__")}
+        assert own == {"__init__", "_shape_args"}, own
+
+
 def test_entries_have_no_scratch_and_no_spilled_registers(built):
     from warp_drive_amd import build as wd_build
 

@@ -12,32 +12,24 @@
 //   4. HipDdpgApply                clip_grad_norm_ per network, torch.optim.Adam's default expression, the soft update of
 //                                  both targets, and the refill of the packed actor the rollout kernels read.
 //
-// No float atomics, no cross-block communication inside a launch, nothing read back by the host.
+// The summation order, relu'(0) = 0, "no float atomics, nothing read back" and the clip and Adam expressions are the parity
+// contract pg_update_common.h states, with the pieces this unit shares with pg_update.hip and pg_update_gridworld.hip.
 //
 // One network = two hidden layers of H ReLU units on I inputs and one linear output, all float32, FLAT in the order of
 // the module's parameters: W0 [H][I], b0 [H], W1 [H][H], b1 [H], Wo [H], bo [1] (ddpg_net_floats(H, I) floats).  The actor
 // has I = O (the observation), output mean = fmaf(action_scale, tanhf(z), action_bias); the critic has I = O + 1 (the
 // observation, then the action).  The buffers of the launches hold the actor, then the critic: PA + PC floats.
 //
-// Forward arithmetic is csrc/kernels/classic_control.hip::cc_actor_mean's: acc = bias, then one fmaf per input in index
-// order, the weights in LDS read as broadcasts, one row per lane.  relu'(0) = 0.
-//
-// Stage 2, per block and per tile of DDPG_TILE rows (grid-stride over the tiles): every lane runs the forward and backward
-// passes of its row and stages what the parameter gradients need -- activations, deltas -- in LDS, unit-major ([unit][row],
-// so a lane's stores are conflict-free); then every thread adds the tile's rows, in row order, to the FIXED set of
-// gradient entries it owns for the whole launch.  A block therefore accumulates every entry in one fixed order (tiles
-// ascending, rows ascending) and writes its partial once; blocks without rows write zeros.  No H-wide array is live in
-// registers across an accumulation: the deltas the next layer needs are read back from the lane's own staged column.
+// Forward arithmetic is csrc/kernels/classic_control.hip::cc_actor_mean's.  In stage 2 no H-wide array is live in registers
+// across an accumulation: the deltas the next layer needs are read back from the lane's own staged column.
 //
 // Restated in float64 in tests/ddpg_update_cases.py.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "pg_update_common.h"
 
 #define DDPG_TILE 128                 // rows per tile = threads per block of HipDdpgGradients
-#define DDPG_LD (DDPG_TILE + 4)       // staged arrays are [unit][DDPG_LD]: rows of 16-byte multiples, units 4 banks apart
+#define DDPG_LD (DDPG_TILE + 4)       // staged arrays are [unit][DDPG_LD]
 
 constexpr int ddpg_net_floats(int H, int I) { return H * I + H + H * H + H + H + 1; }
-constexpr int ddpg_pad4(int n) { return (n + 3) & ~3; }
 
 template <int H, int I>
 struct DdpgNet {
@@ -93,15 +85,7 @@ __device__ __forceinline__ float ddpg_head(const float *w, const float (&h2)[H])
   return z;
 }
 
-template <int H>
-__device__ __forceinline__ uint64_t ddpg_positive_mask(const float (&h)[H]) {
-  uint64_t m = 0;
-#pragma unroll
-  for (int i = 0; i < H; ++i) m |= (h[i] > 0.0f) ? (1ull << i) : 0ull;
-  return m;
-}
-
-// d1[j] = relu'(h1[j]) * sum_i W1[i][j] d2[i], i ascending from +0
+// d1[j] = relu'(h1[j]) * sum_i W1[i][j] d2[i], i ascending from +0.  (Not the header's: d2 is an array in registers here.)
 template <int H, int I>
 __device__ __forceinline__ void ddpg_layer1_backward(const float *w, const float (&d2)[H], uint64_t mask1, float (&d1)[H]) {
   using L = DdpgNet<H, I>;
@@ -128,7 +112,7 @@ __device__ __forceinline__ void ddpg_targets_impl(const float *__restrict__ obs,
                                                   float action_scale, float action_bias, float *__restrict__ next_values) {
   constexpr int I = O + 1, PA = ddpg_net_floats(H, O), PC = ddpg_net_floats(H, I);
   extern __shared__ __attribute__((aligned(16))) float ddpg_lds[];
-  float *wa = ddpg_lds, *wc = ddpg_lds + ddpg_pad4(PA);
+  float *wa = ddpg_lds, *wc = ddpg_lds + upd_pad4(PA);
   ddpg_copy_to_lds(wa, target, PA);
   ddpg_copy_to_lds(wc, target + PA, PC);
   __syncthreads();
@@ -156,16 +140,12 @@ __device__ __forceinline__ void ddpg_targets_impl(const float *__restrict__ obs,
 }
 
 // ---------------------------------------------------------------------------------------------------- 2. gradients
-// What a thread owns of one network's gradient for the whole launch (128 threads):
-//   dW1 [H][H]: rows i = ib + NIB a (a < 4), columns j = jb + NJB b (b < JB), ib = tid % NIB, jb = tid / NIB
-//   dW0 [H][I]: row i = tid % H, columns k = KB (tid / H) + c (c < KB, k < I)
-//   db0, db1, dWo: unit i = tid (tid < H);  dbo and the loss sum: thread 0
+// What a thread owns of one network's gradient for the whole launch (128 threads): UpdOwn's share of dW0, db0, dW1, db1, and
+//   dWo: unit i = tid (tid < H);  dbo and the loss sum: thread 0
 template <int H>
-struct DdpgOwn {
-  static constexpr int NIB = H / 4, NJB = DDPG_TILE / NIB, JB = H / NJB, KG = DDPG_TILE / H;
-  static_assert(NIB * NJB == DDPG_TILE && NJB * JB == H && KG * H == DDPG_TILE, "ownership covers the matrix exactly");
-};
+using DdpgOwn = UpdOwn<H, DDPG_TILE>;
 
+// (not UpdAcc: one head unit per thread and no sum)
 template <int H, int I>
 struct DdpgAcc {
   static constexpr int JB = DdpgOwn<H>::JB, KB = (I + DdpgOwn<H>::KG - 1) / DdpgOwn<H>::KG;
@@ -196,61 +176,6 @@ __device__ __forceinline__ void ddpg_acc_head(DdpgAcc<H, I> &g, float &loss, con
   }
 }
 
-// dW1[i][j] += sum_r d2[i][r] * h1[j][r]; db1[i] += sum_r d2[i][r]
-template <int H, int I>
-__device__ __forceinline__ void ddpg_acc_w1(DdpgAcc<H, I> &g, const float *S0, const float *S1) {
-  using W = DdpgOwn<H>;
-  constexpr int JB = W::JB;
-  const int tid = threadIdx.x, ib = tid % W::NIB, jb = tid / W::NIB;
-  for (int r = 0; r < DDPG_TILE; r += 4) {
-    float4 d[4], h[JB];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) d[a] = *(const float4 *)(S1 + (ib + W::NIB * a) * DDPG_LD + r);
-#pragma unroll
-    for (int b = 0; b < JB; ++b) h[b] = *(const float4 *)(S0 + (jb + W::NJB * b) * DDPG_LD + r);
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < JB; ++b) {
-        float acc = g.w1[a][b];
-        acc = fmaf(d[a].x, h[b].x, acc); acc = fmaf(d[a].y, h[b].y, acc);
-        acc = fmaf(d[a].z, h[b].z, acc); acc = fmaf(d[a].w, h[b].w, acc);
-        g.w1[a][b] = acc;
-      }
-  }
-  if (tid < H) {
-    for (int r = 0; r < DDPG_TILE; r += 4) {
-      const float4 d = *(const float4 *)(S1 + tid * DDPG_LD + r);
-      g.b1 += d.x; g.b1 += d.y; g.b1 += d.z; g.b1 += d.w;
-    }
-  }
-}
-
-// dW0[i][k] += sum_r d1[i][r] * x[k][r]; db0[i] += sum_r d1[i][r]   (x staged as [4][DDPG_LD])
-template <int H, int I>
-__device__ __forceinline__ void ddpg_acc_w0(DdpgAcc<H, I> &g, const float *S1, const float *S2) {
-  constexpr int KB = DdpgAcc<H, I>::KB;
-  const int tid = threadIdx.x, i = tid % H, k0 = KB * (tid / H);
-  for (int r = 0; r < DDPG_TILE; r += 4) {
-    const float4 d = *(const float4 *)(S1 + i * DDPG_LD + r);
-#pragma unroll
-    for (int c = 0; c < KB; ++c) {
-      if (k0 + c < I) {
-        const float4 x = *(const float4 *)(S2 + (k0 + c) * DDPG_LD + r);
-        float acc = g.w0[c];
-        acc = fmaf(d.x, x.x, acc); acc = fmaf(d.y, x.y, acc); acc = fmaf(d.z, x.z, acc); acc = fmaf(d.w, x.w, acc);
-        g.w0[c] = acc;
-      }
-    }
-  }
-  if (tid < H) {
-    for (int r = 0; r < DDPG_TILE; r += 4) {
-      const float4 d = *(const float4 *)(S1 + tid * DDPG_LD + r);
-      g.b0 += d.x; g.b0 += d.y; g.b0 += d.z; g.b0 += d.w;
-    }
-  }
-}
-
 template <int H, int I>
 __device__ __forceinline__ void ddpg_write_partial(const DdpgAcc<H, I> &g, float *out) {
   using L = DdpgNet<H, I>;
@@ -273,17 +198,11 @@ __device__ __forceinline__ void ddpg_write_partial(const DdpgAcc<H, I> &g, float
   if (tid == 0) out[L::BO] = g.bo;
 }
 
-template <int H>
-__device__ __forceinline__ void ddpg_stage(float *S, int row, const float (&h)[H]) {
-#pragma unroll
-  for (int i = 0; i < H; ++i) S[i * DDPG_LD + row] = h[i];
-}
-
 // obs [T, E, O], actions / rewards / next_values as [T (- 1), E] floats, done [T, E] int32; theta = actor, then critic;
 // returns_out [V, E]; partials [gridDim.x][PA + PC + 2]: the block's gradient of the actor, of the critic, then its sums of
 // (returns - Q)^2 and of Q(obs, mu(obs)).  Dynamic LDS: ddpg_gradients_lds_floats(H, O) floats.  blockDim.x = DDPG_TILE.
 constexpr int ddpg_gradients_lds_floats(int H, int O) {
-  return ddpg_pad4(ddpg_net_floats(H, O)) + ddpg_pad4(ddpg_net_floats(H, O + 1)) + 2 * H * DDPG_LD + 4 * DDPG_LD + 2 * DDPG_TILE;
+  return upd_pad4(ddpg_net_floats(H, O)) + upd_pad4(ddpg_net_floats(H, O + 1)) + 2 * H * DDPG_LD + 4 * DDPG_LD + 2 * DDPG_TILE;
 }
 
 template <int H, int O>
@@ -297,7 +216,7 @@ __device__ __forceinline__ void ddpg_gradients_impl(const float *__restrict__ ob
   using LA = DdpgNet<H, O>;
   using LC = DdpgNet<H, I>;
   extern __shared__ __attribute__((aligned(16))) float ddpg_lds[];
-  float *wa = ddpg_lds, *wc = wa + ddpg_pad4(PA), *S0 = wc + ddpg_pad4(PC), *S1 = S0 + H * DDPG_LD, *S2 = S1 + H * DDPG_LD;
+  float *wa = ddpg_lds, *wc = wa + upd_pad4(PA), *S0 = wc + upd_pad4(PC), *S1 = S0 + H * DDPG_LD, *S2 = S1 + H * DDPG_LD;
   float *S3 = S2 + 4 * DDPG_LD, *S4 = S3 + DDPG_TILE;
   ddpg_copy_to_lds(wa, theta, PA);
   ddpg_copy_to_lds(wc, theta + PA, PC);
@@ -348,12 +267,12 @@ __device__ __forceinline__ void ddpg_gradients_impl(const float *__restrict__ ob
       ddpg_layer0<H, I>(wc, x, c1);
       ddpg_layer1<H, I>(wc, c1, c2);
       const float q = ddpg_head<H, I>(wc, c2);
-      m1 = ddpg_positive_mask<H>(c1);
-      m2 = ddpg_positive_mask<H>(c2);
+      m1 = upd_positive_mask<H>(c1);
+      m2 = upd_positive_mask<H>(c2);
       const float diff = live ? q - ret : 0.0f;
       dq = (2.0f * diff) * inv_rows;
-      ddpg_stage<H>(S0, tid, c1);
-      ddpg_stage<H>(S1, tid, c2);
+      upd_stage<H, DDPG_LD>(S0, tid, c1);
+      upd_stage<H, DDPG_LD>(S1, tid, c2);
       S3[tid] = dq;
       S4[tid] = diff * diff;
     }
@@ -364,22 +283,22 @@ __device__ __forceinline__ void ddpg_gradients_impl(const float *__restrict__ ob
       float d2[H];
 #pragma unroll
       for (int i = 0; i < H; ++i) d2[i] = ((m2 >> i) & 1ull) ? dq * wc[LC::WO + i] : 0.0f;
-      ddpg_stage<H>(S1, tid, d2);
+      upd_stage<H, DDPG_LD>(S1, tid, d2);
     }
     __syncthreads();
-    ddpg_acc_w1<H, I>(gc, S0, S1);
+    upd_acc_w1<H, DDPG_TILE, DDPG_LD>(gc, S0, S1);
     {
       float d2[H], d1[H];
 #pragma unroll
       for (int i = 0; i < H; ++i) d2[i] = S1[i * DDPG_LD + tid];
       ddpg_layer1_backward<H, I>(wc, d2, m1, d1);
       __syncthreads();
-      ddpg_stage<H>(S1, tid, d1);
+      upd_stage<H, DDPG_LD>(S1, tid, d1);
 #pragma unroll
       for (int k = 0; k < I; ++k) S2[k * DDPG_LD + tid] = x[k];
     }
     __syncthreads();
-    ddpg_acc_w0<H, I>(gc, S1, S2);
+    upd_acc_w0<H, DDPG_TILE, DDPG_LD, I>(gc, S1, S2);
     __syncthreads();
 
     // ========================================= actor loss: -mean(Q(obs, mu(obs))), differentiated through the action only
@@ -393,10 +312,10 @@ __device__ __forceinline__ void ddpg_gradients_impl(const float *__restrict__ ob
         ddpg_layer0<H, O>(wa, xa, a1);
         ddpg_layer1<H, O>(wa, a1, a2);
         th = tanhf(ddpg_head<H, O>(wa, a2));
-        m1 = ddpg_positive_mask<H>(a1);
-        m2 = ddpg_positive_mask<H>(a2);
-        ddpg_stage<H>(S0, tid, a1);
-        ddpg_stage<H>(S1, tid, a2);
+        m1 = upd_positive_mask<H>(a1);
+        m2 = upd_positive_mask<H>(a2);
+        upd_stage<H, DDPG_LD>(S0, tid, a1);
+        upd_stage<H, DDPG_LD>(S1, tid, a2);
       }
       x[O] = fmaf(action_scale, th, action_bias);
       float dmu = 0.0f;
@@ -405,7 +324,7 @@ __device__ __forceinline__ void ddpg_gradients_impl(const float *__restrict__ ob
         ddpg_layer0<H, I>(wc, x, j1);
         ddpg_layer1<H, I>(wc, j1, j2);
         S4[tid] = live ? ddpg_head<H, I>(wc, j2) : 0.0f;
-        const uint64_t mj1 = ddpg_positive_mask<H>(j1), mj2 = ddpg_positive_mask<H>(j2);
+        const uint64_t mj1 = upd_positive_mask<H>(j1), mj2 = upd_positive_mask<H>(j2);
         const float dj = live ? -inv_rows : 0.0f;
 #pragma unroll
         for (int i = 0; i < H; ++i) j2[i] = ((mj2 >> i) & 1ull) ? dj * wc[LC::WO + i] : 0.0f;
@@ -423,20 +342,20 @@ __device__ __forceinline__ void ddpg_gradients_impl(const float *__restrict__ ob
       float f2[H];
 #pragma unroll
       for (int i = 0; i < H; ++i) f2[i] = ((m2 >> i) & 1ull) ? dz * wa[LA::WO + i] : 0.0f;
-      ddpg_stage<H>(S1, tid, f2);
+      upd_stage<H, DDPG_LD>(S1, tid, f2);
     }
     __syncthreads();
-    ddpg_acc_w1<H, O>(ga, S0, S1);
+    upd_acc_w1<H, DDPG_TILE, DDPG_LD>(ga, S0, S1);
     {
       float f2[H], f1[H];
 #pragma unroll
       for (int i = 0; i < H; ++i) f2[i] = S1[i * DDPG_LD + tid];
       ddpg_layer1_backward<H, O>(wa, f2, m1, f1);
       __syncthreads();
-      ddpg_stage<H>(S1, tid, f1);
+      upd_stage<H, DDPG_LD>(S1, tid, f1);
     }
     __syncthreads();
-    ddpg_acc_w0<H, O>(ga, S1, S2);   // (S2 still holds the tile's observations)
+    upd_acc_w0<H, DDPG_TILE, DDPG_LD, O>(ga, S1, S2);   // (S2 still holds the tile's observations)
     __syncthreads();
   }
   float *out = partials + (long)blockIdx.x * (PA + PC + 2);
@@ -450,9 +369,7 @@ __device__ __forceinline__ void ddpg_gradients_impl(const float *__restrict__ ob
 
 // -------------------------------------------------------------------------------------------------- 3 and 4: layout
 // the twelve parameter tensors of (actor, critic) inside the flat PA + PC floats
-struct DdpgTensor { int off, n; };
-
-__device__ __forceinline__ DdpgTensor ddpg_tensor(int k, int H, int O) {
+__device__ __forceinline__ UpdTensor ddpg_tensor(int k, int H, int O) {
   const int PA = ddpg_net_floats(H, O);
   const int I = k < 6 ? O : O + 1, base = k < 6 ? 0 : PA, j = k < 6 ? k : k - 6;
   const int o1 = H * I, o2 = o1 + H, o3 = o2 + H * H, o4 = o3 + H, o5 = o4 + H, o6 = o5 + 1;
@@ -484,10 +401,9 @@ DDPG_ENTRIES(32, 3)
 DDPG_ENTRIES(64, 2)
 DDPG_ENTRIES(64, 3)
 
-// grid = 13 blocks of DDPG_REDUCE_THREADS: block k < 12 sums tensor k of the n_blocks partials (rows of `stride` floats) in
-// block order into grads [PA + PC] and writes the tensor's sum of squares (per thread over its elements in ascending
-// order, then a pairwise tree over the threads: a fixed order); block 12 writes losses = {sum of squared errors / rows,
-// -(sum of Q) / rows}.
+// grid = 13 blocks of DDPG_REDUCE_THREADS: block k < 12 is upd_reduce_tensor on tensor k of the n_blocks partials (rows of
+// `stride` floats) into grads [PA + PC]; block 12 writes losses = {sum of squared errors / rows, -(sum of Q) / rows}.
+// (Twelve tensors of two networks and two losses divided by the rows: not the policies' reduce body.)
 __global__ void __launch_bounds__(DDPG_REDUCE_THREADS) HipDdpgReduce(const float *__restrict__ partials, int n_blocks,
                                                                      int H, int O, long rows, float *__restrict__ grads,
                                                                      float *__restrict__ sumsq, float *__restrict__ losses) {
@@ -503,27 +419,12 @@ __global__ void __launch_bounds__(DDPG_REDUCE_THREADS) HipDdpgReduce(const float
     }
     return;
   }
-  const DdpgTensor t = ddpg_tensor(blockIdx.x, H, O);
-  float sq = 0.0f;
-  for (int e = tid; e < t.n; e += DDPG_REDUCE_THREADS) {
-    float s = 0.0f;
-    for (int b = 0; b < n_blocks; ++b) s += partials[b * stride + t.off + e];
-    grads[t.off + e] = s;
-    sq += s * s;
-  }
-  tree[tid] = sq;
-  __syncthreads();
-  for (int half = DDPG_REDUCE_THREADS / 2; half > 0; half >>= 1) {
-    if (tid < half) tree[tid] += tree[tid + half];
-    __syncthreads();
-  }
-  if (tid == 0) sumsq[blockIdx.x] = tree[0];
+  upd_reduce_tensor<DDPG_REDUCE_THREADS>(tree, partials, n_blocks, stride, ddpg_tensor(blockIdx.x, H, O), grads, sumsq);
 }
 
 // One thread per parameter of (actor, critic).  theta / target / exp_avg / exp_avg_sq / grads: PA + PC floats.
-//   clip   max_norm > 0: g *= min(1, max_norm / (norm + 1e-6)), norm = the 2-norm of the network's six tensor norms
-//   Adam   m = lerp(m, g, 1 - beta1); v = v beta2 + (1 - beta2) g g; denom = sqrt(v) / bc2_sqrt + eps;
-//          p = p - step_size (m / denom), step_size = lr / (1 - beta1^step) and bc2_sqrt = sqrt(1 - beta2^step) from the host
+//   clip over the network's six tensor norms and Adam: upd_clip_adam's statements with the network's step size (written
+//          out here, where the soft update follows them: as a call they compile to another schedule)
 //   target t = t (1 - tau) + p tau: two products, one sum
 //   packed the rollout's copy of the actor (pack_rollout_actor: W0 rows padded to an even length) or null
 __global__ void __launch_bounds__(256) HipDdpgApply(float *__restrict__ theta, float *__restrict__ target,

@@ -13,34 +13,24 @@
 //   5. HipPgApply                clip_grad_norm_ over the eight tensors, torch.optim.Adam's default expression, and the
 //                                refill of the packed policy the rollout kernels read.
 //
-// No float atomics, no cross-block communication inside a launch, nothing read back by the host.
+// The summation order, relu'(0) = 0, "no float atomics, nothing read back" and the clip and Adam expressions are the parity
+// contract pg_update_common.h states, with the pieces this unit shares with pg_update_gridworld.hip and ddpg_update.hip.
 //
 // One network = two hidden layers of H ReLU units on O inputs, one head of A logits (1 <= A <= 8, a launch argument) and
 // the value head, all float32, FLAT in the order of the module's parameters (training/models.py::FullyConnected):
-// W0 [H][O], b0 [H], W1 [H][H], b1 [H], Wp [A][H], bp [A], Wv [H], bv [1] (pg_net_floats(H, O, A) floats).  The first
+// W0 [H][O], b0 [H], W1 [H][H], b1 [H], Wp [A][H], bp [A], Wv [H], bv [1] (upd_pg_net_floats(H, O, A) floats).  The first
 // six are pack_rollout_policy's layout: the packed policy is a prefix of the flat buffer.  In LDS the value head starts
 // at a fixed 16-byte aligned offset behind EIGHT bias slots (PgNet), whatever A is.
 //
-// Forward arithmetic is cartpole.hip::cp_policy_cum's / classic_control.hip::cc_policy_cum's: acc = bias, then one fmaf per
-// input in index order, fmaxf(acc, 0); the weights in LDS read as broadcasts, one row per lane.  relu'(0) = 0.
-//
-// Stage 3, per block and per tile of PG_TILE rows (grid-stride over the tiles), follows ddpg_update.hip: every lane runs
-// the forward and backward passes of its row and stages what the parameter gradients need -- activations, deltas -- in
-// LDS, unit-major ([unit][row]); then every thread adds the tile's rows, in row order, to the FIXED set of gradient
-// entries it owns for the whole launch.  A block therefore accumulates every entry in one fixed order (tiles ascending,
-// rows ascending) and writes its partial once; blocks without rows write zeros.
+// Forward arithmetic is cartpole.hip::cp_policy_cum's / classic_control.hip::cc_policy_cum's.
 //
 // Restated in float64 in tests/pg_update_cases.py.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "pg_update_common.h"
 
 #define PG_TILE 128                 // rows per tile = threads per block of HipPgGradients
-#define PG_LD (PG_TILE + 4)         // staged arrays are [unit][PG_LD]: rows of 16-byte multiples, units 4 banks apart
+#define PG_LD (PG_TILE + 4)         // staged arrays are [unit][PG_LD]
 #define PG_MAX_ACTIONS 8
 #define PG_OUTPUTS (PG_MAX_ACTIONS + 1)   // staged output deltas: the logits' (those below A are real), then the value's
-
-constexpr int pg_net_floats(int H, int O, int A) { return H * O + H + H * H + H + A * H + A + H + 1; }
-constexpr int pg_pad4(int n) { return (n + 3) & ~3; }
 
 // offsets inside the LDS copy (W0 .. bp as in the flat buffer; the value head behind eight bias slots)
 template <int H, int O>
@@ -50,7 +40,7 @@ struct PgNet {
   static constexpr int bp(int A) { return WP + A * H; }
   static constexpr int wv(int A) { return WP + A * H + PG_MAX_ACTIONS; }
   static constexpr int bv(int A) { return WP + A * H + PG_MAX_ACTIONS + H; }
-  static constexpr int LDS = pg_pad4(WP + PG_MAX_ACTIONS * H + PG_MAX_ACTIONS + H + 1);
+  static constexpr int LDS = upd_pad4(WP + PG_MAX_ACTIONS * H + PG_MAX_ACTIONS + H + 1);
 };
 
 template <int H, int O>
@@ -61,7 +51,8 @@ __device__ __forceinline__ void pg_copy_net_to_lds(float *dst, const float *__re
   for (int i = threadIdx.x; i < H + 1; i += blockDim.x) dst[L::wv(A) + i] = theta[head + i];
 }
 
-// the shared forward: h1 = relu(W0 x + b0), h2 = relu(W1 h1 + b1), returns v = Wv h2 + bv
+// the forward: h1 = relu(W0 x + b0), then the header's second layer and value head.  (The first layer stays here: it reads
+// float2 rows of O floats, the gridworld unit's float4 rows at stride 24 plus a tail.)
 template <int H, int O>
 __device__ __forceinline__ float pg_forward(const float *w, int A, const float (&x)[O], float (&h1)[H], float (&h2)[H]) {
   using L = PgNet<H, O>;
@@ -75,55 +66,7 @@ __device__ __forceinline__ float pg_forward(const float *w, int A, const float (
     }
     h1[i] = fmaxf(acc, 0.0f);
   }
-#pragma unroll
-  for (int i = 0; i < H; ++i) {
-    float acc = w[L::B1 + i];
-#pragma unroll
-    for (int j = 0; j < H; j += 4) {
-      const float4 wr = *(const float4 *)(w + L::W1 + i * H + j);
-      acc = fmaf(wr.x, h1[j], acc); acc = fmaf(wr.y, h1[j + 1], acc);
-      acc = fmaf(wr.z, h1[j + 2], acc); acc = fmaf(wr.w, h1[j + 3], acc);
-    }
-    h2[i] = fmaxf(acc, 0.0f);
-  }
-  const float *wv = w + L::wv(A);
-  float v = wv[H];
-#pragma unroll
-  for (int j = 0; j < H; j += 4) {
-    const float4 wr = *(const float4 *)(wv + j);
-    v = fmaf(wr.x, h2[j], v); v = fmaf(wr.y, h2[j + 1], v);
-    v = fmaf(wr.z, h2[j + 2], v); v = fmaf(wr.w, h2[j + 3], v);
-  }
-  return v;
-}
-
-template <int H>
-__device__ __forceinline__ uint64_t pg_positive_mask(const float (&h)[H]) {
-  uint64_t m = 0;
-#pragma unroll
-  for (int i = 0; i < H; ++i) m |= (h[i] > 0.0f) ? (1ull << i) : 0ull;
-  return m;
-}
-
-// d1[j] = relu'(h1[j]) * sum_i W1[i][j] d2[i], i ascending from +0; d2[i] is read from the lane's own staged column
-// (no second H-wide array in registers)
-template <int H, int O>
-__device__ __forceinline__ void pg_layer1_backward(const float *w, const float *d2_column, uint64_t mask1, float (&d1)[H]) {
-  using L = PgNet<H, O>;
-#pragma unroll
-  for (int j = 0; j < H; ++j) d1[j] = 0.0f;
-#pragma unroll
-  for (int i = 0; i < H; ++i) {
-    const float d2 = d2_column[i * PG_LD];
-#pragma unroll
-    for (int j = 0; j < H; j += 4) {
-      const float4 wr = *(const float4 *)(w + L::W1 + i * H + j);
-      d1[j] = fmaf(wr.x, d2, d1[j]); d1[j + 1] = fmaf(wr.y, d2, d1[j + 1]);
-      d1[j + 2] = fmaf(wr.z, d2, d1[j + 2]); d1[j + 3] = fmaf(wr.w, d2, d1[j + 3]);
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < H; ++j) d1[j] = ((mask1 >> j) & 1ull) ? d1[j] : 0.0f;
+  return upd_layer1_and_value<H>(w + L::W1, w + L::B1, w + L::wv(A), h1, h2);
 }
 
 // ------------------------------------------------------------------------------------------------------ 1. values
@@ -146,37 +89,20 @@ __device__ __forceinline__ void pg_values_impl(const float *__restrict__ obs, co
 }
 
 // --------------------------------------------------------------------------------------------------- 3. gradients
-// What a thread owns of the gradient for the whole launch (128 threads):
-//   dW1 [H][H]: rows i = ib + NIB a (a < 4), columns j = jb + NJB b (b < JB), ib = tid % NIB, jb = tid / NIB
-//   dW0 [H][O]: row i = tid % H, columns k = KB (tid / H) + c (c < KB, k < O)
+// What a thread owns of the gradient for the whole launch (128 threads): UpdOwn's share of dW0, db0, dW1, db1, and
 //   dWp [A][H], dWv [H]: unit i = tid % H, outputs o = tid / H + KG c (c < OB; o < A: a logit, o = 8: the value)
-//   db0, db1: unit i = tid (tid < H);  dbp, dbv: output o = tid (tid < 9);  the four sums: threads 16 .. 19
+//   dbp, dbv: output o = tid (tid < 9);  the four sums: threads 16 .. 19
 template <int H>
-struct PgOwn {
-  static constexpr int NIB = H / 4, NJB = PG_TILE / NIB, JB = H / NJB, KG = PG_TILE / H;
-  static constexpr int OB = (PG_OUTPUTS + KG - 1) / KG;
-  static_assert(NIB * NJB == PG_TILE && NJB * JB == H && KG * H == PG_TILE, "ownership covers the matrix exactly");
+struct PgOwn : UpdOwn<H, PG_TILE> {
+  static constexpr int OB = (PG_OUTPUTS + PgOwn::KG - 1) / PgOwn::KG;
 };
 
 template <int H, int O>
-struct PgAcc {
-  static constexpr int JB = PgOwn<H>::JB, KB = (O + PgOwn<H>::KG - 1) / PgOwn<H>::KG, OB = PgOwn<H>::OB;
-  float w1[4][JB], w0[KB], wo[OB], b0, b1, bo, sum;
-  __device__ __forceinline__ void clear() {
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < JB; ++b) w1[a][b] = 0.0f;
-#pragma unroll
-    for (int c = 0; c < KB; ++c) w0[c] = 0.0f;
-#pragma unroll
-    for (int c = 0; c < OB; ++c) wo[c] = 0.0f;
-    b0 = b1 = bo = sum = 0.0f;
-  }
-};
+using PgAcc = UpdAcc<PgOwn<H>::JB, (O + PgOwn<H>::KG - 1) / PgOwn<H>::KG, PgOwn<H>::OB>;
 
 // dWp[o][i] += sum_r dz[o][r] * h2[i][r]; dWv[i] += sum_r dv[r] * h2[i][r]; dbp[o] += sum_r dz[o][r]; dbv += sum_r dv[r];
-// the four sums += their staged per-row terms   (rows ascending; SD = [PG_OUTPUTS][PG_LD], SS = [4][PG_LD])
+// the four sums += their staged per-row terms   (rows ascending; SD = [PG_OUTPUTS][PG_LD], SS = [4][PG_LD]).  (Stays here:
+// the output rows are eight logit slots of which A are real, then the value's; the gridworld unit's are all real.)
 template <int H, int O>
 __device__ __forceinline__ void pg_acc_heads(PgAcc<H, O> &g, const float *S1, const float *SD, const float *SS, int A) {
   using W = PgOwn<H>;
@@ -201,62 +127,7 @@ __device__ __forceinline__ void pg_acc_heads(PgAcc<H, O> &g, const float *S1, co
   }
 }
 
-// dW1[i][j] += sum_r d2[i][r] * h1[j][r]; db1[i] += sum_r d2[i][r]
-template <int H, int O>
-__device__ __forceinline__ void pg_acc_w1(PgAcc<H, O> &g, const float *S0, const float *S1) {
-  using W = PgOwn<H>;
-  constexpr int JB = W::JB;
-  const int tid = threadIdx.x, ib = tid % W::NIB, jb = tid / W::NIB;
-  for (int r = 0; r < PG_TILE; r += 4) {
-    float4 d[4], h[JB];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) d[a] = *(const float4 *)(S1 + (ib + W::NIB * a) * PG_LD + r);
-#pragma unroll
-    for (int b = 0; b < JB; ++b) h[b] = *(const float4 *)(S0 + (jb + W::NJB * b) * PG_LD + r);
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < JB; ++b) {
-        float acc = g.w1[a][b];
-        acc = fmaf(d[a].x, h[b].x, acc); acc = fmaf(d[a].y, h[b].y, acc);
-        acc = fmaf(d[a].z, h[b].z, acc); acc = fmaf(d[a].w, h[b].w, acc);
-        g.w1[a][b] = acc;
-      }
-  }
-  if (tid < H) {
-    for (int r = 0; r < PG_TILE; r += 4) {
-      const float4 d = *(const float4 *)(S1 + tid * PG_LD + r);
-      g.b1 += d.x; g.b1 += d.y; g.b1 += d.z; g.b1 += d.w;
-    }
-  }
-}
-
-// dW0[i][k] += sum_r d1[i][r] * x[k][r]; db0[i] += sum_r d1[i][r]   (x staged as [O][PG_LD])
-template <int H, int O>
-__device__ __forceinline__ void pg_acc_w0(PgAcc<H, O> &g, const float *S1, const float *S2) {
-  constexpr int KB = PgAcc<H, O>::KB;
-  const int tid = threadIdx.x, i = tid % H, k0 = KB * (tid / H);
-  for (int r = 0; r < PG_TILE; r += 4) {
-    const float4 d = *(const float4 *)(S1 + i * PG_LD + r);
-#pragma unroll
-    for (int c = 0; c < KB; ++c) {
-      if (k0 + c < O) {
-        const float4 x = *(const float4 *)(S2 + (k0 + c) * PG_LD + r);
-        float acc = g.w0[c];
-        acc = fmaf(d.x, x.x, acc); acc = fmaf(d.y, x.y, acc); acc = fmaf(d.z, x.z, acc); acc = fmaf(d.w, x.w, acc);
-        g.w0[c] = acc;
-      }
-    }
-  }
-  if (tid < H) {
-    for (int r = 0; r < PG_TILE; r += 4) {
-      const float4 d = *(const float4 *)(S1 + tid * PG_LD + r);
-      g.b0 += d.x; g.b0 += d.y; g.b0 += d.z; g.b0 += d.w;
-    }
-  }
-}
-
-// the block's partial, in the FLAT layout (A logits): P floats, then the four sums
+// the block's partial, in the FLAT layout (A logits): P floats, then the four sums.  (Stays here for its head part.)
 template <int H, int O>
 __device__ __forceinline__ void pg_write_partial(const PgAcc<H, O> &g, float *out, int A) {
   using L = PgNet<H, O>;
@@ -287,17 +158,11 @@ __device__ __forceinline__ void pg_write_partial(const PgAcc<H, O> &g, float *ou
   if (tid >= 16 && tid < 20) out[BV + 1 + tid - 16] = g.sum;
 }
 
-template <int H>
-__device__ __forceinline__ void pg_stage(float *S, int row, const float (&h)[H]) {
-#pragma unroll
-  for (int i = 0; i < H; ++i) S[i * PG_LD + row] = h[i];
-}
-
 // obs [T * E][O], actions [T * E] int32, adv / ret [T * E]; theta flat; partials [gridDim.x][P + 4]: the block's gradient,
 // then its sums of logp * adv, of the entropy, of (v - ret)^2 and of adv.  Dynamic LDS: pg_gradients_lds_floats(H, O)
 // floats.  blockDim.x = PG_TILE.
 constexpr int pg_gradients_lds_floats(int H, int O) {
-  return pg_pad4(H * O + H + H * H + H + PG_MAX_ACTIONS * H + PG_MAX_ACTIONS + H + 1) + 2 * H * PG_LD + O * PG_LD +
+  return upd_pad4(H * O + H + H * H + H + PG_MAX_ACTIONS * H + PG_MAX_ACTIONS + H + 1) + 2 * H * PG_LD + O * PG_LD +
          PG_OUTPUTS * PG_LD + 4 * PG_LD;
 }
 
@@ -336,8 +201,8 @@ __device__ __forceinline__ void pg_gradients_impl(const float *__restrict__ obs,
       float dz[PG_MAX_ACTIONS], dv;
       float h1[H], h2[H];
       const float v = pg_forward<H, O>(w, A, x, h1, h2);
-      m1 = pg_positive_mask<H>(h1);
-      m2 = pg_positive_mask<H>(h2);
+      m1 = upd_positive_mask<H>(h1);
+      m2 = upd_positive_mask<H>(h2);
       // the logits: acc = bias, one fmaf per hidden unit in index order
       float z[PG_MAX_ACTIONS], m = -__builtin_inff();
 #pragma unroll
@@ -357,7 +222,8 @@ __device__ __forceinline__ void pg_gradients_impl(const float *__restrict__ obs,
       }
       // HipPolicyGradientHead's statements (policy_mlp.hip), one head: the shift by the maximum FIRST.  (Same statements,
       // same build flags -- no contraction -- but other logits and another schedule around them: the results agree with
-      // that entry's under the tests' bound and are not claimed bit-identical to it.)
+      // that entry's under the tests' bound and are not claimed bit-identical to it.  They stay in each unit: as one
+      // template over the action bound they compile to another schedule here.)
       float total = 0.0f;
 #pragma unroll
       for (int j = 0; j < PG_MAX_ACTIONS; ++j)
@@ -385,8 +251,8 @@ __device__ __forceinline__ void pg_gradients_impl(const float *__restrict__ obs,
       }
       const float d = v - rt;
       dv = live ? 2.0f * vf_coeff * d * inv_R : 0.0f;
-      pg_stage<H>(S0, tid, h1);
-      pg_stage<H>(S1, tid, h2);
+      upd_stage<H, PG_LD>(S0, tid, h1);
+      upd_stage<H, PG_LD>(S1, tid, h2);
 #pragma unroll
       for (int j = 0; j < PG_MAX_ACTIONS; ++j) SD[j * PG_LD + tid] = dz[j];
       SD[PG_MAX_ACTIONS * PG_LD + tid] = dv;
@@ -402,7 +268,7 @@ __device__ __forceinline__ void pg_gradients_impl(const float *__restrict__ obs,
     __syncthreads();
     {
       // d2[i] = relu'(h2[i]) * (sum_j dz[j] Wp[j][i] + dv Wv[i]), j ascending from +0, the value last (the deltas read
-      // back from the lane's own staged column)
+      // back from the lane's own staged column).  (Stays here: all H sums in flight; that form spills in the gridworld unit.)
       float d2[H], dz[PG_MAX_ACTIONS];
 #pragma unroll
       for (int j = 0; j < PG_MAX_ACTIONS; ++j) dz[j] = SD[j * PG_LD + tid];
@@ -428,34 +294,24 @@ __device__ __forceinline__ void pg_gradients_impl(const float *__restrict__ obs,
       }
 #pragma unroll
       for (int i = 0; i < H; ++i) d2[i] = ((m2 >> i) & 1ull) ? d2[i] : 0.0f;
-      pg_stage<H>(S1, tid, d2);
+      upd_stage<H, PG_LD>(S1, tid, d2);
     }
     __syncthreads();
-    pg_acc_w1<H, O>(acc, S0, S1);
+    upd_acc_w1<H, PG_TILE, PG_LD>(acc, S0, S1);
     {
       float d1[H];
-      pg_layer1_backward<H, O>(w, S1 + tid, m1, d1);
+      upd_layer1_backward<H, PG_LD>(w + L::W1, S1 + tid, m1, d1);
       __syncthreads();
-      pg_stage<H>(S1, tid, d1);
+      upd_stage<H, PG_LD>(S1, tid, d1);
     }
     __syncthreads();
-    pg_acc_w0<H, O>(acc, S1, S2);
+    upd_acc_w0<H, PG_TILE, PG_LD, O>(acc, S1, S2);
     __syncthreads();
   }
-  pg_write_partial<H, O>(acc, partials + (long)blockIdx.x * (pg_net_floats(H, O, A) + 4), A);
+  pg_write_partial<H, O>(acc, partials + (long)blockIdx.x * (upd_pg_net_floats(H, O, A) + 4), A);
 }
 
-// -------------------------------------------------------------------------------------------------- 4 and 5: layout
-// the eight parameter tensors inside the flat P floats
-struct PgTensor { int off, n; };
-
-__device__ __forceinline__ PgTensor pg_tensor(int k, int H, int O, int A) {
-  const int n[8] = {H * O, H, H * H, H, A * H, A, H, 1};
-  int off = 0;
-  for (int j = 0; j < k; ++j) off += n[j];
-  return {off, n[k]};
-}
-
+// ------------------------------------------------------------------------------------------- 4 and 5: reduce, apply
 __device__ __forceinline__ bool pg_shape_ok(int H, int O, int A) {
   return (H == 32 || H == 64) && (O == 2 || O == 4 || O == 6) && A >= 1 && A <= PG_MAX_ACTIONS;
 }
@@ -486,47 +342,17 @@ PG_ENTRIES(64, 2)
 PG_ENTRIES(64, 4)
 PG_ENTRIES(64, 6)
 
-// grid = 9 blocks of PG_REDUCE_THREADS: block k < 8 sums tensor k of the n_blocks partials (rows of P + 4 floats) in
-// block order into grads [P] and writes the tensor's sum of squares (per thread over its elements in ascending order,
-// then a pairwise tree over the threads: a fixed order); block 8 writes sums [4] = the four sums over the blocks, in
-// block order.
+// upd_pg_reduce on grid = 9 blocks of PG_REDUCE_THREADS
 __global__ void __launch_bounds__(PG_REDUCE_THREADS) HipPgReduce(const float *__restrict__ partials, int n_blocks, int H,
                                                                  int O, int A, float *__restrict__ grads,
                                                                  float *__restrict__ sumsq, float *__restrict__ sums) {
   __shared__ float tree[PG_REDUCE_THREADS];
   if (!pg_shape_ok(H, O, A)) return;
-  const int P = pg_net_floats(H, O, A);
-  const long stride = P + 4;
-  const int tid = threadIdx.x;
-  if (blockIdx.x >= 8) {
-    if (blockIdx.x == 8 && tid < 4) {
-      float s = 0.0f;
-      for (int b = 0; b < n_blocks; ++b) s += partials[b * stride + P + tid];
-      sums[tid] = s;
-    }
-    return;
-  }
-  const PgTensor t = pg_tensor(blockIdx.x, H, O, A);
-  float sq = 0.0f;
-  for (int e = tid; e < t.n; e += PG_REDUCE_THREADS) {
-    float s = 0.0f;
-    for (int b = 0; b < n_blocks; ++b) s += partials[b * stride + t.off + e];
-    grads[t.off + e] = s;
-    sq += s * s;
-  }
-  tree[tid] = sq;
-  __syncthreads();
-  for (int half = PG_REDUCE_THREADS / 2; half > 0; half >>= 1) {
-    if (tid < half) tree[tid] += tree[tid + half];
-    __syncthreads();
-  }
-  if (tid == 0) sumsq[blockIdx.x] = tree[0];
+  upd_pg_reduce<PG_REDUCE_THREADS>(tree, partials, n_blocks, upd_pg_net_floats(H, O, A), H, O, A, grads, sumsq, sums);
 }
 
 // One thread per parameter.  theta / exp_avg / exp_avg_sq / grads: P floats.
-//   clip   max_norm > 0: g *= min(1, max_norm / (norm + 1e-6)), norm = the 2-norm of the eight tensor norms
-//   Adam   m = lerp(m, g, 1 - beta1); v = v beta2 + (1 - beta2) g g; denom = sqrt(v) / bc2_sqrt + eps;
-//          p = p - step_size (m / denom), step_size = lr / (1 - beta1^step) and bc2_sqrt = sqrt(1 - beta2^step) from the host
+//   clip over the eight tensor norms and Adam: upd_clip_adam
 //   packed the rollout's copy of the policy (pack_rollout_policy: W0 .. bp, the first P - H - 1 floats) or null
 __global__ void __launch_bounds__(256) HipPgApply(float *__restrict__ theta, float *__restrict__ exp_avg,
                                                   float *__restrict__ exp_avg_sq, const float *__restrict__ grads,
@@ -534,27 +360,11 @@ __global__ void __launch_bounds__(256) HipPgApply(float *__restrict__ theta, flo
                                                   int A, float max_norm, float step_size, float bc2_sqrt,
                                                   float one_minus_beta1, float beta2, float one_minus_beta2, float eps) {
   if (!pg_shape_ok(H, O, A)) return;
-  const int P = pg_net_floats(H, O, A);
+  const int P = upd_pg_net_floats(H, O, A);
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= P) return;
-  float g = grads[idx];
-  if (max_norm > 0.0f) {
-    float total = 0.0f;
-    for (int k = 0; k < 8; ++k) {
-      const float norm = sqrtf(sumsq[k]);
-      total += norm * norm;
-    }
-    const float coef = fminf(max_norm / (sqrtf(total) + 1e-6f), 1.0f);
-    g *= coef;
-  }
-  const float m0 = exp_avg[idx];
-  const float m = fmaf(one_minus_beta1, g - m0, m0);
-  const float v = fmaf(one_minus_beta2, g * g, exp_avg_sq[idx] * beta2);
-  const float denom = sqrtf(v) / bc2_sqrt + eps;
-  const float p = fmaf(-step_size, m / denom, theta[idx]);
-  exp_avg[idx] = m;
-  exp_avg_sq[idx] = v;
-  theta[idx] = p;
+  const float p = upd_clip_adam(idx, theta, exp_avg, exp_avg_sq, grads, sumsq, 8, max_norm, step_size, bc2_sqrt,
+                                one_minus_beta1, beta2, one_minus_beta2, eps);
   if (packed != nullptr && idx < P - H - 1) packed[idx] = p;
 }
 

@@ -13,26 +13,23 @@
 //   5. HipPgGwApply            clip_grad_norm_, Adam, and the refill of the rollout's packed policy in
 //                              pack_gridworld_policy's layout -- EVERY float of that block, pad columns and tail included.
 //
-// No float atomics, no cross-block communication inside a launch, nothing read back by the host.
+// The summation order, relu'(0) = 0, "no float atomics, nothing read back" and the clip and Adam expressions are the parity
+// contract pg_update_common.h states, with the pieces this unit shares with pg_update.hip and ddpg_update.hip.
 //
 // The network FLAT, in the order of the module's parameters (the parameters are views of it: FlatPolicy): W0 [H][21]
 // (unpadded), b0 [H], W1 [H][H], b1 [H], Wp [5][H], bp [5], Wv [H], bv [1].  In LDS the rows of W0 are GW_IN_STRIDE = 24
 // floats apart (tag_gridworld_n5_common.h's GW5_IN_STRIDE: every row starts on a 16-byte boundary), the three pad columns
 // zero, and the value head starts on a 16-byte boundary behind eight bias slots.
 //
-// Forward arithmetic is gw5_policy_probs' (the same header): acc = bias, then one fmaf per input in index order, fmaxf(acc, 0).  relu'(0) = 0.
-// The probabilities are not claimed bit-identical to the rollout's.
+// Forward arithmetic is gw5_policy_probs' (that header).  The probabilities are not claimed bit-identical to the rollout's.
 //
-// Stage 3 keeps pg_update.hip's structure: a tile of 128 rows per 128-thread block, activations and deltas staged
-// unit-major in LDS, every thread owning a fixed set of gradient entries for the whole launch (tiles ascending, rows
-// ascending: one fixed summation order), one partial per block, zeros from a block without rows.  One thing differs: a
-// tile's 128 x 21 observation floats are contiguous in memory, so the block loads them with coalesced loads and writes
-// them transposed into the staged [21][LD] array FIRST, and the forward reads the lane's own column from there (no
-// observation registers live across the backward pass; no 84-byte-strided loads).
+// Stage 3 differs from pg_update.hip's in one thing: a tile's 128 x 21 observation floats are contiguous in memory, so the
+// block loads them with coalesced loads and writes them transposed into the staged [21][LD] array FIRST, and the forward
+// reads the lane's own column from there (no observation registers live across the backward pass; no 84-byte-strided
+// loads).
 //
 // Restated in float64 in tests/pg_update_cases.py (generic in O and A) with tests/pg_update_gridworld_cases.py's inputs.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "pg_update_common.h"
 
 #define GW_TILE 128                 // rows per tile = threads per block of HipPgGwGradients
 #define GW_LD (GW_TILE + 4)         // staged arrays are [unit][GW_LD]
@@ -42,11 +39,10 @@
 #define GW_OUTPUTS (GW_A + 1)       // staged output deltas: the five logits', then the value's
 #define GW_BIAS_SLOTS 8
 
-constexpr int gw_net_floats(int H) { return H * GW_O + H + H * H + H + GW_A * H + GW_A + H + 1; }
-constexpr int gw_pad4(int n) { return (n + 3) & ~3; }
+constexpr int gw_net_floats(int H) { return upd_pg_net_floats(H, GW_O, GW_A); }
 // pack_gridworld_policy's block: W0 [H][24], b0, W1, b1, Wp, bp, rounded up to whole 16-byte vectors
 constexpr int gw_packed_body(int H) { return H * GW_IN_STRIDE + H + H * H + H + GW_A * H + GW_A; }
-constexpr int gw_packed_floats(int H) { return gw_pad4(gw_packed_body(H)); }
+constexpr int gw_packed_floats(int H) { return upd_pad4(gw_packed_body(H)); }
 
 // offsets inside the LDS copy
 template <int H>
@@ -54,7 +50,7 @@ struct GwNet {
   static_assert(H % 4 == 0, "the rows of W0 / W1 / Wp / Wv are read as float4");
   static constexpr int W0 = 0, B0 = H * GW_IN_STRIDE, W1 = B0 + H, B1 = W1 + H * H, WP = B1 + H, BP = WP + GW_A * H;
   static constexpr int WV = BP + GW_BIAS_SLOTS, BV = WV + H;
-  static constexpr int LDS = gw_pad4(BV + 1);
+  static constexpr int LDS = upd_pad4(BV + 1);
   // the flat buffer
   static constexpr int F_B0 = H * GW_O, F_W1 = F_B0 + H, F_B1 = F_W1 + H * H, F_WP = F_B1 + H, F_BP = F_WP + GW_A * H;
   static constexpr int F_WV = F_BP + GW_A, F_BV = F_WV + H, P = F_BV + 1;
@@ -72,7 +68,8 @@ __device__ __forceinline__ void gw_copy_net_to_lds(float *dst, const float *__re
   for (int i = threadIdx.x; i < H + 1; i += blockDim.x) dst[L::WV + i] = theta[L::F_WV + i];
 }
 
-// h1 = relu(W0 x + b0), x[k] = x_column[k * x_stride]
+// h1 = relu(W0 x + b0), x[k] = x_column[k * x_stride].  (Stays here: float4 rows at stride 24 plus a tail; pg_update.hip
+// reads float2 rows of O floats.)
 template <int H>
 __device__ __forceinline__ void gw_layer0(const float *w, const float *x_column, int x_stride, float (&h1)[H]) {
   using L = GwNet<H>;
@@ -93,59 +90,6 @@ __device__ __forceinline__ void gw_layer0(const float *w, const float *x_column,
   }
 }
 
-// h2 = relu(W1 h1 + b1), returns v = Wv h2 + bv
-template <int H>
-__device__ __forceinline__ float gw_layer1_and_value(const float *w, const float (&h1)[H], float (&h2)[H]) {
-  using L = GwNet<H>;
-#pragma unroll
-  for (int i = 0; i < H; ++i) {
-    float acc = w[L::B1 + i];
-#pragma unroll
-    for (int j = 0; j < H; j += 4) {
-      const float4 wr = *(const float4 *)(w + L::W1 + i * H + j);
-      acc = fmaf(wr.x, h1[j], acc); acc = fmaf(wr.y, h1[j + 1], acc);
-      acc = fmaf(wr.z, h1[j + 2], acc); acc = fmaf(wr.w, h1[j + 3], acc);
-    }
-    h2[i] = fmaxf(acc, 0.0f);
-  }
-  float v = w[L::BV];
-#pragma unroll
-  for (int j = 0; j < H; j += 4) {
-    const float4 wr = *(const float4 *)(w + L::WV + j);
-    v = fmaf(wr.x, h2[j], v); v = fmaf(wr.y, h2[j + 1], v);
-    v = fmaf(wr.z, h2[j + 2], v); v = fmaf(wr.w, h2[j + 3], v);
-  }
-  return v;
-}
-
-template <int H>
-__device__ __forceinline__ uint64_t gw_positive_mask(const float (&h)[H]) {
-  uint64_t m = 0;
-#pragma unroll
-  for (int i = 0; i < H; ++i) m |= (h[i] > 0.0f) ? (1ull << i) : 0ull;
-  return m;
-}
-
-// d1[j] = relu'(h1[j]) * sum_i W1[i][j] d2[i], i ascending from +0; d2[i] read from the lane's own staged column
-template <int H>
-__device__ __forceinline__ void gw_layer1_backward(const float *w, const float *d2_column, uint64_t mask1, float (&d1)[H]) {
-  using L = GwNet<H>;
-#pragma unroll
-  for (int j = 0; j < H; ++j) d1[j] = 0.0f;
-#pragma unroll
-  for (int i = 0; i < H; ++i) {
-    const float d2 = d2_column[i * GW_LD];
-#pragma unroll
-    for (int j = 0; j < H; j += 4) {
-      const float4 wr = *(const float4 *)(w + L::W1 + i * H + j);
-      d1[j] = fmaf(wr.x, d2, d1[j]); d1[j + 1] = fmaf(wr.y, d2, d1[j + 1]);
-      d1[j + 2] = fmaf(wr.z, d2, d1[j + 2]); d1[j + 3] = fmaf(wr.w, d2, d1[j + 3]);
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < H; ++j) d1[j] = ((mask1 >> j) & 1ull) ? d1[j] : 0.0f;
-}
-
 // ------------------------------------------------------------------------------------------------------ 1. values
 // obs [rows][21]; values [rows].  Dynamic LDS: GwNet<H>::LDS floats.
 template <int H>
@@ -160,42 +104,25 @@ __device__ __forceinline__ void gw_values_impl(const float *__restrict__ obs, co
     asm volatile("" ::: "memory");
     float h1[H], h2[H];
     gw_layer0<H>(gw_lds, obs + g * GW_O, 1, h1);
-    values[g] = gw_layer1_and_value<H>(gw_lds, h1, h2);
+    values[g] = upd_layer1_and_value<H>(gw_lds + GwNet<H>::W1, gw_lds + GwNet<H>::B1, gw_lds + GwNet<H>::WV, h1, h2);
   }
 }
 
 // --------------------------------------------------------------------------------------------------- 3. gradients
-// What a thread owns of the gradient for the whole launch (128 threads):
-//   dW1 [H][H]: rows i = ib + NIB a (a < 4), columns j = jb + NJB b (b < JB), ib = tid % NIB, jb = tid / NIB
-//   dW0 [H][21]: row i = tid % H, columns k = KB (tid / H) + c (c < KB, k < 21)
+// What a thread owns of the gradient for the whole launch (128 threads): UpdOwn's share of dW0, db0, dW1, db1, and
 //   dWp [5][H], dWv [H]: unit i = tid % H, outputs o = tid / H + KG c (c < OB; o < 5: a logit, o = 5: the value)
-//   db0, db1: unit i = tid (tid < H);  dbp, dbv: output o = tid (tid < 6);  the four sums: threads 16 .. 19
+//   dbp, dbv: output o = tid (tid < 6);  the four sums: threads 16 .. 19
 template <int H>
-struct GwOwn {
-  static constexpr int NIB = H / 4, NJB = GW_TILE / NIB, JB = H / NJB, KG = GW_TILE / H;
-  static constexpr int OB = (GW_OUTPUTS + KG - 1) / KG, KB = (GW_O + KG - 1) / KG;
-  static_assert(NIB * NJB == GW_TILE && NJB * JB == H && KG * H == GW_TILE, "ownership covers the matrix exactly");
+struct GwOwn : UpdOwn<H, GW_TILE> {
+  static constexpr int OB = (GW_OUTPUTS + GwOwn::KG - 1) / GwOwn::KG, KB = (GW_O + GwOwn::KG - 1) / GwOwn::KG;
 };
 
 template <int H>
-struct GwAcc {
-  static constexpr int JB = GwOwn<H>::JB, KB = GwOwn<H>::KB, OB = GwOwn<H>::OB;
-  float w1[4][JB], w0[KB], wo[OB], b0, b1, bo, sum;
-  __device__ __forceinline__ void clear() {
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < JB; ++b) w1[a][b] = 0.0f;
-#pragma unroll
-    for (int c = 0; c < KB; ++c) w0[c] = 0.0f;
-#pragma unroll
-    for (int c = 0; c < OB; ++c) wo[c] = 0.0f;
-    b0 = b1 = bo = sum = 0.0f;
-  }
-};
+using GwAcc = UpdAcc<GwOwn<H>::JB, GwOwn<H>::KB, GwOwn<H>::OB>;
 
 // dWp[o][i] += sum_r dz[o][r] * h2[i][r]; dWv[i] += sum_r dv[r] * h2[i][r]; dbp[o] += sum_r dz[o][r]; dbv += sum_r dv[r];
-// the four sums += their staged per-row terms   (rows ascending; SD = [GW_OUTPUTS][GW_LD], SS = [4][GW_LD])
+// the four sums += their staged per-row terms   (rows ascending; SD = [GW_OUTPUTS][GW_LD], SS = [4][GW_LD]).  (Stays here:
+// six output rows, all real; pg_update.hip's are eight logit slots guarded by A, then the value's.)
 template <int H>
 __device__ __forceinline__ void gw_acc_heads(GwAcc<H> &g, const float *S1, const float *SD, const float *SS) {
   using W = GwOwn<H>;
@@ -220,62 +147,7 @@ __device__ __forceinline__ void gw_acc_heads(GwAcc<H> &g, const float *S1, const
   }
 }
 
-// dW1[i][j] += sum_r d2[i][r] * h1[j][r]; db1[i] += sum_r d2[i][r]
-template <int H>
-__device__ __forceinline__ void gw_acc_w1(GwAcc<H> &g, const float *S0, const float *S1) {
-  using W = GwOwn<H>;
-  constexpr int JB = W::JB;
-  const int tid = threadIdx.x, ib = tid % W::NIB, jb = tid / W::NIB;
-  for (int r = 0; r < GW_TILE; r += 4) {
-    float4 d[4], h[JB];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) d[a] = *(const float4 *)(S1 + (ib + W::NIB * a) * GW_LD + r);
-#pragma unroll
-    for (int b = 0; b < JB; ++b) h[b] = *(const float4 *)(S0 + (jb + W::NJB * b) * GW_LD + r);
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-      for (int b = 0; b < JB; ++b) {
-        float acc = g.w1[a][b];
-        acc = fmaf(d[a].x, h[b].x, acc); acc = fmaf(d[a].y, h[b].y, acc);
-        acc = fmaf(d[a].z, h[b].z, acc); acc = fmaf(d[a].w, h[b].w, acc);
-        g.w1[a][b] = acc;
-      }
-  }
-  if (tid < H) {
-    for (int r = 0; r < GW_TILE; r += 4) {
-      const float4 d = *(const float4 *)(S1 + tid * GW_LD + r);
-      g.b1 += d.x; g.b1 += d.y; g.b1 += d.z; g.b1 += d.w;
-    }
-  }
-}
-
-// dW0[i][k] += sum_r d1[i][r] * x[k][r]; db0[i] += sum_r d1[i][r]   (x staged as [21][GW_LD])
-template <int H>
-__device__ __forceinline__ void gw_acc_w0(GwAcc<H> &g, const float *S1, const float *S2) {
-  constexpr int KB = GwOwn<H>::KB;
-  const int tid = threadIdx.x, i = tid % H, k0 = KB * (tid / H);
-  for (int r = 0; r < GW_TILE; r += 4) {
-    const float4 d = *(const float4 *)(S1 + i * GW_LD + r);
-#pragma unroll
-    for (int c = 0; c < KB; ++c) {
-      if (k0 + c < GW_O) {
-        const float4 x = *(const float4 *)(S2 + (k0 + c) * GW_LD + r);
-        float acc = g.w0[c];
-        acc = fmaf(d.x, x.x, acc); acc = fmaf(d.y, x.y, acc); acc = fmaf(d.z, x.z, acc); acc = fmaf(d.w, x.w, acc);
-        g.w0[c] = acc;
-      }
-    }
-  }
-  if (tid < H) {
-    for (int r = 0; r < GW_TILE; r += 4) {
-      const float4 d = *(const float4 *)(S1 + tid * GW_LD + r);
-      g.b0 += d.x; g.b0 += d.y; g.b0 += d.z; g.b0 += d.w;
-    }
-  }
-}
-
-// the block's partial, in the FLAT layout: P floats, then the four sums
+// the block's partial, in the FLAT layout: P floats, then the four sums.  (Stays here for its head part.)
 template <int H>
 __device__ __forceinline__ void gw_write_partial(const GwAcc<H> &g, float *out) {
   using L = GwNet<H>;
@@ -305,17 +177,11 @@ __device__ __forceinline__ void gw_write_partial(const GwAcc<H> &g, float *out) 
   if (tid >= 16 && tid < 20) out[L::P + tid - 16] = g.sum;
 }
 
-template <int H>
-__device__ __forceinline__ void gw_stage(float *S, int row, const float (&h)[H]) {
-#pragma unroll
-  for (int i = 0; i < H; ++i) S[i * GW_LD + row] = h[i];
-}
-
 // obs [rows][21], actions [rows] int32, adv / ret [rows]; theta flat; partials [gridDim.x][P + 4]: the block's gradient,
 // then its sums of logp * adv, of the entropy, of (v - ret)^2 and of adv.  Dynamic LDS: gw_gradients_lds_floats(H)
 // floats.  blockDim.x = GW_TILE.
 constexpr int gw_gradients_lds_floats(int H) {
-  return gw_pad4(H * GW_IN_STRIDE + H + H * H + H + GW_A * H + GW_BIAS_SLOTS + H + 1) + 2 * H * GW_LD + GW_O * GW_LD +
+  return upd_pad4(H * GW_IN_STRIDE + H + H * H + H + GW_A * H + GW_BIAS_SLOTS + H + 1) + 2 * H * GW_LD + GW_O * GW_LD +
          GW_OUTPUTS * GW_LD + 4 * GW_LD;
 }
 
@@ -339,7 +205,8 @@ __device__ __forceinline__ void gw_gradients_impl(const float *__restrict__ obs,
   for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const long g = tile * GW_TILE + tid;
     const bool live = g < rows;
-    // the tile's observation floats, contiguous in memory, transposed into S2 [21][GW_LD] (rows beyond the batch: zeros)
+    // the tile's observation floats, contiguous in memory, transposed into S2 [21][GW_LD] (rows beyond the batch: zeros).
+    // (This unit's alone: pg_update.hip's rows of 2 .. 6 floats are loaded by their lanes.)
     {
       const long first = tile * (GW_TILE * GW_O);
       for (int q = tid; q < GW_TILE * GW_O; q += GW_TILE) {
@@ -360,9 +227,9 @@ __device__ __forceinline__ void gw_gradients_impl(const float *__restrict__ obs,
       float dz[GW_A], dv;
       float h1[H], h2[H];
       gw_layer0<H>(w, S2 + tid, GW_LD, h1);
-      const float v = gw_layer1_and_value<H>(w, h1, h2);
-      m1 = gw_positive_mask<H>(h1);
-      m2 = gw_positive_mask<H>(h2);
+      const float v = upd_layer1_and_value<H>(w + L::W1, w + L::B1, w + L::WV, h1, h2);
+      m1 = upd_positive_mask<H>(h1);
+      m2 = upd_positive_mask<H>(h2);
       // the logits: acc = bias, one fmaf per hidden unit in index order
       float z[GW_A], m = -__builtin_inff();
 #pragma unroll
@@ -377,7 +244,8 @@ __device__ __forceinline__ void gw_gradients_impl(const float *__restrict__ obs,
         z[j] = s;
         m = fmaxf(m, s);
       }
-      // HipPolicyGradientHead's statements (policy_mlp.hip), one head: the shift by the maximum FIRST
+      // HipPolicyGradientHead's statements (policy_mlp.hip), one head: the shift by the maximum FIRST (they stay in each
+      // unit: see pg_update.hip)
       float total = 0.0f;
 #pragma unroll
       for (int j = 0; j < GW_A; ++j) total += expf(z[j] - m);
@@ -403,8 +271,8 @@ __device__ __forceinline__ void gw_gradients_impl(const float *__restrict__ obs,
       }
       const float d = v - rt;
       dv = live ? 2.0f * vf_coeff * d * inv_R : 0.0f;
-      gw_stage<H>(S0, tid, h1);
-      gw_stage<H>(S1, tid, h2);
+      upd_stage<H, GW_LD>(S0, tid, h1);
+      upd_stage<H, GW_LD>(S1, tid, h2);
 #pragma unroll
       for (int j = 0; j < GW_A; ++j) SD[j * GW_LD + tid] = dz[j];
       SD[GW_A * GW_LD + tid] = dv;
@@ -419,7 +287,8 @@ __device__ __forceinline__ void gw_gradients_impl(const float *__restrict__ obs,
     {
       // d2[i] = relu'(h2[i]) * (sum_j dz[j] Wp[j][i] + dv Wv[i]), j ascending from +0, the value last (the deltas read
       // back from the lane's own staged column).  Four units at a time, staged as they are formed: with all H sums in
-      // flight at once the compiler splits the weight rows into 8-byte reads at addresses of their own and spills.
+      // flight at once (pg_update.hip's form) the compiler splits the weight rows into 8-byte reads at addresses of their
+      // own and spills.
       float dz[GW_A];
 #pragma unroll
       for (int j = 0; j < GW_A; ++j) dz[j] = SD[j * GW_LD + tid];
@@ -441,31 +310,21 @@ __device__ __forceinline__ void gw_gradients_impl(const float *__restrict__ obs,
       }
     }
     __syncthreads();
-    gw_acc_w1<H>(acc, S0, S1);
+    upd_acc_w1<H, GW_TILE, GW_LD>(acc, S0, S1);
     {
       float d1[H];
-      gw_layer1_backward<H>(w, S1 + tid, m1, d1);
+      upd_layer1_backward<H, GW_LD>(w + L::W1, S1 + tid, m1, d1);
       __syncthreads();
-      gw_stage<H>(S1, tid, d1);
+      upd_stage<H, GW_LD>(S1, tid, d1);
     }
     __syncthreads();
-    gw_acc_w0<H>(acc, S1, S2);
+    upd_acc_w0<H, GW_TILE, GW_LD, GW_O>(acc, S1, S2);
     __syncthreads();
   }
   gw_write_partial<H>(acc, partials + (long)blockIdx.x * (L::P + 4));
 }
 
-// -------------------------------------------------------------------------------------------------- 4 and 5: layout
-// the eight parameter tensors inside the flat P floats
-struct GwTensor { int off, n; };
-
-__device__ __forceinline__ GwTensor gw_tensor(int k, int H) {
-  const int n[8] = {H * GW_O, H, H * H, H, GW_A * H, GW_A, H, 1};
-  int off = 0;
-  for (int j = 0; j < k; ++j) off += n[j];
-  return {off, n[k]};
-}
-
+// ------------------------------------------------------------------------------------------- 4 and 5: reduce, apply
 __device__ __forceinline__ bool gw_width_ok(int H) { return H == 32 || H == 64; }
 
 #define GW_REDUCE_THREADS 1024
@@ -487,51 +346,22 @@ extern "C" {
 GW_ENTRIES(32)
 GW_ENTRIES(64)
 
-// grid = 9 blocks of GW_REDUCE_THREADS: block k < 8 sums tensor k of the n_blocks partials (rows of P + 4 floats) in
-// block order into grads [P] and writes the tensor's sum of squares (per thread over its elements in ascending order,
-// then a pairwise tree over the threads: a fixed order); block 8 writes sums [4] = the four sums over the blocks, in
-// block order.  (A width other than 32 / 64: touches nothing.)
+// upd_pg_reduce on grid = 9 blocks of GW_REDUCE_THREADS.  (A width other than 32 / 64: touches nothing.)
 __global__ void __launch_bounds__(GW_REDUCE_THREADS) HipPgGwReduce(const float *__restrict__ partials, int n_blocks, int H,
                                                                    float *__restrict__ grads, float *__restrict__ sumsq,
                                                                    float *__restrict__ sums) {
   __shared__ float tree[GW_REDUCE_THREADS];
   if (!gw_width_ok(H)) return;
-  const int P = gw_net_floats(H);
-  const long stride = P + 4;
-  const int tid = threadIdx.x;
-  if (blockIdx.x >= 8) {
-    if (blockIdx.x == 8 && tid < 4) {
-      float s = 0.0f;
-      for (int b = 0; b < n_blocks; ++b) s += partials[b * stride + P + tid];
-      sums[tid] = s;
-    }
-    return;
-  }
-  const GwTensor t = gw_tensor(blockIdx.x, H);
-  float sq = 0.0f;
-  for (int e = tid; e < t.n; e += GW_REDUCE_THREADS) {
-    float s = 0.0f;
-    for (int b = 0; b < n_blocks; ++b) s += partials[b * stride + t.off + e];
-    grads[t.off + e] = s;
-    sq += s * s;
-  }
-  tree[tid] = sq;
-  __syncthreads();
-  for (int half = GW_REDUCE_THREADS / 2; half > 0; half >>= 1) {
-    if (tid < half) tree[tid] += tree[tid + half];
-    __syncthreads();
-  }
-  if (tid == 0) sumsq[blockIdx.x] = tree[0];
+  upd_pg_reduce<GW_REDUCE_THREADS>(tree, partials, n_blocks, gw_net_floats(H), H, GW_O, GW_A, grads, sumsq, sums);
 }
 
 // One thread per float of max(P, the packed block).  theta / exp_avg / exp_avg_sq / grads: P floats.
-//   clip   max_norm > 0: g *= min(1, max_norm / (norm + 1e-6)), norm = the 2-norm of the eight tensor norms
-//   Adam   m = lerp(m, g, 1 - beta1); v = v beta2 + (1 - beta2) g g; denom = sqrt(v) / bc2_sqrt + eps;
-//          p = p - step_size (m / denom), step_size = lr / (1 - beta1^step) and bc2_sqrt = sqrt(1 - beta2^step) from the host
+//   clip over the eight tensor norms and Adam: upd_clip_adam
 //   packed the rollout's copy of the policy in pack_gridworld_policy's layout (gw_packed_floats(H) floats) or null:
 //          thread idx < P - H - 1 writes its parameter where that layout has it (W0 [r][c] at r * 24 + c, the rest 3 H
 //          further on than in the flat buffer); thread idx < gw_packed_floats(H) writes +0 if float idx of the block is a
-//          pad column of W0 or the tail.  Every float of the block is written by exactly one thread.
+//          pad column of W0 or the tail.  Every float of the block is written by exactly one thread.  (This refill is
+//          the unit's own: pg_update.hip's packed policy is a prefix of the flat buffer.)
 __global__ void __launch_bounds__(256) HipPgGwApply(float *__restrict__ theta, float *__restrict__ exp_avg,
                                                     float *__restrict__ exp_avg_sq, const float *__restrict__ grads,
                                                     const float *__restrict__ sumsq, float *__restrict__ packed, int H,
@@ -545,24 +375,8 @@ __global__ void __launch_bounds__(256) HipPgGwApply(float *__restrict__ theta, f
     if (pad) packed[idx] = 0.0f;
   }
   if (idx >= P) return;
-  float g = grads[idx];
-  if (max_norm > 0.0f) {
-    float total = 0.0f;
-    for (int k = 0; k < 8; ++k) {
-      const float norm = sqrtf(sumsq[k]);
-      total += norm * norm;
-    }
-    const float coef = fminf(max_norm / (sqrtf(total) + 1e-6f), 1.0f);
-    g *= coef;
-  }
-  const float m0 = exp_avg[idx];
-  const float m = fmaf(one_minus_beta1, g - m0, m0);
-  const float v = fmaf(one_minus_beta2, g * g, exp_avg_sq[idx] * beta2);
-  const float denom = sqrtf(v) / bc2_sqrt + eps;
-  const float p = fmaf(-step_size, m / denom, theta[idx]);
-  exp_avg[idx] = m;
-  exp_avg_sq[idx] = v;
-  theta[idx] = p;
+  const float p = upd_clip_adam(idx, theta, exp_avg, exp_avg_sq, grads, sumsq, 8, max_norm, step_size, bc2_sqrt,
+                                one_minus_beta1, beta2, one_minus_beta2, eps);
   if (packed != nullptr && idx < P - H - 1) {
     const int w0 = H * GW_O;
     packed[idx < w0 ? (idx / GW_O) * GW_IN_STRIDE + idx % GW_O : idx + H * (GW_IN_STRIDE - GW_O)] = p;
