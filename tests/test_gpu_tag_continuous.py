@@ -28,6 +28,8 @@ STATE = (("loc_x", "loc_x"), ("loc_y", "loc_y"), ("speed", "speed"), ("direction
 
 
 from tests.hip_harness import NEAR_TIE_TOTALS as _TOTALS  # noqa: E402
+from tests.tick_range_cases import (FUSED_SWEEP_CASES, TICK_ON_GIVEN_ACTIONS_SWEEP, fused_tick_sweep_case,  # noqa: E402
+                                    random_configuration, sweep_probabilities)
 
 
 def _mk(cfg, E):
@@ -256,8 +258,27 @@ def test_fused_tick_kernel(full_obs, acc_levels, turn_levels, runners, K, E):
     """HipTagContinuousTick: sampling + step + in-kernel reset in ONE launch.  The actions it
     sampled are pulled back and replayed through the oracle; finished replicas must already
     be reset when the launch returns while `_done_` still reports them for the trainer."""
+    n_taggers = 5 if (full_obs and runners == 60) else 4   # 65 agents -> 64 neighbour slots
+    cfg = dict(num_taggers=n_taggers, num_runners=runners, grid_length=6.0, episode_length=11, seed=5, max_speed=0.6,
+               max_acceleration=0.3, min_acceleration=-0.3, num_acceleration_levels=acc_levels,
+               num_turn_levels=turn_levels, use_full_observation=full_obs, num_other_agents_observed=K,
+               tagging_distance=0.12, edge_hit_penalty=-0.2, step_reward_for_runner=0.01,
+               runner_exits_game_after_tagged=True)
+    rng = np.random.RandomState(0)
+    N = n_taggers + runners
+    probs_host = [rng.dirichlet(np.ones(a), size=(E, N)).astype(np.float32) for a in (acc_levels + 1, turn_levels + 1)]
+    _, finished_total, near_tie = _fused_tick_vs_oracle(cfg, E, probs_host, ticks=40)
+    assert finished_total >= 2 * E and near_tie <= 1
+
+
+def _fused_tick_vs_oracle(cfg, E, probs_host, ticks):
+    """`ticks` launches of the fused tick with the policies `probs_host` ([E, N, n_actions] float32 per head), every tick
+    against the oracle: the draws restated on the host from the RNG words and compared index for index, rewards, `_done_`,
+    the nine state arrays and the reset observation bit for bit, `nearest_neighbor_ids`; an observation row of a live
+    replica that differs must classify as a near-tie (module docstring; none with full observations) and is counted.
+    Returns (restarts per replica, finished replicas in all, near-tie rows)."""
     import torch
-    from tests.hip_harness import OBS, REW, make_wrapper, pull, require_gpu
+    from tests.hip_harness import OBS, REW, pull, require_gpu
     from warp_drive_amd.envs.tag_continuous import TagContinuous
     from warp_drive_amd.managers.function_manager import HIPSampler
     from warp_drive_amd.rollout import RolloutEngine
@@ -265,35 +286,30 @@ def test_fused_tick_kernel(full_obs, acc_levels, turn_levels, runners, K, E):
     from warp_drive_amd.env_wrapper import EnvWrapper
 
     require_gpu()
-    n_taggers = 5 if (full_obs and runners == 60) else 4   # 65 agents -> 64 neighbour slots
-    cfg = dict(num_taggers=n_taggers, num_runners=runners, grid_length=6.0, episode_length=11, seed=5, max_speed=0.6,
-               max_acceleration=0.3, min_acceleration=-0.3, num_acceleration_levels=acc_levels,
-               num_turn_levels=turn_levels, use_full_observation=full_obs, num_other_agents_observed=K,
-               tagging_distance=0.12, edge_hit_penalty=-0.2, step_reward_for_runner=0.01,
-               runner_exits_game_after_tagged=True)
-    na, nt = acc_levels + 1, turn_levels + 1
+    full_obs, K = cfg["use_full_observation"], cfg["num_other_agents_observed"]
+    na, nt = cfg["num_acceleration_levels"] + 1, cfg["num_turn_levels"] + 1
     w = EnvWrapper(env_obj=TagContinuous(**cfg), num_envs=E, env_backend="hip")
     w.reset_all_envs()
     sampler = HIPSampler(w.cuda_function_manager)
     sampler.init_random(seed=11)
     create_and_push_data_placeholders(env_wrapper=w, action_sampler=sampler, training_batch_size_per_env=None,
                                       push_data_batch_placeholders=False)
-    rng = np.random.RandomState(0)
     N = w.n_agents
-    probs = [torch.from_numpy(rng.dirichlet(np.ones(a), size=(E, N)).astype(np.float32)).cuda() for a in (na, nt)]
+    assert [tuple(p.shape) for p in probs_host] == [(E, N, na), (E, N, nt)]
+    probs = [torch.from_numpy(p).cuda() for p in probs_host]
     engine = RolloutEngine(w, sampler, probabilities=probs)
     assert engine.fused and engine.step_kernel_name.startswith("HipTagContinuousTick")
     orc = TagContinuousOracle(num_envs=E, **cfg)
     stats = {"near_tie_rows": 0, "rows": 0}
     counts = [np.zeros(na), np.zeros(nt)]
     finished_total = 0
+    restarts = np.zeros(E, dtype=np.int64)
     from oracle.core_np import fused_tick_uniforms, sample_actions_counting
     from warp_drive_amd.managers import hip_driver as drv
     from warp_drive_amd.managers.function_manager import _stream_tag
 
     rng_words = np.zeros(4 + E * N, dtype=np.uint32)
-    probs_host = [p.cpu().numpy() for p in probs]
-    for t in range(40):
+    for t in range(ticks):
         drv.memcpy_dtoh(rng_words, sampler.rng_state)
         torch.cuda.synchronize()
         assert (rng_words[4:] == t).all()  # one epoch per tick and agent row
@@ -312,6 +328,7 @@ def test_fused_tick_kernel(full_obs, acc_levels, turn_levels, runners, K, E):
         np.testing.assert_array_equal(pull(w, "_done_"), orc.done, err_msg=f"done t={t}")  # still set
         fin = orc.done > 0
         finished_total += int(fin.sum())
+        restarts += fin
         obs_before_reset = orc.obs.astype(np.float32).copy()
         ids_ref = None if full_obs else orc.nearest_ids.copy()
         in_game = obs_before_reset[..., -1] != 0   # time column: set for agents in the game at observation time
@@ -325,11 +342,42 @@ def test_fused_tick_kernel(full_obs, acc_levels, turn_levels, runners, K, E):
         live = ~fin
         if not np.array_equal(obs_dev[live], obs_before_reset[live]):
             assert not full_obs
-            stats["near_tie_rows"] += int((obs_dev[live] != obs_before_reset[live]).any(axis=2).sum())
-    assert finished_total >= 2 * E and stats["near_tie_rows"] <= 1
-    for c, p in zip(counts, probs):
-        expected = p.cpu().numpy().reshape(-1, c.size).sum(0) * 40
+            bad = np.argwhere(((obs_dev != obs_before_reset).any(axis=2)) & live[:, None])
+            assert _near_tie_rows(orc, bad), f"obs mismatch that is not a near-tie t={t}: {bad[:5]}"
+            stats["near_tie_rows"] += len(bad)
+        stats["rows"] += E * N
+    _TOTALS["near_tie_rows"] += stats["near_tie_rows"]
+    _TOTALS["rows"] += stats["rows"]
+    for c, p in zip(counts, probs_host):
+        expected = p.reshape(-1, c.size).sum(0) * ticks
         assert np.abs(c - expected).max() < 6 * np.sqrt(expected.max())
+    return restarts, finished_total, stats["near_tie_rows"]
+
+
+@pytest.mark.parametrize("case", range(FUSED_SWEEP_CASES))
+def test_fused_tick_random_configurations(case):
+    """The fused Tick entry (slab fetch into LDS, both heads sampled in the kernel, finished replicas restored in the
+    kernel) on the seeded shapes of tests/tick_range_cases.py: test_random_configurations' generator plus the two head
+    sizes -- both sides of WD_SLAB_CH = 24, above the 64-entry action table, unequal either way -- with the checks of
+    test_fused_tick_kernel.  Dirichlet policies; in every replica one agent row of each head is one-hot and one has
+    exact zeros in front of and behind its mass (the end cases of the inverse CDF inside the kernel).  2 * episode + 3
+    ticks: every replica restarts at least twice.  Mismatch allowance: the suite's rule (near-ties of <= 2 ulp, at most
+    2 rows per case, none with full observations)."""
+    cfg, E, heads = fused_tick_sweep_case(case)
+    N = cfg["num_taggers"] + cfg["num_runners"]
+    rng = np.random.RandomState(7000 + case)
+    probs_host = [sweep_probabilities(rng, E, N, a) for a in heads]
+    restarts, _, near_tie = _fused_tick_vs_oracle(cfg, E, probs_host, ticks=2 * cfg["episode_length"] + 3)
+    assert restarts.min() >= 2, restarts
+    assert near_tie <= 2, near_tie
+
+
+@pytest.mark.parametrize("case", TICK_ON_GIVEN_ACTIONS_SWEEP)
+def test_tick_on_given_actions_random_configurations(case):
+    """the TickA entry (step + restore on actions that are already in `sampled_actions`) against the sampling tick on the
+    partial-observation shapes of the sweep that have one: same actions, same arrays, bit for bit, through two restarts"""
+    cfg, E, _ = fused_tick_sweep_case(case)
+    _tick_on_given_actions_vs_sampling_tick(cfg, E, ticks=2 * cfg["episode_length"] + 3)
 
 
 def _near_tie_rows_c(orc, bad_rows):
@@ -839,25 +887,8 @@ def test_many_agents_paths(n_runners, K, full_obs):
 def test_random_configurations(case):
     """seeded random shapes and reward settings: agent counts around the wavefront / block boundaries,
     K from 1 to N-1, both observation modes, both exit rules, replica counts that do not fill a block"""
-    rng = np.random.RandomState(1000 + case)
-    n_taggers = int(rng.randint(1, 7))
-    n_runners = int(rng.choice([1, 2, 5, 30, 58, 59, 60, 63, 64, 65, 100, 123, 124, 127, 130]))
-    N = n_taggers + n_runners
-    full = bool(rng.randint(0, 2)) and N <= 70
-    K = int(rng.randint(1, min(N - 1, 33) + 1)) if N > 2 else 1
-    cfg = dict(num_taggers=n_taggers, num_runners=n_runners, grid_length=float(rng.choice([2.0, 7.5, 20.0])),
-               episode_length=int(rng.randint(3, 12)), seed=int(rng.randint(1, 10 ** 6)),
-               max_speed=float(rng.choice([0.5, 1.0, 2.5])), max_acceleration=0.25, min_acceleration=-0.25,
-               max_turn=float(rng.choice([0.8, 2.356])), min_turn=-float(rng.choice([0.8, 2.356])),
-               num_acceleration_levels=int(rng.randint(1, 9)), num_turn_levels=int(rng.randint(1, 9)),
-               skill_level_runner=float(rng.choice([0.7, 1.0])), skill_level_tagger=float(rng.choice([0.9, 1.0, 1.3])),
-               use_full_observation=full, num_other_agents_observed=K,
-               tagging_distance=float(rng.choice([0.02, 0.3, 1.0])), tag_reward_for_tagger=float(rng.choice([1.0, 10.0])),
-               tag_penalty_for_runner=-float(rng.choice([1.0, 10.0])), step_penalty_for_tagger=-float(rng.choice([0.0, 0.01])),
-               step_reward_for_runner=float(rng.choice([0.0, 0.01])), edge_hit_penalty=-float(rng.choice([0.0, 0.5])),
-               end_of_game_reward_for_runner=float(rng.choice([0.0, 1.0])),
-               runner_exits_game_after_tagged=bool(rng.randint(0, 2)))
-    _run_lockstep(cfg, E=int(rng.choice([1, 2, 3, 7, 33])), ticks=14, seed=case)
+    cfg, E = random_configuration(np.random.RandomState(1000 + case))
+    _run_lockstep(cfg, E=E, ticks=14, seed=case)
 
 
 def test_rollout_falls_back_when_the_tick_does_not_fit_lds():
@@ -928,6 +959,17 @@ def test_tick_on_given_actions_equals_the_sampling_tick(runners, K, levels, E, e
     """`TickA` entries (step + restore of finished replicas on actions that are ALREADY in `sampled_actions`: the policy
     forward's epilogue draws them, training/policy_kernel.py) against the sampling tick: the same actions give the same
     arrays, bit for bit, through a whole episode and the restarts."""
+    cfg = dict(num_taggers=5, num_runners=runners, grid_length=8.0, episode_length=30, seed=3, max_speed=0.5,
+               max_acceleration=0.2, min_acceleration=-0.2, num_acceleration_levels=levels, num_turn_levels=levels,
+               use_full_observation=False, num_other_agents_observed=K, tagging_distance=0.15, edge_hit_penalty=-0.1,
+               runner_exits_game_after_tagged=True)
+    _tick_on_given_actions_vs_sampling_tick(cfg, E, ticks=70, entry=entry)
+
+
+def _tick_on_given_actions_vs_sampling_tick(cfg, E, ticks, entry=None):
+    """two engines with the same seeds, one sampling (`Tick`), one on the first one's actions (`TickA`): every array
+    equal after every tick; every replica must restart at least twice.  entry: the TickA entry the shape must resolve
+    to (None: any, it must only be the sampling entry's twin)."""
     import torch
     from tests.hip_harness import ACT, OBS, REW, pull, require_gpu
     from warp_drive_amd.env_wrapper import EnvWrapper
@@ -937,10 +979,6 @@ def test_tick_on_given_actions_equals_the_sampling_tick(runners, K, levels, E, e
     from warp_drive_amd.training.data_loader import create_and_push_data_placeholders
 
     require_gpu()
-    cfg = dict(num_taggers=5, num_runners=runners, grid_length=8.0, episode_length=30, seed=3, max_speed=0.5,
-               max_acceleration=0.2, min_acceleration=-0.2, num_acceleration_levels=levels, num_turn_levels=levels,
-               use_full_observation=False, num_other_agents_observed=K, tagging_distance=0.15, edge_hit_penalty=-0.1,
-               runner_exits_game_after_tagged=True)
 
     def make(presampled):
         w = EnvWrapper(env_obj=TagContinuous(**cfg), num_envs=E, env_backend="hip")
@@ -952,12 +990,14 @@ def test_tick_on_given_actions_equals_the_sampling_tick(runners, K, levels, E, e
         return w, RolloutEngine(w, sampler, probabilities=None, presampled_actions=presampled)
 
     (wa, ea), (wb, eb) = make(False), make(True)
-    assert eb.step_kernel_name == entry and ea.step_kernel_name == entry.replace("TickA", "Tick")
+    assert entry is None or eb.step_kernel_name == entry
+    assert "TickA" in eb.step_kernel_name and ea.step_kernel_name == eb.step_kernel_name.replace("TickA", "Tick")
     act_a = wa.cuda_data_manager.data_on_device_via_torch(ACT)
     act_b = wb.cuda_data_manager.data_on_device_via_torch(ACT)
     names = [n for n, _ in STATE] + [OBS, REW, "_done_", "_timestep_", "nearest_neighbor_ids", "num_runners"]
     finished = 0
-    for t in range(70):
+    restarts = np.zeros(E, dtype=np.int64)
+    for t in range(ticks):
         ea.run(1)                 # draws its actions (uniform probabilities) and steps
         act_b.copy_(act_a)        # the same actions, given
         eb.run(1)
@@ -965,7 +1005,8 @@ def test_tick_on_given_actions_equals_the_sampling_tick(runners, K, levels, E, e
         for n in names:
             np.testing.assert_array_equal(pull(wb, n), pull(wa, n), err_msg=f"{n} t={t}")
         finished += int((pull(wa, "_done_") > 0).sum())
-    assert finished >= 2 * E
+        restarts += pull(wa, "_done_") > 0
+    assert finished >= 2 * E and restarts.min() >= 2, restarts
 
 
 def test_shape_entries_built_on_demand(monkeypatch):

@@ -48,8 +48,10 @@ COHORT_ALIGN = 32  # cohort boundaries at multiples of 32 replicas: 32 rows of 4
 
 def cohort_bounds(n_envs, cohorts):
     """replica ranges [(begin, end), ...] of `cohorts` near-equal cohorts whose inner boundaries are multiples of
-    COHORT_ALIGN replicas"""
-    cuts = [0] + [int(round(n_envs * c / cohorts / COHORT_ALIGN)) * COHORT_ALIGN for c in range(1, cohorts)] + [n_envs]
+    COHORT_ALIGN replicas (never beyond n_envs: with few replicas the last cohorts are empty)"""
+    last = n_envs // COHORT_ALIGN * COHORT_ALIGN
+    cuts = [0] + [min(int(round(n_envs * c / cohorts / COHORT_ALIGN)) * COHORT_ALIGN, last)
+                  for c in range(1, cohorts)] + [n_envs]
     return list(zip(cuts[:-1], cuts[1:]))
 
 
