@@ -184,6 +184,49 @@ def test_n5_lds_formulas_match_the_kernel_layout():
         assert (12 * 105) % 4 == 0 and (12 * CD) % 4 == 0 and (12 * 105 + 12 * CD + 64) % 4 == 0   # s_pol stays 16-byte aligned
 
 
+def test_the_rollout_units_share_one_policy_header_and_its_float_counts():
+    """the five units with an in-kernel policy are built around csrc/kernels/rollout_policy.h, and its float counts --
+    restated here, next to the header's own expressions -- are what the host sizes the launches' LDS with"""
+    import os
+
+    from warp_drive_amd import build as wd_build
+    from warp_drive_amd.envs.cartpole import CUDAClassicControlCartPoleEnv
+    from warp_drive_amd.envs.classic_control import rollout_actor_floats
+    from warp_drive_amd.envs.tag_gridworld import gridworld_policy_floats
+
+    header = os.path.join(wd_build.KDIR, "rollout_policy.h")
+    for unit in ("wd_kernels.hip", "cartpole_pool.hip", "classic_control.hip", "tag_gridworld_n5.hip",
+                 "tag_gridworld_n5_pool.hip"):
+        assert header in wd_build.unit_sources(unit), unit
+    text = open(header).read()
+    for expression in ("rp_pad4(int n) { return (n + 3) & ~3; }",
+                       "rp_policy_floats(int I, int H, int A) { return I * H + H + H * H + H + A * H + A; }",
+                       "rp_actor_op(int O) { return (O + 1) & ~1; }",
+                       "rp_actor_floats(int H, int O) { return rp_actor_op(O) * H + H + H * H + H + H + 1; }"):
+        assert expression in text, expression
+    common = open(os.path.join(wd_build.KDIR, "tag_gridworld_n5_common.h")).read()
+    assert "return rp_pad4(rp_policy_floats(GW5_IN_STRIDE, H, GW5_ACTIONS));" in common
+    assert "GW5_IN_STRIDE = 24;" in common and "GW5_ACTIONS = 5;" in common
+
+    def rp_pad4(n):
+        return (n + 3) & ~3
+
+    def rp_policy_floats(I, H, A):
+        return I * H + H + H * H + H + A * H + A
+
+    def rp_actor_floats(H, O):
+        return ((O + 1) & ~1) * H + H + H * H + H + H + 1
+
+    for H in (32, 64):
+        assert gridworld_policy_floats(H) == rp_pad4(rp_policy_floats(24, H, 5))
+        for O in (2, 3, 4, 6):
+            assert rollout_actor_floats(O, H) == rp_actor_floats(H, O)
+        for A in (1, 2, 3, 5, 8):
+            policy_bytes = CUDAClassicControlCartPoleEnv.pool_rollout_lds_bytes(H, A, 0, False)
+            assert policy_bytes == 4 * rp_pad4(rp_policy_floats(4, H, A))
+            assert CUDAClassicControlCartPoleEnv.pool_rollout_lds_bytes(H, A, 7, True) == policy_bytes + 16 * 7
+
+
 def test_live_policy_rollout_has_one_lds_limit():
     """has_live_policy_rollout admits a shape only if its launch fits ROLLOUT_POLICY_MAX_LDS (the time table grows with
     the episode length); H = 64 passes 64 KiB at episode_length 1504 and needs 75 904 bytes at 4095"""

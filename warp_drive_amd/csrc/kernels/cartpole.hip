@@ -36,10 +36,10 @@ __device__ __forceinline__ void cp_tick_impl(float *cp_weights,
     const float *policy, int hidden, int invariant_divide_ok) {
   const CpPhysics p{gravity, masspole, total_mass, length, polemass_length, force_mag, tau,
                     theta_threshold_radians, x_threshold, 1.0f / total_mass};
-  const CpResetEntry *table = (const CpResetEntry *)reset_table;
+  const wd_reset_entry *table = (const wd_reset_entry *)reset_table;
   const uint32_t k0 = rng_state[0], k1 = rng_state[1];
   if (H > 0) {
-    const int n_w = 4 * H + H + H * H + H + n_actions * H + n_actions;
+    const int n_w = rp_policy_floats(4, H, n_actions);
     for (int i = threadIdx.x; i < n_w; i += blockDim.x) cp_weights[i] = policy[i];
     __syncthreads();
   }
@@ -58,7 +58,7 @@ __device__ __forceinline__ void cp_tick_impl(float *cp_weights,
     // wavefront finishes on nearly every tick; the restore used to LOAD the registered rows inside the tick loop
     // (and reload the state): 12 loads per tick and wavefront, each waiting for every store issued before it (the
     // memory counters return in order) -- 70 % of the wavefronts' cycles were waits (profiles/r04_pmc_mix_cartpole_T50.txt).
-    CpResetEntry ent0 = CpResetEntry{nullptr, nullptr, 0, 0}, ent1 = ent0;
+    wd_reset_entry ent0 = wd_reset_entry{nullptr, nullptr, 0, 0}, ent1 = ent0;
     uint4 row0 = make_uint4(0u, 0u, 0u, 0u), row1 = row0;
     bool cached = (n_reset_arrays >= 1) && (n_reset_arrays <= 2);
     if (cached) {
@@ -166,7 +166,7 @@ __device__ __forceinline__ void cp_tick_impl(float *cp_weights,
         } else {
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the untracked stores above have left
           for (int r = 0; r < n_reset_arrays; ++r) {
-            const CpResetEntry ent = table[r];
+            const wd_reset_entry ent = table[r];
             const long base = (long)env * ent.row_elems;
             for (int i = 0; i < ent.row_elems; ++i) ent.data[base + i] = ent.ref[base + i];
           }
@@ -196,59 +196,8 @@ __device__ __forceinline__ void cp_tick_impl(float *cp_weights,
 }
 
 // ---- evaluation: ONE episode of every replica in one launch (the ...EnvEvaluate_H<H> entries), greedy or sampled; the
-// Cartpole counterpart of classic_control.hip::cc_evaluate_impl.  cp_policy_probs is cp_policy_cum up to and including
-// the division -- the same loads, fmaf chains and softmax -- and returns the probabilities p[a] = e[a] / sum themselves
-// (oracle/cartpole_np.py::policy_probabilities), which the greedy scan needs; the sampled draw forms cp_policy_cum's
-// running sums from them with the same two expressions.
-template <int H>
-__device__ __forceinline__ void cp_policy_probs(const float *w, const float4 &s, int n_actions,
-                                                float (&prob)[CP_MAX_REG_ACTIONS]) {
-  const float *W0 = w, *b0 = W0 + 4 * H, *W1 = b0 + H, *b1 = W1 + H * H, *Wp = b1 + H, *bp = Wp + n_actions * H;
-  float h1[H], h2[H];
-#pragma unroll
-  for (int i = 0; i < H; ++i) {
-    const float4 wr = *(const float4 *)(W0 + 4 * i);
-    float acc = b0[i];
-    acc = fmaf(wr.x, s.x, acc); acc = fmaf(wr.y, s.y, acc); acc = fmaf(wr.z, s.z, acc); acc = fmaf(wr.w, s.w, acc);
-    h1[i] = fmaxf(acc, 0.0f);
-  }
-#pragma unroll
-  for (int i = 0; i < H; ++i) {
-    float acc = b1[i];
-#pragma unroll
-    for (int j = 0; j < H; j += 4) {
-      const float4 wr = *(const float4 *)(W1 + i * H + j);
-      acc = fmaf(wr.x, h1[j], acc); acc = fmaf(wr.y, h1[j + 1], acc);
-      acc = fmaf(wr.z, h1[j + 2], acc); acc = fmaf(wr.w, h1[j + 3], acc);
-    }
-    h2[i] = fmaxf(acc, 0.0f);
-  }
-  float logit[CP_MAX_REG_ACTIONS], m = -__builtin_inff();
-#pragma unroll
-  for (int a = 0; a < CP_MAX_REG_ACTIONS; ++a) {
-    logit[a] = -__builtin_inff();
-    if (a < n_actions) {
-      float acc = bp[a];
-#pragma unroll
-      for (int j = 0; j < H; j += 4) {
-        const float4 wr = *(const float4 *)(Wp + a * H + j);
-        acc = fmaf(wr.x, h2[j], acc); acc = fmaf(wr.y, h2[j + 1], acc);
-        acc = fmaf(wr.z, h2[j + 2], acc); acc = fmaf(wr.w, h2[j + 3], acc);
-      }
-      logit[a] = acc;
-      m = fmaxf(m, acc);
-    }
-  }
-  float e[CP_MAX_REG_ACTIONS], sum = 0.0f;
-#pragma unroll
-  for (int a = 0; a < CP_MAX_REG_ACTIONS; ++a) {
-    e[a] = (a < n_actions) ? expf(logit[a] - m) : 0.0f;
-    sum += e[a];
-  }
-#pragma unroll
-  for (int a = 0; a < CP_MAX_REG_ACTIONS; ++a) prob[a] = e[a] / sum;
-}
-
+// Cartpole counterpart of classic_control.hip::cc_evaluate_impl.  The greedy scan reads cp_policy_probs, the sampled
+// draw counts on the running sums formed from the same probabilities (cartpole_common.h, rollout_policy.h).
 // One lane per replica: the state (= the observation the network reads, as in cp_tick_impl) and the timestep are loaded
 // once, then at most `ticks` ticks of (network -> action -> cp_euler<false>), stopping at the first finished tick; the
 // terminal tick counts (sum += 1, steps += 1 before the test).  use_argmax: the first maximum of the probabilities
@@ -264,7 +213,7 @@ __device__ __forceinline__ void cp_evaluate_impl(float *cp_weights, const float4
                                                  float *eval_reward_sum, int *eval_steps, int *eval_done,
                                                  int *action_trace) {
   if (hidden != H || n_actions < 1 || n_actions > CP_MAX_REG_ACTIONS || policy == nullptr) return;  // (uniform)
-  const int n_w = 4 * H + H + H * H + H + n_actions * H + n_actions;
+  const int n_w = rp_policy_floats(4, H, n_actions);
   for (int i = threadIdx.x; i < n_w; i += blockDim.x) cp_weights[i] = policy[i];
   __syncthreads();
   const uint32_t k0 = rng_state[0], k1 = rng_state[1];
@@ -285,13 +234,7 @@ __device__ __forceinline__ void cp_evaluate_impl(float *cp_weights, const float4
       cp_policy_probs<H>(cp_weights, s, n_actions, prob);
       int a = 0;
       if (greedy) {
-        float best = prob[0];
-#pragma unroll
-        for (int i = 1; i < CP_MAX_REG_ACTIONS; ++i) {
-          const bool better = i < n_actions && best < prob[i];
-          best = better ? prob[i] : best;
-          a = better ? i : a;
-        }
+        a = rp_first_maximum(prob, n_actions);
       } else {
         const float u = wd_u01_open_closed(wd_tick_draw((uint32_t)env, epoch0 + (uint32_t)k, (uint32_t)stream_tag, k0, k1,
                                                         blk, blk_quad));

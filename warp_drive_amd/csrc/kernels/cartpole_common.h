@@ -1,10 +1,11 @@
 // cartpole_common.h -- what the two Cartpole code paths share: the Euler step (cp_euler), the in-kernel policy's running
-// sums (cp_policy_cum), the reset table's entry and the untracked stores through a scalar base.  Included by cartpole.hip
+// sums (cp_policy_cum, around rollout_policy.h) and the untracked stores through a scalar base.  Included by cartpole.hip
 // (the main code object: Step, Tick, Rollout_H<H>, Evaluate_H<H>, the two Verify entries) and by cartpole_pool.hip
 // (wd_kernels_cp_pool.hsaco: the T-tick rollout whose finished replicas restart from a reset pool).  A change here
 // changes both objects: compare the main object's disassembly as profiles/r26_cartpole_asm_diff.txt did.
 #pragma once
 #include "wd_common.h"
+#include "rollout_policy.h"
 
 namespace {
 
@@ -89,54 +90,29 @@ __device__ __forceinline__ bool cp_euler(float4 &s, int action, const CpPhysics 
          theta > p.theta_threshold_radians;
 }
 
-// ---- a small policy INSIDE the rollout kernel: two hidden layers of H units + one softmax head, the
-// weights in LDS (every lane reads the same address: broadcast), the activations in registers.
-// Packed weights (training/policy_kernel.py::pack_rollout_policy): W0 [H][4], b0 [H], W1 [H][H], b1 [H],
-// Wp [A][H], bp [A], all float32.  Arithmetic: acc = bias, then fmaf over the inputs in index order;
-// softmax with the maximum subtracted, expf, one division per action; restated in
-// oracle/cartpole_np.py::policy_probabilities.  Returns the running float32 sums of the probabilities
-// (what the inverse-CDF sampler compares the uniform with, random.cu:51-85).
+// ---- the policy INSIDE the rollout and evaluation kernels: rollout_policy.h (the network, the parity contract and the
+// packed layout, pack_rollout_policy with I = 4) behind the float4 first layer; restated on the host in
+// oracle/cartpole_np.py::policy_probabilities.  cp_policy_probs: the probabilities e[a] / sum (what the greedy scan
+// needs); cp_policy_cum: their running float32 sums (what the inverse-CDF sampler compares the uniform with).
 constexpr int CP_MAX_REG_ACTIONS = 8;
 
 template <int H>
+__device__ __forceinline__ void cp_policy_probs(const float *w, const float4 &s, int n_actions,
+                                                float (&prob)[CP_MAX_REG_ACTIONS]) {
+  float h1[H], logit[CP_MAX_REG_ACTIONS];
+  rp_first_layer<H>(w, w + 4 * H, s, h1);
+  const float m = rp_policy_logits<H>(w + 4 * H + H, h1, n_actions, logit);
+  rp_softmax_probs(logit, m, n_actions, prob);
+}
+
+// (the softmax's terms and divisions stand here next to the running sums: behind a call the rollout entries compile to
+// another schedule; rollout_policy.h::rp_softmax_probs is the same statements)
+template <int H>
 __device__ __forceinline__ void cp_policy_cum(const float *w, const float4 &s, int n_actions,
                                               float (&cumv)[CP_MAX_REG_ACTIONS]) {
-  const float *W0 = w, *b0 = W0 + 4 * H, *W1 = b0 + H, *b1 = W1 + H * H, *Wp = b1 + H, *bp = Wp + n_actions * H;
-  float h1[H], h2[H];
-#pragma unroll
-  for (int i = 0; i < H; ++i) {
-    const float4 wr = *(const float4 *)(W0 + 4 * i);
-    float acc = b0[i];
-    acc = fmaf(wr.x, s.x, acc); acc = fmaf(wr.y, s.y, acc); acc = fmaf(wr.z, s.z, acc); acc = fmaf(wr.w, s.w, acc);
-    h1[i] = fmaxf(acc, 0.0f);
-  }
-#pragma unroll
-  for (int i = 0; i < H; ++i) {
-    float acc = b1[i];
-#pragma unroll
-    for (int j = 0; j < H; j += 4) {
-      const float4 wr = *(const float4 *)(W1 + i * H + j);
-      acc = fmaf(wr.x, h1[j], acc); acc = fmaf(wr.y, h1[j + 1], acc);
-      acc = fmaf(wr.z, h1[j + 2], acc); acc = fmaf(wr.w, h1[j + 3], acc);
-    }
-    h2[i] = fmaxf(acc, 0.0f);
-  }
-  float logit[CP_MAX_REG_ACTIONS], m = -__builtin_inff();
-#pragma unroll
-  for (int a = 0; a < CP_MAX_REG_ACTIONS; ++a) {
-    logit[a] = -__builtin_inff();
-    if (a < n_actions) {
-      float acc = bp[a];
-#pragma unroll
-      for (int j = 0; j < H; j += 4) {
-        const float4 wr = *(const float4 *)(Wp + a * H + j);
-        acc = fmaf(wr.x, h2[j], acc); acc = fmaf(wr.y, h2[j + 1], acc);
-        acc = fmaf(wr.z, h2[j + 2], acc); acc = fmaf(wr.w, h2[j + 3], acc);
-      }
-      logit[a] = acc;
-      m = fmaxf(m, acc);
-    }
-  }
+  float h1[H], logit[CP_MAX_REG_ACTIONS];
+  rp_first_layer<H>(w, w + 4 * H, s, h1);
+  const float m = rp_policy_logits<H>(w + 4 * H + H, h1, n_actions, logit);
   float e[CP_MAX_REG_ACTIONS], sum = 0.0f;
 #pragma unroll
   for (int a = 0; a < CP_MAX_REG_ACTIONS; ++a) {
@@ -151,13 +127,6 @@ __device__ __forceinline__ void cp_policy_cum(const float *w, const float4 &s, i
     cumv[a] = cum;
   }
 }
-
-struct CpResetEntry {  // same layout as wd_reset_entry in wd_core.hip
-  wd_global_u32 *data;
-  const wd_global_u32 *ref;
-  int row_elems;
-  int pad_;
-};
 
 // Fused rollout tick(s): sample the action + step + reset a finished replica, `ticks` times per launch
 // with the state kept in registers (a single tick at E = 100 000 moves 6.8 MB: under 1 us of HBM time,

@@ -55,11 +55,11 @@ __device__ __forceinline__ void cp_pool_rollout(float *lds,
   if (hidden != H || n_actions < 1 || n_actions > CP_MAX_REG_ACTIONS || (H > 0 && policy == nullptr) || ticks < 1 ||
       pa.n_pool < 1 || pa.pool == nullptr || pa.pool_rng == nullptr || n_reset_arrays != 1 || reset_table == nullptr)
     return;
-  const CpResetEntry ent = *(const CpResetEntry *)reset_table;
+  const wd_reset_entry ent = *(const wd_reset_entry *)reset_table;
   if ((size_t)ent.data != (size_t)observation_arr || ent.row_elems != 4) return;
   const int n_pool = pa.n_pool;
   const bool staged = pa.pool_in_lds != 0;
-  const int n_w = (H > 0) ? 4 * H + H + H * H + H + n_actions * H + n_actions : 0;
+  const int n_w = (H > 0) ? rp_policy_floats(4, H, n_actions) : 0;
   float *cp_weights = lds;
   float4 *pool_lds = (float4 *)(lds + ((n_w + 3) & ~3));
   const float4 *pool4 = (const float4 *)pa.pool;

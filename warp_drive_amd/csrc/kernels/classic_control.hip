@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "wd_common.h"
+#include "rollout_policy.h"
 
 namespace {
 
@@ -251,13 +252,6 @@ __device__ __forceinline__ void cc_step_impl(const Env &e, float *state_arr, con
   }
 }
 
-struct CcResetEntry {  // same layout as wd_reset_entry in wd_core.hip
-  wd_global_u32 *data;
-  const wd_global_u32 *ref;
-  int row_elems;
-  int pad_;
-};
-
 // the arguments every fused tick takes after its env's step arguments
 struct CcTickArgs {
   float *state_arr;
@@ -285,19 +279,19 @@ struct CcTickArgs {
 
 constexpr int CC_MAX_ACTIONS = 8;
 
-// ---- a small policy INSIDE the tick (the arithmetic of cartpole.hip::cp_policy_cum, for an observation of O floats):
-// two hidden layers of H ReLU units + one softmax head, the weights in LDS (every lane reads the same address:
-// broadcast), the activations in registers.  Packed weights (training/policy_kernel.py::pack_rollout_policy): W0 [H][O],
-// b0 [H], W1 [H][H], b1 [H], Wp [A][H], bp [A], all float32.  acc = bias, then one fmaf per input in index order; softmax
-// with the maximum subtracted, expf, one division per action, the sum in action order; restated on the host in
-// tests/classic_control_policy.py::policy_probabilities.  Returns the running float32 sums of the probabilities.
-// The activations (2 H registers) and the float64 temporaries of the env's step are live in different phases of a tick.
+// ---- the policy INSIDE the tick and the evaluation: rollout_policy.h (the network, the parity contract and the packed
+// layout, pack_rollout_policy with I = O) behind the float2-row first layer; restated on the host in
+// tests/classic_control_policy.py::policy_probabilities.  cc_policy_probs: the probabilities e[a] / sum (what the greedy
+// scan needs); cc_policy_cum: their running float32 sums.  The activations (2 H registers) and the float64 temporaries
+// of the env's step are live in different phases of a tick.
+// (the float2-row first layer stands in both functions: as a function of its own, here or in rollout_policy.h, the
+// rollout and evaluation entries' registers are numbered otherwise)
 template <int H, int O>
-__device__ __forceinline__ void cc_policy_cum(const float *w, const float (&o)[O], int n_actions,
-                                              float (&cumv)[CC_MAX_ACTIONS]) {
-  static_assert(O % 2 == 0 && H % 4 == 0, "the rows of W0 are read as float2, those of W1 and Wp as float4");
+__device__ __forceinline__ void cc_policy_probs(const float *w, const float (&o)[O], int n_actions,
+                                                float (&prob)[CC_MAX_ACTIONS]) {
+  static_assert(O % 2 == 0, "the rows of W0 are read as float2");
   const float *W0 = w, *b0 = W0 + O * H, *W1 = b0 + H, *b1 = W1 + H * H, *Wp = b1 + H, *bp = Wp + n_actions * H;
-  float h1[H], h2[H];
+  float h1[H], h2[H], logit[CC_MAX_ACTIONS];
 #pragma unroll
   for (int i = 0; i < H; ++i) {
     float acc = b0[i];
@@ -308,33 +302,31 @@ __device__ __forceinline__ void cc_policy_cum(const float *w, const float (&o)[O
     }
     h1[i] = fmaxf(acc, 0.0f);
   }
+  rp_second_layer<H>(W1, b1, h1, h2);
+  const float m = rp_logits<H>(Wp, bp, h2, n_actions, logit);
+  rp_softmax_probs(logit, m, n_actions, prob);
+}
+
+// (the softmax's terms and divisions stand here next to the running sums: behind a call the rollout entries compile to
+// another schedule; rollout_policy.h::rp_softmax_probs is the same statements)
+template <int H, int O>
+__device__ __forceinline__ void cc_policy_cum(const float *w, const float (&o)[O], int n_actions,
+                                              float (&cumv)[CC_MAX_ACTIONS]) {
+  static_assert(O % 2 == 0, "the rows of W0 are read as float2");
+  const float *W0 = w, *b0 = W0 + O * H, *W1 = b0 + H, *b1 = W1 + H * H, *Wp = b1 + H, *bp = Wp + n_actions * H;
+  float h1[H], h2[H], logit[CC_MAX_ACTIONS];
 #pragma unroll
   for (int i = 0; i < H; ++i) {
-    float acc = b1[i];
+    float acc = b0[i];
 #pragma unroll
-    for (int j = 0; j < H; j += 4) {
-      const float4 wr = *(const float4 *)(W1 + i * H + j);
-      acc = fmaf(wr.x, h1[j], acc); acc = fmaf(wr.y, h1[j + 1], acc);
-      acc = fmaf(wr.z, h1[j + 2], acc); acc = fmaf(wr.w, h1[j + 3], acc);
+    for (int j = 0; j < O; j += 2) {
+      const float2 wr = *(const float2 *)(W0 + O * i + j);
+      acc = fmaf(wr.x, o[j], acc); acc = fmaf(wr.y, o[j + 1], acc);
     }
-    h2[i] = fmaxf(acc, 0.0f);
+    h1[i] = fmaxf(acc, 0.0f);
   }
-  float logit[CC_MAX_ACTIONS], m = -__builtin_inff();
-#pragma unroll
-  for (int a = 0; a < CC_MAX_ACTIONS; ++a) {
-    logit[a] = -__builtin_inff();
-    if (a < n_actions) {  // (uniform)
-      float acc = bp[a];
-#pragma unroll
-      for (int j = 0; j < H; j += 4) {
-        const float4 wr = *(const float4 *)(Wp + a * H + j);
-        acc = fmaf(wr.x, h2[j], acc); acc = fmaf(wr.y, h2[j + 1], acc);
-        acc = fmaf(wr.z, h2[j + 2], acc); acc = fmaf(wr.w, h2[j + 3], acc);
-      }
-      logit[a] = acc;
-      m = fmaxf(m, acc);
-    }
-  }
+  rp_second_layer<H>(W1, b1, h1, h2);
+  const float m = rp_logits<H>(Wp, bp, h2, n_actions, logit);
   float e[CC_MAX_ACTIONS], sum = 0.0f;
 #pragma unroll
   for (int a = 0; a < CC_MAX_ACTIONS; ++a) {
@@ -350,60 +342,22 @@ __device__ __forceinline__ void cc_policy_cum(const float *w, const float (&o)[O
   }
 }
 
-// ---- a deterministic actor INSIDE the tick of the Box envs (DDPG): two hidden layers of H ReLU units + one linear output z,
-// mean = fmaf(action_scale, tanhf(z), action_bias).  cc_policy_cum's arithmetic (acc = bias, then one fmaf per input in
-// index order), the weights in LDS, the activations in registers.  Packed weights (training/policy_kernel.py::
-// pack_rollout_actor): W0 [H][OP], b0 [H], W1 [H][H], b1 [H], Wa [H], ba [1], all float32, OP = O rounded up to even (the
-// rows of W0 are read as float2): the pad column is zero and the lane's pad observation is 0, so the pad adds +0 exactly.
-// Restated on the host in tests/classic_control_actor.py::actor_mean_f32.
-constexpr int cc_actor_op(int O) { return (O + 1) & ~1; }
-constexpr int cc_actor_floats(int H, int O) { return cc_actor_op(O) * H + H + H * H + H + H + 1; }
+// ---- the deterministic actor INSIDE the tick and the evaluation of the Box envs (DDPG): rollout_policy.h behind the
+// padded first layer (pack_rollout_actor: rows of OP = O rounded up to even floats, the pad column zero), mean =
+// fmaf(action_scale, tanhf(z), action_bias); restated on the host in tests/classic_control_actor.py::actor_mean_f32.
+template <int H, int O>
+__device__ __forceinline__ float cc_actor_mean(const float *w, const float (&o)[O], float action_scale,
+                                               float action_bias) {
+  constexpr int OP = rp_actor_op(O);
+  float h1[H];
+  rp_first_layer_padded<H, O>(w, w + OP * H, o, h1);
+  return rp_actor_mean<H>(w + OP * H + H, h1, action_scale, action_bias);
+}
 
 struct CcActorArgs {
   float action_scale, action_bias;
   float *mean_batch;  // [T, E] or null: row k = the means of tick k
 };
-
-template <int H, int O>
-__device__ __forceinline__ float cc_actor_mean(const float *w, const float (&o)[O], float action_scale,
-                                               float action_bias) {
-  constexpr int OP = cc_actor_op(O);
-  static_assert(H % 4 == 0, "the rows of W1 and Wa are read as float4");
-  const float *W0 = w, *b0 = W0 + OP * H, *W1 = b0 + H, *b1 = W1 + H * H, *Wa = b1 + H, *ba = Wa + H;
-  float op[OP];
-#pragma unroll
-  for (int j = 0; j < OP; ++j) op[j] = (j < O) ? o[j < O ? j : 0] : 0.0f;
-  float h1[H], h2[H];
-#pragma unroll
-  for (int i = 0; i < H; ++i) {
-    float acc = b0[i];
-#pragma unroll
-    for (int j = 0; j < OP; j += 2) {
-      const float2 wr = *(const float2 *)(W0 + OP * i + j);
-      acc = fmaf(wr.x, op[j], acc); acc = fmaf(wr.y, op[j + 1], acc);
-    }
-    h1[i] = fmaxf(acc, 0.0f);
-  }
-#pragma unroll
-  for (int i = 0; i < H; ++i) {
-    float acc = b1[i];
-#pragma unroll
-    for (int j = 0; j < H; j += 4) {
-      const float4 wr = *(const float4 *)(W1 + i * H + j);
-      acc = fmaf(wr.x, h1[j], acc); acc = fmaf(wr.y, h1[j + 1], acc);
-      acc = fmaf(wr.z, h1[j + 2], acc); acc = fmaf(wr.w, h1[j + 3], acc);
-    }
-    h2[i] = fmaxf(acc, 0.0f);
-  }
-  float z = ba[0];
-#pragma unroll
-  for (int j = 0; j < H; j += 4) {
-    const float4 wr = *(const float4 *)(Wa + j);
-    z = fmaf(wr.x, h2[j], z); z = fmaf(wr.y, h2[j + 1], z);
-    z = fmaf(wr.z, h2[j + 2], z); z = fmaf(wr.w, h2[j + 3], z);
-  }
-  return fmaf(action_scale, tanhf(z), action_bias);
-}
 
 // Fused rollout tick(s) (the conventions of HipClassicControlCartPoleEnvTick): per tick, draw the action, step, and
 // restart a finished replica; the state, the observation and the timestep stay in registers.  Discrete envs draw
@@ -419,7 +373,7 @@ __device__ __forceinline__ float cc_actor_mean(const float *w, const float (&o)[
 // on the observation the lane holds (the one row k of `obs_batch` records) instead of reading `probs`.  The draw keeps
 // the fixed-probability tick's Philox counters.
 // H > 0 (Box envs, the ...EnvRollout_A<H> entries): a LIVE deterministic actor.  `weights` = dynamic LDS of
-// cc_actor_floats(H, O) floats, copied from the packed network `policy` once per launch; every tick sets `mean` to
+// rp_actor_floats(H, O) floats, copied from the packed network `policy` once per launch; every tick sets `mean` to
 // cc_actor_mean of the observation the lane holds instead of keeping the launch's one `probs[env]` (`probs` is not read),
 // and with `actor.mean_batch` records it in row k.  The OU draw, the step and the restart are the code below, unchanged.
 template <class Env, bool BATCH, int H = 0>
@@ -428,13 +382,13 @@ __device__ __forceinline__ void cc_tick_impl(const Env &e, const CcTickArgs &a, 
                                              const CcActorArgs &actor = CcActorArgs{1.0f, 0.0f, nullptr}) {
   constexpr bool ACTOR = H > 0 && Env::CONT;
   if constexpr (H > 0) {
-    const int n_w = ACTOR ? cc_actor_floats(H, Env::O) : Env::O * H + H + H * H + H + a.n_actions * H + a.n_actions;
+    const int n_w = ACTOR ? rp_actor_floats(H, Env::O) : rp_policy_floats(Env::O, H, a.n_actions);
     for (int i = threadIdx.x; i < n_w; i += blockDim.x) weights[i] = policy[i];
     __syncthreads();
   }
   using Act = typename std::conditional<Env::CONT, float, int>::type;
   constexpr int S = Env::S, O = Env::O;
-  const CcResetEntry *table = (const CcResetEntry *)a.reset_table;
+  const wd_reset_entry *table = (const wd_reset_entry *)a.reset_table;
   const uint32_t k0 = a.rng_state[0], k1 = a.rng_state[1];
   const uint32_t pk0 = a.pool ? a.pool_rng[0] : 0u, pk1 = a.pool ? a.pool_rng[1] : 0u;
   Act *action_arr = (Act *)a.action_arr;
@@ -509,7 +463,7 @@ __device__ __forceinline__ void cc_tick_impl(const Env &e, const CcTickArgs &a, 
       if (done) {
         t = 0;
         for (int r = 0; r < a.n_reset_arrays; ++r) {
-          const CcResetEntry ent = table[r];
+          const wd_reset_entry ent = table[r];
           const long base = (long)env * ent.row_elems;
           for (int i = 0; i < ent.row_elems; ++i) ent.data[base + i] = ent.ref[base + i];
           if ((size_t)ent.data == (size_t)a.state_arr && ent.row_elems == S) {
@@ -570,63 +524,6 @@ __device__ __forceinline__ void cc_rollout_actor(const Env &e, const CcTickArgs 
 }
 
 // ---- evaluation: ONE episode of every replica in one launch (the ...EnvEvaluate_H<H> entries), greedy or sampled.
-// cc_policy_probs is cc_policy_cum up to and including the division: the same loads, the same fmaf chains, the same
-// softmax (maximum subtracted, expf, the sum in action order, one division per action) -- it returns the probabilities
-// p[a] = e[a] / sum themselves (what tests/classic_control_policy.py::policy_probabilities restates), which the greedy
-// scan needs; the sampled draw forms cc_policy_cum's running sums from them with the same two expressions.
-template <int H, int O>
-__device__ __forceinline__ void cc_policy_probs(const float *w, const float (&o)[O], int n_actions,
-                                                float (&prob)[CC_MAX_ACTIONS]) {
-  static_assert(O % 2 == 0 && H % 4 == 0, "the rows of W0 are read as float2, those of W1 and Wp as float4");
-  const float *W0 = w, *b0 = W0 + O * H, *W1 = b0 + H, *b1 = W1 + H * H, *Wp = b1 + H, *bp = Wp + n_actions * H;
-  float h1[H], h2[H];
-#pragma unroll
-  for (int i = 0; i < H; ++i) {
-    float acc = b0[i];
-#pragma unroll
-    for (int j = 0; j < O; j += 2) {
-      const float2 wr = *(const float2 *)(W0 + O * i + j);
-      acc = fmaf(wr.x, o[j], acc); acc = fmaf(wr.y, o[j + 1], acc);
-    }
-    h1[i] = fmaxf(acc, 0.0f);
-  }
-#pragma unroll
-  for (int i = 0; i < H; ++i) {
-    float acc = b1[i];
-#pragma unroll
-    for (int j = 0; j < H; j += 4) {
-      const float4 wr = *(const float4 *)(W1 + i * H + j);
-      acc = fmaf(wr.x, h1[j], acc); acc = fmaf(wr.y, h1[j + 1], acc);
-      acc = fmaf(wr.z, h1[j + 2], acc); acc = fmaf(wr.w, h1[j + 3], acc);
-    }
-    h2[i] = fmaxf(acc, 0.0f);
-  }
-  float logit[CC_MAX_ACTIONS], m = -__builtin_inff();
-#pragma unroll
-  for (int a = 0; a < CC_MAX_ACTIONS; ++a) {
-    logit[a] = -__builtin_inff();
-    if (a < n_actions) {  // (uniform)
-      float acc = bp[a];
-#pragma unroll
-      for (int j = 0; j < H; j += 4) {
-        const float4 wr = *(const float4 *)(Wp + a * H + j);
-        acc = fmaf(wr.x, h2[j], acc); acc = fmaf(wr.y, h2[j + 1], acc);
-        acc = fmaf(wr.z, h2[j + 2], acc); acc = fmaf(wr.w, h2[j + 3], acc);
-      }
-      logit[a] = acc;
-      m = fmaxf(m, acc);
-    }
-  }
-  float e[CC_MAX_ACTIONS], sum = 0.0f;
-#pragma unroll
-  for (int a = 0; a < CC_MAX_ACTIONS; ++a) {
-    e[a] = (a < n_actions) ? expf(logit[a] - m) : 0.0f;
-    sum += e[a];
-  }
-#pragma unroll
-  for (int a = 0; a < CC_MAX_ACTIONS; ++a) prob[a] = e[a] / sum;
-}
-
 // One lane per replica: load the state, the observation and the timestep once, then at most `ticks` ticks of
 // (network on the observation in registers -> action -> Env::step), stopping at the first non-zero done; the terminal
 // tick counts (sum += reward, steps += 1 before the test).  use_argmax: the first maximum of the probabilities (the
@@ -647,7 +544,7 @@ __device__ __forceinline__ void cc_evaluate_impl(const Env &e, const float *stat
   static_assert(!Env::CONT, "the in-kernel policy has a softmax head");
   if (hidden != H || n_actions < 1 || n_actions > CC_MAX_ACTIONS || policy == nullptr) return;  // (uniform)
   constexpr int S = Env::S, O = Env::O;
-  const int n_w = O * H + H + H * H + H + n_actions * H + n_actions;
+  const int n_w = rp_policy_floats(O, H, n_actions);
   for (int i = threadIdx.x; i < n_w; i += blockDim.x) weights[i] = policy[i];
   __syncthreads();
   const uint32_t k0 = rng_state[0], k1 = rng_state[1];
@@ -673,13 +570,7 @@ __device__ __forceinline__ void cc_evaluate_impl(const Env &e, const float *stat
       cc_policy_probs<H, O>(weights, o, n_actions, prob);
       int act = 0;
       if (greedy) {
-        float best = prob[0];
-#pragma unroll
-        for (int i = 1; i < CC_MAX_ACTIONS; ++i) {
-          const bool better = i < n_actions && best < prob[i];
-          best = better ? prob[i] : best;
-          act = better ? i : act;
-        }
+        act = rp_first_maximum(prob, n_actions);
       } else {
         const float u = wd_u01_open_closed(wd_tick_draw((uint32_t)env, epoch0 + (uint32_t)k, (uint32_t)stream_tag,
                                                         k0, k1, blk, blk_quad));
@@ -733,7 +624,7 @@ __device__ __forceinline__ void cc_evaluate_actor_impl(const Env &e, const float
   static_assert(Env::CONT, "the actor's output is a Box action");
   if (hidden != H || actor == nullptr) return;  // (uniform)
   constexpr int S = Env::S, O = Env::O;
-  constexpr int n_w = cc_actor_floats(H, O);
+  constexpr int n_w = rp_actor_floats(H, O);
   for (int i = threadIdx.x; i < n_w; i += blockDim.x) weights[i] = actor[i];
   __syncthreads();
   const uint32_t k0 = rng_state[0], k1 = rng_state[1];

@@ -119,7 +119,7 @@
   TcFuse fz;                                                                                   \
   fz.rng_state = rng_state; fz.probs_acc = probs_acc; fz.probs_turn = probs_turn;              \
   fz.actions_out = const_cast<int *>(action_indices_arr);                                      \
-  fz.reset_table = (const TcResetEntry *)reset_table; fz.n_reset_arrays = n_reset_arrays;      \
+  fz.reset_table = (const wd_reset_entry *)reset_table; fz.n_reset_arrays = n_reset_arrays;      \
   fz.stream_tag = stream_tag;
 
 // ---- entries.  This file is compiled into SEVERAL code objects (warp_drive_amd/build.py UNITS; a build of all of them

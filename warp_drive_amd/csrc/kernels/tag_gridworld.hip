@@ -24,18 +24,11 @@ __constant__ int kIndexToActionArr[10] = {0, 0, 1, 0, -1, 0, 0, 1, 0, -1};
 
 namespace {
 
-struct GwResetEntry {  // same layout as wd_reset_entry in wd_core.hip
-  wd_global_u32 *data;
-  const wd_global_u32 *ref;
-  int row_elems;
-  int pad_;
-};
-
 struct GwFuse {
   uint32_t *rng_state;       // Philox epoch counters (WD_RNG_HEADER + one word per agent row)
   const float *probs;        // [E, N, n_actions] policy output
   int n_actions;
-  const GwResetEntry *reset_table;
+  const wd_reset_entry *reset_table;
   int n_reset_arrays;
   int stream_tag;
 };
@@ -187,7 +180,7 @@ __device__ __forceinline__ void gw_step_impl(
       for (int e = 0; e < envs_here; ++e) {
         if (s_done[e] == 0) continue;  // block-uniform
         for (int r = 0; r < fz.n_reset_arrays; ++r) {
-          const GwResetEntry ent = fz.reset_table[r];
+          const wd_reset_entry ent = fz.reset_table[r];
           const long base = (long)(env0 + e) * ent.row_elems;
           for (int i = tid; i < ent.row_elems; i += T_) ent.data[base + i] = ent.ref[base + i];
         }
@@ -279,7 +272,7 @@ __device__ __forceinline__ void gw_rollout_impl(
       // that all its loads are in flight together; a loop nest over replicas and arrays is a chain of round trips)
       int off = 0;
       for (int r = 0; r < fz.n_reset_arrays; ++r) {
-        const GwResetEntry ent = fz.reset_table[r];
+        const wd_reset_entry ent = fz.reset_table[r];
         const int re = ent.row_elems;
         const wd_global_u32 *const src = ent.ref + (long)env0 * re;
         const float inv_re = 1.0f / (float)re;
@@ -397,7 +390,7 @@ __device__ __forceinline__ void gw_rollout_impl(
         if (s_done[e] == 0) continue;
         int off = 0;
         for (int r = 0; r < fz.n_reset_arrays; ++r) {
-          const GwResetEntry ent = fz.reset_table[r];
+          const wd_reset_entry ent = fz.reset_table[r];
           const long base = (long)(env0 + e) * ent.row_elems;
           const bool is_obs = ((size_t)ent.data == (size_t)obs_arr);
           // (two copies of the loop, not a select between an LDS and a global pointer: that becomes a FLAT access)
@@ -472,7 +465,7 @@ __global__ void HipTagGridWorldTick(
   extern __shared__ __attribute__((aligned(16))) int gw_smem[];
   GwFuse fz;
   fz.rng_state = rng_state; fz.probs = probs; fz.n_actions = n_actions;
-  fz.reset_table = (const GwResetEntry *)reset_table; fz.n_reset_arrays = n_reset_arrays;
+  fz.reset_table = (const wd_reset_entry *)reset_table; fz.n_reset_arrays = n_reset_arrays;
   fz.stream_tag = stream_tag;
   gw_step_impl<true>(states_x_arr, states_y_arr, actions_arr, done_arr, rewards_arr, obs_arr, wall_hit_penalty,
                      tag_reward_for_tagger, tag_penalty_for_runner, step_cost_for_tagger, use_full_observation,
@@ -491,7 +484,7 @@ __global__ void HipTagGridWorldRollout(
   extern __shared__ __attribute__((aligned(16))) int gw_smem[];
   GwFuse fz;
   fz.rng_state = rng_state; fz.probs = probs; fz.n_actions = n_actions;
-  fz.reset_table = (const GwResetEntry *)reset_table; fz.n_reset_arrays = n_reset_arrays;
+  fz.reset_table = (const wd_reset_entry *)reset_table; fz.n_reset_arrays = n_reset_arrays;
   fz.stream_tag = stream_tag;
   gw_rollout_impl(states_x_arr, states_y_arr, actions_arr, done_arr, rewards_arr, obs_arr, wall_hit_penalty,
                   tag_reward_for_tagger, tag_penalty_for_runner, step_cost_for_tagger, use_full_observation,

@@ -47,8 +47,8 @@
 // (training/policy_kernel.py::pack_gridworld_policy): W0 [H][24] (rows of the 21 inputs, padded to 24 floats so that
 // every row starts on a 16-byte boundary; the padding is never read), b0 [H], W1 [H][H], b1 [H], Wp [5][H], bp [5],
 // float32, the block padded to a multiple of four floats.  Both sets live in LDS for the whole launch; a lane reads
-// its own policy's.  Arithmetic: acc = bias, then one fmaf per input in index order; softmax with the maximum
-// subtracted, expf, one division per action -- restated in oracle/tag_gridworld_np.py::policy_probabilities.
+// its own policy's.  The network and its parity contract: rollout_policy.h; restated on the host in
+// oracle/tag_gridworld_np.py::policy_probabilities.
 // Measured (profiles/r05_prepared_items_first_call.txt, 1000 replicas, 20 ticks per launch): 10.9 us per tick at
 // H = 32, 30.1 at H = 64 -- the trainer's per-tick path costs 390 - 490 us per tick of the same replicas.
 //
@@ -66,16 +66,10 @@
 // table up for it.)
 #pragma once
 #include "wd_common.h"
+#include "rollout_policy.h"
 #include "tag_gridworld_rewards.h"
 
 namespace {
-
-struct Gw5ResetEntry {  // same layout as wd_reset_entry in wd_core.hip
-  wd_global_u32 *data;
-  const wd_global_u32 *ref;
-  int row_elems;
-  int pad_;
-};
 
 constexpr int GW5_N = 5, GW5_F = 21, GW5_EPB = 12;
 constexpr int GW5_ROW = GW5_N * GW5_F;        // 105 floats: one replica's observation rows
@@ -85,64 +79,20 @@ constexpr int GW5_ACTIONS = 5;
 
 // floats of one policy's packed weights, rounded up to whole 16-byte vectors (the second policy starts aligned)
 __host__ __device__ constexpr int gw5_policy_floats(int H) {
-  return (H * GW5_IN_STRIDE + H + H * H + H + GW5_ACTIONS * H + GW5_ACTIONS + 3) & ~3;
+  return rp_pad4(rp_policy_floats(GW5_IN_STRIDE, H, GW5_ACTIONS));
 }
 
 __device__ __forceinline__ int gw5_roundup4(int n) { return (n + 3) & ~3; }
 
 // the action probabilities of one agent (the evaluation entries: the greedy action is their first maximum): w = its
-// policy's packed weights (LDS), x = its observation row (LDS, 21 floats)
+// policy's packed weights (LDS), x = its observation row (LDS, 21 floats).  rollout_policy.h behind the first layer at
+// stride 24 plus a tail column; the action count is a constant, so the head's guards fold away
 template <int H>
 __device__ __forceinline__ void gw5_policy_probs(const float *w, const float *x, float (&prob)[GW5_ACTIONS]) {
-  const float *W0 = w, *b0 = W0 + H * GW5_IN_STRIDE, *W1 = b0 + H, *b1 = W1 + H * H, *Wp = b1 + H, *bp = Wp + GW5_ACTIONS * H;
-  float in[GW5_F];
-#pragma unroll
-  for (int j = 0; j < GW5_F; ++j) in[j] = x[j];
-  float h1[H], h2[H];
-#pragma unroll
-  for (int i = 0; i < H; ++i) {
-    float acc = b0[i];
-#pragma unroll
-    for (int j = 0; j < 20; j += 4) {
-      const float4 wr = *(const float4 *)(W0 + i * GW5_IN_STRIDE + j);
-      acc = fmaf(wr.x, in[j], acc); acc = fmaf(wr.y, in[j + 1], acc);
-      acc = fmaf(wr.z, in[j + 2], acc); acc = fmaf(wr.w, in[j + 3], acc);
-    }
-    acc = fmaf(W0[i * GW5_IN_STRIDE + 20], in[20], acc);
-    h1[i] = fmaxf(acc, 0.0f);
-  }
-#pragma unroll
-  for (int i = 0; i < H; ++i) {
-    float acc = b1[i];
-#pragma unroll
-    for (int j = 0; j < H; j += 4) {
-      const float4 wr = *(const float4 *)(W1 + i * H + j);
-      acc = fmaf(wr.x, h1[j], acc); acc = fmaf(wr.y, h1[j + 1], acc);
-      acc = fmaf(wr.z, h1[j + 2], acc); acc = fmaf(wr.w, h1[j + 3], acc);
-    }
-    h2[i] = fmaxf(acc, 0.0f);
-  }
-  float logit[GW5_ACTIONS], m = -__builtin_inff();
-#pragma unroll
-  for (int a = 0; a < GW5_ACTIONS; ++a) {
-    float acc = bp[a];
-#pragma unroll
-    for (int j = 0; j < H; j += 4) {
-      const float4 wr = *(const float4 *)(Wp + a * H + j);
-      acc = fmaf(wr.x, h2[j], acc); acc = fmaf(wr.y, h2[j + 1], acc);
-      acc = fmaf(wr.z, h2[j + 2], acc); acc = fmaf(wr.w, h2[j + 3], acc);
-    }
-    logit[a] = acc;
-    m = fmaxf(m, acc);
-  }
-  float e[GW5_ACTIONS], sum = 0.0f;
-#pragma unroll
-  for (int a = 0; a < GW5_ACTIONS; ++a) {
-    e[a] = expf(logit[a] - m);
-    sum += e[a];
-  }
-#pragma unroll
-  for (int a = 0; a < GW5_ACTIONS; ++a) prob[a] = e[a] / sum;
+  float h1[H], logit[GW5_ACTIONS];
+  rp_first_layer_strided<H, GW5_F, GW5_IN_STRIDE>(w, w + H * GW5_IN_STRIDE, x, h1);
+  const float m = rp_policy_logits<H>(w + H * GW5_IN_STRIDE + H, h1, GW5_ACTIONS, logit);
+  rp_softmax_probs(logit, m, GW5_ACTIONS, prob);
 }
 
 // their running float32 sums (the rollout's counting draw), the last repeated up to eight entries
@@ -199,7 +149,7 @@ __device__ __forceinline__ void gw5_rollout(
   GW_REWARD_TABLE(wall_hit_penalty, tag_reward_for_tagger, tag_penalty_for_runner, step_cost_for_tagger);
   const int lane = threadIdx.x;                             // (blocks are one wavefront)
   const int el = lane / GW5_N, ag = lane - el * GW5_N;      // local replica (12 = none), agent
-  const Gw5ResetEntry *const table = (const Gw5ResetEntry *)reset_table;
+  const wd_reset_entry *const table = (const wd_reset_entry *)reset_table;
   const uint32_t k0 = rng_state[0], k1 = rng_state[1];
   uint32_t pk0 = 0u, pk1 = 0u;  // pooled only: the keys of the resetter's pool generator
   if constexpr (V::POOL) { pk0 = pool_rng[0]; pk1 = pool_rng[1]; }
@@ -273,7 +223,7 @@ __device__ __forceinline__ void gw5_rollout(
     {
       int off = 0;
       for (int r = 0; r < n_reset_arrays; ++r) {
-        const Gw5ResetEntry ent = table[r];
+        const wd_reset_entry ent = table[r];
         const int re = ent.row_elems;
         if constexpr (V::POOL) {
           if (off + re > CD) break;
@@ -518,13 +468,7 @@ __device__ __forceinline__ void gw5_evaluate(
         gw5_policy_probs<H>(my_policy, rep + ag * GW5_F, prob);
         int a = 0;
         if (greedy) {
-          float best = prob[0];
-#pragma unroll
-          for (int i = 1; i < GW5_ACTIONS; ++i) {
-            const bool better = best < prob[i];
-            best = better ? prob[i] : best;
-            a = better ? i : a;
-          }
+          a = rp_first_maximum(prob, GW5_ACTIONS);
         } else {
           float cum = 0.0f;
           int cnt = 0;

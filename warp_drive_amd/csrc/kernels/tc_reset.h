@@ -18,7 +18,7 @@ __device__ __forceinline__ void tc_reset_finished(const TcArgs &a, const TcFuse 
   for (int e = 0; e < envs_here; ++e) {
     if (tb.doneflag[e] == 0) continue;  // block-uniform
     for (int r = 0; r < fz.n_reset_arrays; ++r) {
-      const TcResetEntry ent = fz.reset_table[r];
+      const wd_reset_entry ent = fz.reset_table[r];
       const long base = (long)(env0 + e) * ent.row_elems;
       for (int i = tid; i < ent.row_elems; i += T_) ent.data[base + i] = ent.ref[base + i];
     }

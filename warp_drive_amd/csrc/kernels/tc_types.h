@@ -40,18 +40,12 @@ struct TcArgs {
 
 // extra inputs of the fused rollout tick (sample both action heads -> step -> reset finished
 // replicas, ONE launch)
-struct TcResetEntry {  // same layout as wd_reset_entry in wd_core.hip (global pointers: wd_common.h, wd_global_u32)
-  wd_global_u32 *data;
-  const wd_global_u32 *ref;
-  int row_elems;
-  int pad_;
-};
 struct TcFuse {
   uint32_t *rng_state;             // Philox epoch counters (WD_RNG_HEADER + one word per agent row)
   const float *probs_acc;          // [E, N, n_acc]  policy output, head 0
   const float *probs_turn;         // [E, N, n_turn] policy output, head 1
   int *actions_out;                // [E, N, 2] sampled_actions
-  const TcResetEntry *reset_table; // arrays registered with save_copy_and_apply_at_reset
+  const wd_reset_entry *reset_table; // arrays registered with save_copy_and_apply_at_reset
   int n_reset_arrays;
   int stream_tag;
 };

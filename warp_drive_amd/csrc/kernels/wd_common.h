@@ -117,6 +117,15 @@ __device__ __forceinline__ float wd_u01_open_closed(uint32_t bits) {
 // load then waits for every global store in flight as well.  The tables only ever hold device-memory addresses: say so.
 typedef uint32_t __attribute__((address_space(1))) wd_global_u32;
 
+// One entry of the reset table (reset_when_done_fused in wd_core.hip and every fused tick / rollout kernel that restores
+// the registered arrays itself): row `env` of `data` is restored from row `env` of `ref`, row_elems 32-bit words each.
+struct wd_reset_entry {
+  wd_global_u32 *data;
+  const wd_global_u32 *ref;
+  int row_elems;
+  int pad_;
+};
+
 // Global stores the compiler does NOT track, for the record stores inside a T-tick loop.  The waitcnt pass protects
 // the address / data registers of a store until the memory counter says it has left; a loop body that reuses those
 // registers on every trip therefore waits for the previous trip's stores (~1 us per tick: the whole cost of a

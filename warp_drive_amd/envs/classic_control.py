@@ -335,7 +335,7 @@ class ClassicControlPendulumEnv(_ClassicControlEnv):
 
 # ---------------------------------------------------------------------------------------------------- device envs
 def rollout_actor_floats(obs_size, width):
-    """floats of the packed actor the ...Rollout_A<width> entries read (classic_control.hip::cc_actor_floats): W0
+    """floats of the packed actor the ...Rollout_A<width> entries read (csrc/kernels/rollout_policy.h::rp_actor_floats): W0
     [H][OP], b0 [H], W1 [H][H], b1 [H], Wa [H], ba [1], OP = the observation size rounded up to even"""
     op = (int(obs_size) + 1) // 2 * 2
     return op * width + width + width * width + width + width + 1

@@ -4,7 +4,7 @@ The reference's counterparts are warp_drive/training/models/fully_connected_acto
 fully_connected_action_value_critic.py: an MLP trunk with a tanh output scaled into the action range, and an MLP on the
 concatenated (observation, action) with one output.  The actor's module layout -- `fc["0"]`, `fc["1"]`, `action_head` --
 is the one training/policy_kernel.py::pack_rollout_actor reads, so the rollout kernels of the Box envs can evaluate it
-(csrc/kernels/classic_control.hip::cc_actor_mean)."""
+(csrc/kernels/classic_control.hip::cc_actor_mean, the actor head of csrc/kernels/rollout_policy.h)."""
 import numpy as np
 import torch
 from torch import nn

@@ -280,7 +280,8 @@ def rollout_policy_width(model, obs_size, widths=(32, 64)):
 @torch.no_grad()
 def pack_rollout_policy(model, out=None):
     """W0 [H][obs], b0 [H], W1 [H][H], b1 [H], Wp [A][H], bp [A] as one flat float32 tensor (the layout
-    csrc/kernels/cartpole.hip::cp_policy_cum reads from LDS).  `out`: refill an existing tensor in place (the
+    csrc/kernels/rollout_policy.h states; cartpole_common.h::cp_policy_cum and classic_control.hip::cc_policy_cum read it from
+    LDS).  `out`: refill an existing tensor in place (the
     launch plan holds its address)."""
     parts = [model.fc["0"][0].weight, model.fc["0"][0].bias, model.fc["1"][0].weight, model.fc["1"][0].bias,
              model.policy_head[0].weight, model.policy_head[0].bias]
@@ -307,7 +308,7 @@ def rollout_actor_width(model, obs_size, widths=(32, 64)):
 @torch.no_grad()
 def pack_rollout_actor(model, out=None):
     """W0 [H][OP], b0 [H], W1 [H][H], b1 [H], Wa [H], ba [1] as one flat float32 tensor (the layout
-    csrc/kernels/classic_control.hip::cc_actor_mean reads from LDS); OP = the observation size rounded up to even, the
+    csrc/kernels/rollout_policy.h states and classic_control.hip::cc_actor_mean reads from LDS); OP = the observation size rounded up to even, the
     pad column zero.  `out`: refill an existing tensor in place (the launch plan holds its address)."""
     w0 = model.fc["0"][0].weight
     H, O = w0.shape
@@ -326,7 +327,8 @@ def pack_rollout_actor(model, out=None):
 
 @torch.no_grad()
 def pack_gridworld_policy(model, out=None):
-    """One policy of the live-policy TagGridWorld rollout (csrc/kernels/tag_gridworld_n5_common.h::gw5_policy_probs): W0
+    """One policy of the live-policy TagGridWorld rollout (csrc/kernels/tag_gridworld_n5_common.h::gw5_policy_probs, the
+    network of rollout_policy.h behind a first layer at stride 24): W0
     [H][24] (the 21 inputs of a row padded to 24 floats: every row starts on a 16-byte boundary), b0 [H], W1 [H][H],
     b1 [H], Wp [5][H], bp [5], float32, the block padded to a multiple of four floats.  `out`: refill in place."""
     from warp_drive_amd.envs.tag_gridworld import gridworld_policy_floats
