@@ -575,8 +575,16 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   WD_TC_PROBE(12);
   // the sparse form pays when few rows are live (late in an episode); wave-uniform choice
   const int n_live_rows = __popcll(__ballot(lane < wrows && (l.sig[wrow0 + lane] & 1)));
-  if (n_live_rows * 16 <= wrows * 9) {
-    tc_gather_rows_sparse(a, l, tb, stage, env0, wrow0, wrows, lane, K, N, invK, invN);
+  // (LOOP: a constant pair of its own, WD_TC_LOOP_SPARSE_NUM / 16 -- both forms are valid on any tick, the choice is cost
+  // alone, and a free-running block pays for latency where the one-tick kernel pays for bytes: docs/rounds/r30.md)
+  constexpr int SPARSE_NUM = LOOP ? WD_TC_LOOP_SPARSE_NUM : 9, SPARSE_DEN = 16;
+  if (n_live_rows * SPARSE_DEN <= wrows * SPARSE_NUM) {
+    if constexpr (LOOP) {
+      static_assert(!LOOP || (EXACTK && KMAX == 10), "the descriptor flush of the multi-tick entry is built for K = 10");
+      tc_gather_rows_sparse<true, KMAX>(a, l, tb, stage, env0, wrow0, wrows, lane, K, N, invK, invN);
+    } else {
+      tc_gather_rows_sparse(a, l, tb, stage, env0, wrow0, wrows, lane, K, N, invK, invN);
+    }
   } else {
     // observation rows, R rows per chunk: work item = (row, neighbour slot) -> 7 values at
     // row*F + c*K + k of the chunk image; then the time column; then the chunk leaves as one run.

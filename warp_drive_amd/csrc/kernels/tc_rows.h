@@ -74,6 +74,10 @@ __device__ __forceinline__ void tc_flush_ids(const unsigned short *src, int *dst
 #define WD_TC_STAGE_TARGET 5400  // bytes of rows per wavefront (19 rows of 71 floats); half of it for blocks of more
                                  // than four wavefronts (replicas of more than 256 agents), whose LDS also holds
                                  // the larger replica
+// sparse / dense choice of the multi-tick entry: sparse when at most this many sixteenths of a wavefront's rows are live
+#ifndef WD_TC_LOOP_SPARSE_NUM
+#define WD_TC_LOOP_SPARSE_NUM 9
+#endif
 __device__ __forceinline__ int tc_stage_rows(int row_dwords, int n_waves) {
   const int target = (n_waves > 4) ? WD_TC_STAGE_TARGET / 2 : WD_TC_STAGE_TARGET;
   return max(1, min(64, target / (4 * row_dwords)));
@@ -144,21 +148,64 @@ __device__ __forceinline__ TcFastLds tc_carve_fast(unsigned char *p0, int epb, i
 //   * neighbour in the game and built in the same chunk (the next slot): the lower row stores the line,
 //     merged (OR) with the first vector of the next slot; the upper row skips its first vector;
 //   * neighbour unknown (other wavefront / other block) or in another chunk: single dwords, own part only.
+// The flush below decides all of this per round and per lane; the multi-tick entry (LOOP) decides it once per row and
+// flushes from descriptors (TcLeanRows, further down): same rules, same bytes, a third of the instructions.
 __device__ __forceinline__ void tc_store_own_dwords(float *rowp, int F, int d0, const float (&v)[4], bool on) {
 #pragma unroll
   for (int e = 0; e < 4; ++e)
     if (on && d0 + e >= 0 && d0 + e < F) rowp[d0 + e] = v[e];
 }
 
+// ---- the LOOP variant (the multi-tick entry, one shape: K = 10) builds and stores the same row images from the same
+// two forms, but its flush works from one DESCRIPTOR word per packed row, formed once per chunk by lane j for slot j and
+// fetched in the flush round by lane (fsub, fv) with one ds_bpermute_b32 -- what depends on the row alone (the row list
+// read, mis, the shifts against lmask, the head / tail rules, the address) is not redone per round and per lane:
+//   bits  0.. 1  action of vector 0: the row's head (head mode: skip / own dwords / full line; no head when mis = 0: full)
+//   bits  2.. 3  action of vector NV - 2: the row's tail when mis = 0, else a full line
+//   bits  4.. 5  action of vector NV - 1: the row's tail when mis >= 2, else nothing (it lies past the row)
+//                (tail mode: merge with the next slot's first vector / own dwords / full line; no tail when mis = 1)
+//   bits  6.. 7  action of every other vector: a full line
+//   bits  8.. 9  mis
+//   bits 10..11  zero: what the lanes beyond the round's RPR * NV read
+//   bits 16..31  4 * (r * F - mis + 3): byte offset of the slot's first vector from the wavefront's first row, + 12
+// actions: 0 nothing, 1 own dwords only, 2 the whole 16-byte line, 3 the whole line OR-merged with the next slot's first
+// vector.  Lanes at or past the chunk's row count hold 0: nothing is stored for them.
+template <int KC>
+struct TcLeanRows {
+  static constexpr int F = 7 * KC + 1, SL = (F + 6) & ~3, NV = SL >> 2, RPR = 64 / NV;
+  // the wavefront's staging buffer (tc_carve_fast, blocks of at most four wavefronts) and the rows per chunk it gives
+  static constexpr int STAGE_DWORDS = (((4 * (WD_TC_STAGE_TARGET / (4 * F)) * F) + 15) & ~15) / 4 + 4 + 16;
+  static constexpr int CAP = STAGE_DWORDS - 16;
+  static constexpr int RS = (CAP / SL < 192 / KC) ? (CAP / SL < 64 ? CAP / SL : 64) : (192 / KC < 64 ? 192 / KC : 64);
+  static constexpr int ACT_NONE = 0, ACT_OWN = 1, ACT_FULL = 2, ACT_MERGE = 3;
+  // the flush reads slots up to RS (one past the chunk: the merge operand of the last slot, never used) without clamping
+  static_assert((RS + 1) * SL + 4 <= STAGE_DWORDS, "the unclamped LDS reads of the flush stay inside the staging buffer");
+  static_assert(((RS - 1) / (3 * RPR)) * 3 * RPR + 3 * RPR - 1 <= RS, "highest slot a trip of three rounds reads");
+  // the row's end lies in vector NV - 2 (mis = 0), nowhere short of a line end (mis = 1) or in vector NV - 1 (mis >= 2)
+  static_assert(4 * (NV - 2) < F && 4 * (NV - 2) + 4 > F && 4 * (NV - 1) - 1 == F, "tail positions of the descriptor");
+  static_assert(4 * (52 * F + 3) < 65536 && NV >= 4 && RPR * NV <= 64, "descriptor fields");
+};
+
+// the own-dword store sites of the LOOP flush: p = address of the vector's first dword, d0 its row-relative index
+__device__ __forceinline__ void tc_store_own_dwords_at(float *p, int F, int d0, const float (&v)[4], bool on) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    if (on && d0 + e >= 0 && d0 + e < F) p[e] = v[e];
+}
+
+template <bool LOOP = false, int KC = 0>
 __device__ __forceinline__ void tc_gather_rows_sparse(const TcArgs &a, const TcFastLds &l, const TcTables &tb, float *stage,
-                                               int env0, int wrow0, int wrows, int lane, int K, int N, float invK,
+                                               int env0, int wrow0, int wrows, int lane, int K_, int N, float invK,
                                                float invN) {
   typedef float v4f __attribute__((ext_vector_type(4)));
+  const int K = LOOP ? KC : K_;
   const int F = 7 * K + 1;
   const int SL = (F + 6) & ~3;       // dwords per row slot (mis + F <= SL)
   const int NV = SL >> 2;            // 16-byte vectors per slot
   const int cap = l.stage_dwords - 16;
-  const int rs = min(min(64, cap / SL), 192 / K);  // rows per chunk (at most 3 items per lane)
+  // rows per chunk (at most 3 items per lane); LOOP: the value the formula gives for the shape, as a constant
+  int rs = min(min(64, cap / SL), 192 / K);
+  if constexpr (LOOP) rs = TcLeanRows<KC>::RS;
   const int RPR = 64 / NV;           // rows per flush round (NV <= 58 for K <= 32)
   const float invNV = 1.0f / (float)NV;
   constexpr int U = 3;
@@ -233,15 +280,79 @@ __device__ __forceinline__ void tc_gather_rows_sparse(const TcArgs &a, const TcF
         }
       }
     }
+    [[maybe_unused]] unsigned desc = 0u;  // LOOP: the descriptor of slot `lane` (see TcLeanRows)
     if (lane < rc) {
       // time column: float(t) / episode_length (agents in the game, :474,:493,:543)
       const int r = rowlist[j0 + lane];
       const int e_m = (int)(((float)(wrow0 + r) + 0.5f) * invN);
       const int mis = (int)((bdw + (unsigned)(r * F)) & 3u);
       stage[lane * SL + mis + 7 * K] = tb.tfrac[e_m];
+      if constexpr (LOOP) {
+        typedef TcLeanRows<KC> D;
+        // the neighbouring rows: in the game?  known at all (inside this wavefront's rows)?  The packed order is the
+        // row order, so a live neighbour is the previous / next slot unless the chunk ends in between.
+        const bool prev_known = (r > 0), next_known = (r + 1 < wrows);
+        const bool prev_live = (((lmask << 1) >> r) & 1ull) != 0ull, next_live = (((lmask >> 1) >> r) & 1ull) != 0ull;
+        const unsigned head = (mis == 0)                   ? D::ACT_FULL   // no head: vector 0 is the row's own
+                              : (prev_live && lane > 0)    ? D::ACT_NONE   // stored by the row below, merged
+                              : (prev_live || !prev_known) ? D::ACT_OWN
+                                                           : D::ACT_FULL;  // the row below is (being) cleared
+        const unsigned tail = (next_live && lane + 1 < rc) ? D::ACT_MERGE
+                              : (next_live || !next_known) ? D::ACT_OWN
+                                                           : D::ACT_FULL;
+        const unsigned a_nv2 = (mis == 0) ? tail : (unsigned)D::ACT_FULL, a_nv1 = (mis >= 2) ? tail : (unsigned)D::ACT_NONE;
+        desc = head | (a_nv2 << 2) | (a_nv1 << 4) | ((unsigned)D::ACT_FULL << 6) | ((unsigned)mis << 8) |
+               ((unsigned)(4 * (r * F - mis + 3)) << 16);
+      }
     }
     asm volatile("" ::: "memory");
     __builtin_amdgcn_wave_barrier();
+    if constexpr (LOOP) {
+      // ---- flush from the descriptors: three rounds of RPR rows per trip, as below; per round and lane one
+      // bpermute, the action and the byte offset out of the word, the two LDS vectors, the OR-merge, one store
+      typedef TcLeanRows<KC> D;
+      static_assert(D::RPR == 3 && D::NV == 19 && D::F == 71 && D::SL == 76 && D::RS == 17, "built for K = 10");
+      constexpr int W = 3;
+      const bool idle = (fsub >= D::RPR);  // the lanes past RPR * NV: they read slot 0's neighbours and a zero field
+      const int fs = idle ? 0 : fsub;
+      const unsigned sh = idle ? 10u : (fv == 0) ? 0u : (fv == D::NV - 2) ? 2u : (fv == D::NV - 1) ? 4u : 6u;
+      for (int sb = 0; sb < rc; sb += W * D::RPR) {
+        unsigned dd[W];
+        v4f q[W], nx[W];
+#pragma unroll
+        for (int u = 0; u < W; ++u)
+          dd[u] = (unsigned)__builtin_amdgcn_ds_bpermute(4 * (sb + u * D::RPR + fs), (int)desc);
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+          q[u] = *(const v4f *)(stage + (sb + u * D::RPR + fs) * D::SL + 4 * fv);
+          nx[u] = *(const v4f *)(stage + (sb + u * D::RPR + fs + 1) * D::SL);  // first vector of the next slot (merge)
+        }
+#pragma unroll
+        for (int u = 0; u < W; ++u) {
+          if (sb + u * D::RPR < rc) {  // wave-uniform
+            const unsigned act = (dd[u] >> sh) & 3u;
+            const unsigned voff = (dd[u] >> 16) + 16u * (unsigned)fv;  // byte offset of the vector from obs_w, + 12
+            unsigned mm = (act == (unsigned)D::ACT_MERGE) ? 0xffffffffu : 0u;
+            asm volatile("" : "+v"(mm));  // (AND mask, not four selects)
+            v4f o = q[u];
+            o.x = __uint_as_float(__float_as_uint(o.x) | (__float_as_uint(nx[u].x) & mm));
+            o.y = __uint_as_float(__float_as_uint(o.y) | (__float_as_uint(nx[u].y) & mm));
+            o.z = __uint_as_float(__float_as_uint(o.z) | (__float_as_uint(nx[u].z) & mm));
+            o.w = __uint_as_float(__float_as_uint(o.w) | (__float_as_uint(nx[u].w) & mm));
+            if (act >= (unsigned)D::ACT_FULL)
+              asm volatile("global_store_dwordx4 %0, %1, %2 offset:-12 sc1" ::"v"(voff), "v"(o), "s"(obs_w) : "memory");
+            if (__ballot(act == (unsigned)D::ACT_OWN) != 0ull) {  // wave-uniform: a row at the edge of the wavefront's rows or of the chunk
+              const float vals[4] = {o.x, o.y, o.z, o.w};
+              const int d0 = 4 * fv - (int)((dd[u] >> 8) & 3u);
+              tc_store_own_dwords_at((float *)((char *)obs_w + voff) - 3, F, d0, vals, act == (unsigned)D::ACT_OWN);
+            }
+          }
+        }
+      }
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+      continue;
+    }
     // ---- flush: RPR rows per round, lane = (row of the round, 16-byte vector of its slot); three rounds
     // per trip so that three independent chains of LDS reads are in flight
     for (int sb = 0; sb < rc; sb += 3 * RPR) {
