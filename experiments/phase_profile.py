@@ -2,7 +2,8 @@
 """Per-wavefront phase timeline of the fused TagContinuous tick: the kernel source built with -DWD_TC_PROBES (shader-clock
 stamps at the phase boundaries + counters of the search's fallbacks, written through a __device__ pointer the harness
 sets).  Build the stamped code object here (hipcc cross-compiles), run on the GPU box:
-    python experiments/phase_profile.py build
+    python experiments/phase_profile.py build      (WD_PROF_LEVEL=2: a build that also counts the tag scans of the multi-tick
+                                                    entry that skip the roots; its "tags" phase is not for timing)
     python experiments/phase_profile.py [num_envs] [episode tick of the stamped launch] [runners per replica] [ticks of the stamped launch]
 With the multi-tick entry (WD_TICK_ROLLOUT=1, the default) the stamped launch is a run of [ticks] ticks (default 32) and ONE
 of its trips is stamped, the middle one, which is the episode tick asked for; WD_TICK_ROLLOUT=0 stamps a one-tick launch.
@@ -26,7 +27,9 @@ if len(sys.argv) > 1 and sys.argv[1] == "build":
     os.makedirs(PROF_DIR, exist_ok=True)
     for out, (unit, flags) in wb.UNITS.items():
         if out.startswith("wd_kernels_tc_k10"):  # the headline entry and the runtime-size K = 10 entries (big replicas)
-            subprocess.run([wb._hipcc(), *wb.KERNEL_FLAGS, *flags, "-DWD_TC_PROBES=1", os.path.join(wb.KDIR, unit), "-o",
+            # WD_PROF_LEVEL=2: also count the tag scans that skip the roots (slot 18); that build's "tags" phase is not for timing
+            subprocess.run([wb._hipcc(), *wb.KERNEL_FLAGS, *flags, f"-DWD_TC_PROBES={int(os.environ.get('WD_PROF_LEVEL', '1'))}",
+                            os.path.join(wb.KDIR, unit), "-o",
                             os.path.join(PROF_DIR, out)], check=True)
             print("built", os.path.join(PROF_DIR, out))
     sys.exit(0)
@@ -95,6 +98,12 @@ searched = st[:, 9] > 0
 print(f"wavefronts: {ran.sum()}; ran the search: {searched.sum()}; with a lane in the two-pass fallback / whole-wavefront resolution: "
       f"{(st[:, 20] > 0).sum()}; with a lane whose close pair was settled by one exact compare: "
       f"{(st[:, 23] > 0).sum()}; with a lane in the full ranking: {(st[:, 22] > 0).sum()}")
+# slot 18 of the multi-tick entry (a build with WD_PROF_LEVEL=2 only): trips on which the wavefront left the tag scan before
+# the roots (tc_find_tag<SKIP>)
+if looped and st[:, 18].any():
+    for wv in range(WPB):
+        sk = st[wv::WPB][ran[wv::WPB], 18]
+        print(f"tag roots skipped, wave {wv}: {sk.sum()} of {len(sk) * N_TICKS} wavefront-trips ({sk.sum() / max(1, len(sk) * N_TICKS):.4f})")
 pre = searched & (st[:, 19] > 0)   # (replicas of more than 128 agents: the prefiltered search; 1 = its radius held, 2 = repeated with the full chain)
 if pre.any():
     tr = st[pre, 18]

@@ -165,6 +165,58 @@ __global__ void HipTagContinuousTick(WD_TC_PARAMS WD_TC_FUSE_PARAMS) {
   tc_generic_impl<true>(a, fz, tc_smem, kNumAccelerationActions, kNumTurnActions);
 }
 
+// Exhaustive proof, for the divisors of ONE env configuration, that the multi-tick entry's division by launch constants
+// (tc_div_const behind tc_div_const_in_class, tc_divide.h -- the same functions, the same reciprocals from tc_loop_consts)
+// returns the bits of the true division:
+//   res[1], res[2]  every float32 bit pattern x (2^32 of them; a NaN quotient matches any NaN) against x / sp_div and
+//                   x / two_pi, where x is in the class the form is used for; outside it tc_move divides, so there is nothing
+//                   to compare (res[6] counts the patterns inside the class);
+//   res[3]          every float32 pattern widened to float64 against x / diag, EXCEPT +-inf (res[5] counts the excluded
+//                   patterns: 2), for which the form gives inf - inf: the dividends are positions clamped to [0, L];
+//   res[4]          t / T for t = 1 .. T, narrowed to float32 as the time column is.
+// -0.0 is NOT excluded: the form returns -0.0 for it (tc_divide.h).  res[1 .. 4] count mismatches; res[0], preset to 1 by
+// the host, is cleared on any mismatch or when a divisor is not a positive finite number.  Run once per distinct
+// (max_speed, grid_length, episode_length) by envs/tag_continuous.py::invariant_divide_ok; the env offers the multi-tick
+// entry only when res[0] stays 1.
+__global__ void HipTagContinuousVerifyInvariantDivide(float kMaxSpeed, float kGridLength, int kEpisodeLength, int *res) {
+  const TcLoopConsts lc = tc_loop_consts(kMaxSpeed, kGridLength, kEpisodeLength, 0.0f);
+  const float sp_div = tc_sp_div(kMaxSpeed);
+  const double diag = tc_diag(kGridLength), Td = (double)kEpisodeLength;
+  const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x, gsize = gridDim.x * blockDim.x;
+  if (gtid == 0) {
+    const bool sane = sp_div > 0.0f && sp_div < __builtin_inff() && diag > 0.0 && diag < (double)__builtin_inff() &&
+                      kEpisodeLength > 0;
+    if (!sane) res[0] = 0;
+    res[5] = 2;
+  }
+  int bad_sp = 0, bad_pi = 0, bad_diag = 0, bad_T = 0, in_class = 0;
+  for (uint64_t i = gtid; i < (1ull << 32); i += gsize) {
+    const float x = __uint_as_float((uint32_t)i);
+    if (tc_div_const_in_class(x, 0.0f, 0.0f)) {
+      ++in_class;
+      const float w0 = x / sp_div, g0 = tc_div_const(x, sp_div, lc.r_sp);
+      const float w1 = x / WD_TC_TWO_PI, g1 = tc_div_const(x, WD_TC_TWO_PI, WD_TC_R_TWO_PI);
+      bad_sp += (__float_as_uint(w0) != __float_as_uint(g0)) && !(w0 != w0 && g0 != g0);
+      bad_pi += (__float_as_uint(w1) != __float_as_uint(g1)) && !(w1 != w1 && g1 != g1);
+    }
+    if ((__float_as_uint(x) & 0x7fffffffu) != 0x7f800000u) {
+      const double xd = (double)x, w = xd / diag, g = tc_div_const(xd, diag, lc.r_diag);
+      bad_diag += (__double_as_longlong(w) != __double_as_longlong(g)) && !(w != w && g != g);
+    }
+  }
+  for (int t = 1 + (int)gtid; t <= kEpisodeLength && t > 0; t += (int)min(gsize, 0x40000000u)) {
+    const float w = (float)((double)t / Td), g = (float)tc_div_const((double)t, Td, lc.r_T);
+    bad_T += __float_as_uint(w) != __float_as_uint(g);
+  }
+  if (bad_sp) atomicAdd(&res[1], bad_sp);
+  if (bad_pi) atomicAdd(&res[2], bad_pi);
+  if (bad_diag) atomicAdd(&res[3], bad_diag);
+  if (bad_T) atomicAdd(&res[4], bad_T);
+  if (bad_sp | bad_pi | bad_diag | bad_T) res[0] = 0;
+  // (res[6 .. 7] are one 64-bit count: 2^32 does not fit an int)
+  if (in_class) atomicAdd((unsigned long long *)(res + 6), (unsigned long long)in_class);
+}
+
 #elif defined(WD_TC_SHAPE_N)
 
 // one shape, sizes folded: N, K (exactly KM) and the two head sizes are constants from here on

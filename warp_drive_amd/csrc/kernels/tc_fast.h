@@ -21,7 +21,8 @@ namespace {
 template <int KMAX, bool FUSED, bool EXACTK, int IDB, bool SAMPLE = FUSED, bool LOOP = false, int SN = 0, int SA = 0,
           int ST = 0>
 __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, unsigned char *smem, int n_acc,
-                                            int n_turn, int tick = 0, int n_taggers_in = 0, TcCarry *cy = nullptr) {
+                                            int n_turn, int tick = 0, int n_taggers_in = 0, TcCarry *cy = nullptr,
+                                            const TcLoopConsts *lc = nullptr) {
   WD_TC_PROBE_TICK(LOOP, tick);
   const int N = a.N, K = EXACTK ? KMAX : a.K;
   const int F = 7 * K + 1;
@@ -186,7 +187,7 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   const int sg = in.sg;
   const bool is_runner = active && (in.type == 0) && (sg != 0);  // member of self.runners
   if (active) {
-    const TcMoved m = tc_move(a, tb, in, sampled, gi, tab_in_lds, LOOP ? cy : nullptr);
+    const TcMoved m = tc_move<LOOP>(a, tb, in, sampled, gi, tab_in_lds, LOOP ? cy : nullptr, LOOP ? lc : nullptr);
     edge_pen = m.edge_pen; my_x = m.x; my_y = m.y;
     if constexpr (LOOP) {  // what the next trip would read back
       cy->in.x = m.x; cy->in.y = m.y;
@@ -235,7 +236,9 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
       const int t = in.tstep + 1;  // :800
       a.timestep[env] = t;
       tb.tstep[el] = t;
-      tb.tfrac[el] = (float)((double)t / (double)a.T);  // float(t) / episode_length, :474
+      // float(t) / episode_length, :474 (LOOP: by the reciprocal, proved for t = 1 .. T by the same verifier)
+      if constexpr (LOOP) tb.tfrac[el] = (float)tc_div_const((double)t, (double)a.T, lc->r_T);
+      else tb.tfrac[el] = (float)((double)t / (double)a.T);
       if constexpr (LOOP) {
         cy->in.tstep = t;
         if (reloaded) tb.nrun[el] = in.nrun;  // (otherwise the count the last trip left there: the tables survive the trip)
@@ -271,8 +274,15 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   // ------------------------------------------------------------ tags (counts are read after the
   // barrier that follows the gather)
   bool tagged = false;
-  if (is_runner)
-    tagged = tc_find_tag(a, tb, l.xy + el * NP, l.tagcnt + el * N, &tb.nrun[el], n_taggers, my_x, my_y);
+  if constexpr (LOOP) {
+    // the roots are taken only by a wavefront with a runner near enough for them to matter; lanes that are not runners
+    // take no part in that vote
+    if (is_runner)
+      tagged = tc_find_tag<true>(a, tb, l.xy + el * NP, l.tagcnt + el * N, &tb.nrun[el], n_taggers, my_x, my_y, lc->Bc);
+  } else {
+    if (is_runner)
+      tagged = tc_find_tag(a, tb, l.xy + el * NP, l.tagcnt + el * N, &tb.nrun[el], n_taggers, my_x, my_y);
+  }
   if constexpr (PRE) {
     if (cells_C != 0) __syncthreads();  // the packed positions, ids and hints are in place
   }
@@ -728,8 +738,11 @@ __device__ __forceinline__ void tc_fast_rollout(const TcArgs &a, const TcFuse &f
   // the Philox key never changes: read once per launch, kept in scalar registers
   cy.k0 = __builtin_amdgcn_readfirstlane(fz.rng_state[0]);
   cy.k1 = __builtin_amdgcn_readfirstlane(fz.rng_state[1]);
+  // the reciprocals of the launch's divisors and the tag filter's bound: the only true divisions of the launch
+  const TcLoopConsts lc = tc_loop_consts(a.max_speed, a.grid_length, a.T, a.margin);
   for (int tick = 0; tick < ticks; ++tick) {
-    n_taggers = tc_fast_impl<KMAX, true, EXACTK, IDB, true, true, SN, SA, ST>(a, fz, smem, n_acc, n_turn, tick, n_taggers, &cy);
+    n_taggers = tc_fast_impl<KMAX, true, EXACTK, IDB, true, true, SN, SA, ST>(a, fz, smem, n_acc, n_turn, tick, n_taggers, &cy,
+                                                                              &lc);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }

@@ -4,6 +4,7 @@
 #pragma once
 #include "wd_common.h"
 #include "tc_types.h"
+#include "tc_divide.h"
 
 namespace {
 
@@ -28,8 +29,11 @@ struct TcMoved {
   TcFeat ft;
 };
 // `cy` (the multi-tick entry only): the stored heading, acceleration and speed also go to the thread's carry
+// CDIV (the multi-tick entry only, with `lc`): the five divisions by launch constants that end the move are products with
+// the reciprocals of `lc` plus one residual correction (tc_div_const, tc_divide.h)
+template <bool CDIV = false>
 __device__ __forceinline__ TcMoved tc_move(const TcArgs &a, const TcTables &tb, const TcIn &in, int2 act, int gi,
-                                           bool tab_in_lds, TcCarry *cy = nullptr) {
+                                           bool tab_in_lds, TcCarry *cy = nullptr, const TcLoopConsts *lc = nullptr) {
   const float two_pi = 6.2831854820251465f;            // float32(2*pi), :356
   const float L = a.grid_length;
   const double diag = (double)L * 1.4142135623730951;  // float32 L * np.sqrt(2) -> f64, :146
@@ -66,11 +70,26 @@ __device__ __forceinline__ TcMoved tc_move(const TcArgs &a, const TcTables &tb, 
   m.x = px;
   m.y = py;
   if (cy != nullptr) { cy->in.dir = dir; cy->in.acc = acc; cy->in.speed = v; }
-  m.ft.nx = (double)px / diag;    // :462 (float64 division)
-  m.ft.ny = (double)py / diag;
-  m.ft.nsp = v / sp_div;          // float32 division (:456-458)
-  m.ft.nac = acc / sp_div;
-  m.ft.ndir = dir / two_pi;
+  if constexpr (CDIV) {
+    // px, py lie in [0, L] (the clamps above; fmaxf drops a NaN): never infinite, the one float32 dividend for which the
+    // float64 form fails for a finite `diag` (the verifier says so).  v, acc and dir are anything the state arrays held.
+    m.ft.nx = tc_div_const((double)px, diag, lc->r_diag);
+    m.ft.ny = tc_div_const((double)py, diag, lc->r_diag);
+    m.ft.nsp = tc_div_const(v, sp_div, lc->r_sp);
+    m.ft.nac = tc_div_const(acc, sp_div, lc->r_sp);
+    m.ft.ndir = tc_div_const(dir, two_pi, WD_TC_R_TWO_PI);
+    if (__builtin_expect(__ballot(!tc_div_const_in_class(v, acc, dir)) != 0ull, 0)) {  // (wave-uniform, never in practice)
+      m.ft.nsp = v / sp_div;
+      m.ft.nac = acc / sp_div;
+      m.ft.ndir = dir / two_pi;
+    }
+  } else {
+    m.ft.nx = (double)px / diag;    // :462 (float64 division)
+    m.ft.ny = (double)py / diag;
+    m.ft.nsp = v / sp_div;          // float32 division (:456-458)
+    m.ft.nac = acc / sp_div;
+    m.ft.ndir = dir / two_pi;
+  }
   m.ft.type_sig = ((in.type & 1) ? 0x3f800000 : 0) | (in.sg ? 1 : 0);
   return m;
 }

@@ -473,9 +473,40 @@ class TagContinuous(CUDAEnvironmentContext):
         name = self.cuda_step.name.replace("Step", "Rollout")
         if not fm.has_function(name):
             return None
+        if not self.invariant_divide_ok():  # the entry divides by reciprocals: only with the proof for THIS env's divisors
+            return None
         _, args, block, grid, shared = self.tick_launch(sampler, probabilities, resetter)
         fm.initialize_functions([name])
         return fm.get_function(name), args + [np.int32(1)], block, grid, shared
+
+    _INVARIANT_DIVIDE_VERDICTS = {}  # (max_speed, grid_length, episode_length) -> the verifier's eight result words
+
+    def invariant_divide_verdict(self):
+        """The multi-tick entry divides by max_speed + eps, 2 pi, the grid diagonal and the episode length through
+        reciprocals formed once per launch (csrc/kernels/tc_divide.h).  HipTagContinuousVerifyInvariantDivide compares that
+        form with the true division for every float32 dividend (and t = 1 .. T), on the device, with the kernel's own
+        functions: one launch per distinct (max_speed, grid_length, episode_length) of the process, made when a rollout
+        engine is built, never inside a run.  Returns its result words: [ok, mismatches for max_speed + eps, for 2 pi, for
+        the diagonal, for t / T, patterns excluded for the diagonal (+-inf), patterns inside the float32 class (2 words)]."""
+        key = (float(self.max_speed), float(self.grid_length), int(self.episode_length))
+        cache = TagContinuous._INVARIANT_DIVIDE_VERDICTS
+        if key not in cache:
+            import torch
+
+            fm = self.cuda_function_manager
+            fm.initialize_functions(["HipTagContinuousVerifyInvariantDivide"])
+            res = torch.zeros(8, dtype=torch.int32, device=torch.device("cuda", torch.cuda.current_device()))
+            res[0] = 1
+            fm.get_function("HipTagContinuousVerifyInvariantDivide")(
+                np.float32(self.max_speed), np.float32(self.grid_length), np.int32(self.episode_length), res,
+                block=(256, 1, 1), grid=(8192, 1), shared=0)
+            cache[key] = [int(v) for v in res.cpu().numpy()]
+        return cache[key]
+
+    def invariant_divide_ok(self):
+        """True when the device proved the reciprocal form bit-identical for this env's divisors; False: the env offers no
+        multi-tick entry and the rollout engine keeps one launch per tick (cohorts), as with WD_TICK_ROLLOUT=0."""
+        return self.invariant_divide_verdict()[0] == 1
 
     # ------------------------------------------------------------------------------ step
     def step(self, actions=None):
