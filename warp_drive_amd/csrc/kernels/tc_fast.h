@@ -136,7 +136,7 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   if constexpr (LOOP) {
     // (two slabs side by side, no tc_one_slab path: replicas of at most 128 agents, which is what the 7-bit ids mean)
     static_assert(!LOOP || IDB == 7, "tc_sample_heads_carried samples from two slabs: replicas of at most 128 agents");
-    sampled = tc_sample_heads_carried(fz, in.epoch, cy->k0, cy->k1, active, gi, li, slab_acc, slab_turn, n_acc, n_turn);
+    sampled = tc_sample_heads_carried<SA>(fz, in.epoch, cy->k0, cy->k1, active, gi, li, slab_acc, slab_turn, n_acc, n_turn);
     if (compact && lane == 0) tb.live_cnt[wave] = __popcll(live_mask);  // (no LDS access between slab issue and slab wait)
   } else if (FUSED) {
     if (active && ag == 0) a.done[env] = 0;  // a replica that finished (and was reset) last tick
@@ -551,7 +551,44 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   // `nearest_neighbor_ids` rows after the barrier.  Entry k goes to slot k at fixed offsets; the few
   // lanes whose entries are not in order (a near-tie, fewer than K agents in the game) then rewrite
   // their rows by rank.
-  {
+  if constexpr (LOOP) {
+    static_assert(!LOOP || (EXACTK && KMAX == 10 && IDB == 7), "the id rows of the multi-tick entry are built for K = 10");
+    // The multi-tick entry (one replica per block: block-local ids ARE agent ids) also stores the `nearest_neighbor_ids`
+    // rows here, from the registers of the lanes that found them, in front of the barrier: 40 bytes at
+    // ((env0 * N + row_agent) * K) int32, 8-byte aligned.  Nothing reads the 16-bit LDS copies back for it
+    // (tc_flush_ids, which the one-tick entries keep, did so for every row on every tick).
+    const bool any_out_of_order = __ballot(!in_order) != 0ull;  // wave-uniform
+    if (searcher) {
+      // the LDS row, for the gather: ten halfwords as five dwords (rows are 20 bytes apart; -1 gives 0xffff)
+      unsigned *const idrow = (unsigned *)(l.ids + row_agent * KMAX);
+#pragma unroll
+      for (int k = 0; k < KMAX; k += 2) idrow[k >> 1] = ((unsigned)nid[k] & 0xffffu) | ((unsigned)nid[k + 1] << 16);
+      if (any_out_of_order && !in_order) {
+        // entries not in slot order: the row is rewritten by rank as before, then read back (sign-extending: 0xffff
+        // gives -1; the reads follow the lane's own writes in LDS order and are waited for before the store), so that
+        // such a lane takes the common store below
+        unsigned short *const hrow = l.ids + row_agent * KMAX;
+#pragma unroll
+        for (int k = 0; k <= KMAX; ++k)  // (K of the KMAX + 1 entries have a rank < K)
+          if (rank[k] < KMAX) hrow[rank[k]] = (unsigned short)(nid[k] < 0 ? 0xffff : nid[k]);
+#pragma unroll
+        for (int k = 0; k < KMAX; ++k) nid[k] = (int)((const short *)hrow)[k];
+      }
+      tc_store_id_row<false>(a.nearest_ids + (long)env0 * (SN * KMAX), __umul24((unsigned)row_agent, 4u * KMAX), nid);
+    }
+    // An agent out of the game has the row ten times -1, and so it had on the tick before -- unless this is the first
+    // tick it is out (an agent tagged on trip t is in the game, and a searcher, on t; on t + 1 it arrives here with
+    // cleared == 0 and the row is written; from t + 2 on cleared == 1 and nothing is stored), or trip 0 of a launch or
+    // the trip after a restore (`reloaded`: the host may have written anything to the array, and to obs_rows_cleared).
+    // Its 16-bit LDS row is not written at all: the sparse gather reads the ids of live rows only (its row list), and
+    // the dense gather reads idp[] of such a row in bounds and discards the value (`valid` needs me.type_sig & 1).
+    if (active && sg == 0 && (reloaded || in.cleared == 0)) {
+      int none[KMAX];
+#pragma unroll
+      for (int k = 0; k < KMAX; ++k) none[k] = -1;
+      tc_store_id_row<true>(a.nearest_ids + (long)env0 * (SN * KMAX), __umul24((unsigned)ag, 4u * KMAX), none);
+    }
+  } else {
     const int ebase = el * N;
     const bool any_out_of_order = __ballot(!in_order) != 0ull;  // wave-uniform
     if (active && sg == 0) {  // out of the game: no neighbours
@@ -580,8 +617,10 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   const int wrow0 = wave * rpw;
   const int wrows = max(0, min(rpw, agents_here - wrow0));
   // nearest_neighbor_ids [E, N, K]: this wavefront's rows, straight from the 16-bit LDS copies
-  tc_flush_ids(l.ids + (size_t)wrow0 * K, a.nearest_ids + ((long)env0 * N + wrow0) * K, wrows * K, lane, wrow0, N,
-               invK, invN, epb == 1);
+  // (LOOP: stored in front of the barrier, from registers)
+  if constexpr (!LOOP)
+    tc_flush_ids(l.ids + (size_t)wrow0 * K, a.nearest_ids + ((long)env0 * N + wrow0) * K, wrows * K, lane, wrow0, N,
+                 invK, invN, epb == 1);
   WD_TC_PROBE(12);
   // the sparse form pays when few rows are live (late in an episode); wave-uniform choice
   const int n_live_rows = __popcll(__ballot(lane < wrows && (l.sig[wrow0 + lane] & 1)));

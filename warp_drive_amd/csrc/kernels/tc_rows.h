@@ -69,6 +69,35 @@ __device__ __forceinline__ void tc_flush_ids(const unsigned short *src, int *dst
   if (lane < n - tail0) dst[tail0 + lane] = local((int)(short)src[tail0 + lane], tail0 + lane);
 }
 
+// One nearest_neighbor_ids row of K = 10 int32 from a lane's registers (the multi-tick entry: the lane that found the
+// ids stores them, tc_fast.h "ids out").  The row is 8-byte aligned (rows are 40 bytes), so it is two 16-byte
+// stores (global stores need dword alignment only) and an 8-byte tail.  Plain stores: written through (sc1), the form of
+// tc_flush_run, these 40-byte pieces cost more than the whole tc_flush_ids they replace (measured: docs/rounds/r32.md,
+// which also has five 8-byte stores, plain -- the compiler merges them into these three -- and written through).
+// DWORD_TAIL: the tail as two single dwords -- the form of the rare row of an agent that has just left the game; the loop
+// keeps as many single-dword store sites as the one-tick entry, whose tc_flush_ids has two.
+template <bool DWORD_TAIL, int NN>
+__device__ __forceinline__ void tc_store_id_row(int *replica_rows, unsigned row_bytes, const int (&v)[NN]) {
+  static_assert(NN >= 10, "a row of ten ids");
+  typedef int v4i __attribute__((ext_vector_type(4)));
+  typedef int v2i __attribute__((ext_vector_type(2)));
+  typedef v4i __attribute__((aligned(8))) v4i_a8;
+  typedef v2i __attribute__((aligned(8))) v2i_a8;
+  // (the replica's first row is uniform, the row's place in it a 32-bit byte offset: scalar base + vector offset)
+  int *const dst = (int *)((char *)replica_rows + row_bytes);
+  const v4i q0 = {v[0], v[1], v[2], v[3]}, q1 = {v[4], v[5], v[6], v[7]};
+  *(v4i_a8 *)dst = q0;
+  *(v4i_a8 *)(dst + 4) = q1;
+  if constexpr (DWORD_TAIL) {
+    // (asm: two stores, not one merged pair)
+    asm volatile("global_store_dword %0, %1, off offset:32" ::"v"(dst), "v"(v[8]) : "memory");
+    asm volatile("global_store_dword %0, %1, off offset:36" ::"v"(dst), "v"(v[9]) : "memory");
+  } else {
+    const v2i q2 = {v[8], v[9]};
+    *(v2i_a8 *)(dst + 8) = q2;
+  }
+}
+
 // rows of a wavefront's staging buffer: the host sizes the buffer with the same formula
 // (envs/tag_continuous.py: lds_bytes_fast)
 #define WD_TC_STAGE_TARGET 5400  // bytes of rows per wavefront (19 rows of 71 floats); half of it for blocks of more

@@ -53,6 +53,9 @@ __device__ __forceinline__ int2 tc_sample_heads(const TcArgs &a, const TcFuse &f
 // call site).  The caller has issued both slabs and NOTHING else since; between that and the wait there is only register work: the ten Philox rounds, on the epoch the thread carries
 // and the key the launch read once, run in the shadow of the fetch.  No load, no store (its acknowledgement would be
 // waited for in order with the slabs' data) and no LDS access lies in between.  The epoch word goes out with the actions.
+// SA: the size of both heads as a constant (n_acc == n_turn == SA, set by the entry): SA entries read and scanned per
+// head, not WD_SLAB_CH of which the last are masked off.
+template <int SA>
 __device__ __forceinline__ int2 tc_sample_heads_carried(const TcFuse &fz, uint32_t epoch, uint32_t k0, uint32_t k1,
                                                         bool active, int gi, int li, const float *slab_acc,
                                                         const float *slab_turn, int n_acc, int n_turn) {
@@ -66,8 +69,12 @@ __device__ __forceinline__ int2 tc_sample_heads_carried(const TcFuse &fz, uint32
   __builtin_amdgcn_wave_barrier();
   int2 sampled = make_int2(0, 0);
   if (active) {
-    sampled.x = wd_slab_sample(slab_acc + (size_t)li * n_acc, n_acc, wd_u01_open_closed(rnd.x));
-    sampled.y = wd_slab_sample(slab_turn + (size_t)li * n_turn, n_turn, wd_u01_open_closed(rnd.y));
+    sampled.x = wd_slab_sample<SA>(slab_acc + (size_t)li * SA, wd_u01_open_closed(rnd.x));
+    // (the second slab's row through a byte offset the compiler cannot see through: one address register and immediate
+    // offsets, as for the first -- folded into the offsets, the slab's distance is beyond what a two-dword read encodes)
+    unsigned turn_row = (unsigned)((const char *)slab_turn - (const char *)slab_acc) + 4u * SA * (unsigned)li;
+    asm volatile("" : "+v"(turn_row));
+    sampled.y = wd_slab_sample<SA>((const float *)((const char *)slab_acc + turn_row), wd_u01_open_closed(rnd.y));
     ((int2 *)fz.actions_out)[gi] = sampled;
     fz.rng_state[WD_RNG_HEADER + gi] = epoch + 1u;
   }

@@ -199,3 +199,21 @@ __device__ __forceinline__ int wd_slab_sample(const float *row, int n, float u) 
   }
   return min(cnt, n - 1);
 }
+
+// the same for a row length known at compile time (NC <= WD_SLAB_CH): NC entries read and scanned, none masked off --
+// entry i sits on bit NC-1-i and nothing else is in the mask
+template <int NC>
+__device__ __forceinline__ int wd_slab_sample(const float *row, float u) {
+  static_assert(NC >= 1 && NC <= WD_SLAB_CH, "a row that is read back with all LDS loads in flight");
+  float p[NC];
+#pragma unroll
+  for (int i = 0; i < NC; ++i) p[i] = row[i];
+  float cum = 0.0f;
+  unsigned m = 0u;
+#pragma unroll
+  for (int i = 0; i < NC; ++i) {
+    cum = (i == 0) ? p[0] : cum + p[i];
+    m = __builtin_amdgcn_alignbit(m, __float_as_uint(cum - u), 31);
+  }
+  return min((int)__popc(m), NC - 1);
+}
