@@ -12,9 +12,15 @@
   csrc/wd_kernels.manifest.json   kernel name -> code object, written after every build (the host asks it which object
                               to load for a function: managers/hip_driver.py)
 
+  $WD_ENV_CACHE/<name>-<hash>.hsaco   (default ~/.cache/warp_drive_amd/envs) the code object of a CUSTOM environment,
+                              compiled on first use from the source its registrar holds (build_env_unit): never
+                              written under csrc/, never in the manifest
+
 hipcc cross-compiles gfx950 without a GPU, so this runs in the build container; the built files are git-ignored but
 travel to the GPU box with the tree.
 """
+import functools
+import hashlib
 import json
 import os
 import re
@@ -130,15 +136,22 @@ def build_runtime(force=False, verbose=False):
 _INCLUDE = re.compile(r'^\s*#include\s+"([^"]+)"', re.M)
 
 
-def unit_sources(unit):
-    """the translation unit and every local file it includes (transitively)"""
+def unit_sources(unit, include_dirs=None):
+    """the translation unit and every local file it includes (transitively).  `unit`: a file name under csrc/kernels/,
+    or -- with `include_dirs`, the compiler's -I directories in order -- any path: a quoted include is then looked up
+    next to the including file first and in those directories after it, as the compiler does"""
     todo, seen = [os.path.join(KDIR, unit)], []
     while todo:
         path = todo.pop()
         if path in seen or not os.path.exists(path):
             continue
         seen.append(path)
-        todo += [os.path.join(KDIR, inc) for inc in _INCLUDE.findall(open(path).read())]
+        for inc in _INCLUDE.findall(open(path).read()):
+            if include_dirs is None:
+                todo.append(os.path.join(KDIR, inc))
+                continue
+            places = [os.path.join(d, inc) for d in [os.path.dirname(path), *include_dirs]]
+            todo.append(next((p for p in places if os.path.exists(p)), places[0]))
     return seen
 
 
@@ -193,6 +206,81 @@ def build_shape_unit(k, n_agents, n_actions, threads, verbose=False):
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)
     return out
+
+
+def env_cache_dir():
+    """where the code objects of custom environments are kept (build_env_unit): $WD_ENV_CACHE, else the user's cache"""
+    return os.environ.get("WD_ENV_CACHE") or os.path.join(os.path.expanduser("~"), ".cache", "warp_drive_amd", "envs")
+
+
+@functools.lru_cache(maxsize=None)
+def _hipcc_version(hipcc):
+    return subprocess.run([hipcc, "--version"], check=True, capture_output=True, text=True).stdout
+
+
+def env_unit_flags(src_path):
+    """compiler flags of a custom environment's unit: the in-tree kernels' (the parity contract -- no contraction,
+    correctly rounded divide and sqrt -- holds for user kernels too), include/ for wd_env.h, the source's own directory"""
+    return [*KERNEL_FLAGS, f"-I{os.path.join(ROOT, 'include')}", f"-I{os.path.dirname(os.path.abspath(src_path))}"]
+
+
+def env_unit_path(name, src_path):
+    """<cache>/<name>-<16 hex>.hsaco: the hash covers the source, every local file it includes (transitively), the flags
+    and the compiler's version -- the object is a function of CONTENT, never of a modification time"""
+    src_path = os.path.abspath(src_path)
+    flags = env_unit_flags(src_path)
+    digest = hashlib.sha256()
+    for path in unit_sources(src_path, [f[2:] for f in flags if f.startswith("-I")]):
+        digest.update(open(path, "rb").read() + b"\0")
+    digest.update("\0".join(flags).encode() + b"\0" + _hipcc_version(_hipcc()).encode())
+    safe = re.sub(r"[^A-Za-z0-9_.]", "_", str(name))
+    return os.path.join(env_cache_dir(), f"{safe}-{digest.hexdigest()[:16]}.hsaco")
+
+
+def build_env_unit(name, src_path, verbose=False):
+    """Build (once per content, under the cache directory's lock) the code object of ONE custom environment from the
+    source registered for it (utils/env_registrar.py::add_cuda_env_src_path) -- what the reference does by compiling the
+    registered file next to its core services (pycuda_function_manager.py:133-232).  Nothing under csrc/ is written: an
+    install may be read-only, and the in-tree manifest does not know these kernels (the function manager that asked
+    keeps the module to itself).  Returns the code object's path."""
+    import fcntl
+
+    src_path = os.path.abspath(src_path)
+    if not os.path.isfile(src_path):
+        raise FileNotFoundError(f"the device source of environment {name} is missing: {src_path}")
+    target = env_unit_path(name, src_path)
+    if os.path.exists(target):  # (written by os.replace: whole or absent)
+        return target
+    os.makedirs(os.path.dirname(target), exist_ok=True)
+    with open(os.path.join(os.path.dirname(target), ".build.lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        try:
+            if not os.path.exists(target):
+                tmp = target + f".{os.getpid()}.tmp"
+                cmd = [_hipcc(), *env_unit_flags(src_path), *_cuid(os.path.basename(target)), src_path, "-o", tmp]
+                if verbose:
+                    print(" ".join(cmd), flush=True)
+                done = subprocess.run(cmd, capture_output=True, text=True)
+                if done.returncode != 0 or not os.path.exists(tmp):
+                    if os.path.exists(tmp):
+                        os.remove(tmp)
+                    raise RuntimeError(f"hipcc failed (exit status {done.returncode}) on the device source of environment "
+                                       f"{name}, {src_path}:\n{done.stderr}")
+                os.replace(tmp, target)
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)
+    return target
+
+
+def in_tree_kernel_owners():
+    """{kernel name: code object file name} of every in-tree kernel: the manifest's, and the main object's own"""
+    owners = {}
+    if os.path.exists(HSACO):
+        owners.update({k: os.path.basename(HSACO) for k in kernels_in(HSACO)})
+    if os.path.exists(MANIFEST):
+        for k, v in json.load(open(MANIFEST)).items():
+            owners.setdefault(k, v)
+    return owners
 
 
 def write_manifest():

@@ -34,7 +34,8 @@ def generate_random_actions(env, num_envs, rng):
 
 class EnvironmentCPUvsGPU:
     def __init__(self, cpu_env_class=None, cuda_env_class=None, dual_mode_env_class=None, env_configs=None,
-                 num_envs=3, num_episodes=2, env_wrapper=EnvWrapper, gpu_env_backend="hip", **_ignored):
+                 num_envs=3, num_episodes=2, env_wrapper=EnvWrapper, gpu_env_backend="hip", env_registrar=None,
+                 **_ignored):
         if dual_mode_env_class is not None:
             cpu_env_class = cuda_env_class = dual_mode_env_class
         assert cpu_env_class is not None and cuda_env_class is not None and env_configs
@@ -42,13 +43,16 @@ class EnvironmentCPUvsGPU:
         self.env_configs = env_configs
         self.num_envs, self.num_episodes = num_envs, num_episodes
         self.env_wrapper = env_wrapper
+        # a custom environment: the registrar that holds its device source, handed to the device wrapper
+        self.env_registrar = env_registrar
 
     def test_env_reset_and_step(self, consistency_threshold_pct=None, seed=None, atol=1e-5):
         for scenario, cfg in self.env_configs.items():
             E = self.num_envs
             cpu = [self.env_wrapper(env_obj=self.cpu_env_class(**cfg), env_backend="cpu") for _ in range(E)]
             obs_cpu = [e.reset() for e in cpu]
-            gpu = self.env_wrapper(env_obj=self.cuda_env_class(**cfg), num_envs=E, env_backend="hip")
+            extra = {} if self.env_registrar is None else {"env_registrar": self.env_registrar}
+            gpu = self.env_wrapper(env_obj=self.cuda_env_class(**cfg), num_envs=E, env_backend="hip", **extra)
             gpu.reset_all_envs()
             create_and_push_data_placeholders(env_wrapper=gpu, action_sampler=None,
                                               training_batch_size_per_env=None, push_data_batch_placeholders=False)

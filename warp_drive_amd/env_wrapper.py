@@ -6,6 +6,8 @@ API mirror of reference warp_drive/env_wrapper.py:28-408.  Differences:
     code object or the GPU is missing -- there is no silent CPU fallback;
   * the code object is prebuilt, so `testing_mode` simply loads it (the reference
     loads a fixed 2-env x 5-agent test binary, :196-206);
+  * a custom environment -- `env_registrar` holds a device source for the env's name -- is compiled on first use and
+    its `Hip<name>Step` (or, a ported source, `Cuda<name>Step`) served from that object (docs/custom_environments.md);
   * blocks_per_env must be 1 (multi-block replicas are out of scope).
 First reset happens on the host and pushes every array once; all later resets and
 steps run on the device in place (:264-353).
@@ -84,13 +86,20 @@ class EnvWrapper:
         self.cuda_function_feed = CUDAFunctionFeed(self.cuda_data_manager)
         ready = self.env.initialize_step_function_context(
             cuda_data_manager=self.cuda_data_manager, cuda_function_manager=self.cuda_function_manager,
-            cuda_step_function_feed=self.cuda_function_feed, step_function_name=f"Hip{self.name}Step")
+            cuda_step_function_feed=self.cuda_function_feed, step_function_name=self._kernel_name("Step"))
         assert ready, "The environment class failed to initialize the HIP step function"
         self.env_resetter = HIPEnvironmentReset(function_manager=self.cuda_function_manager)
         self.env_resetter.register_custom_reset_function(self.cuda_data_manager,
-                                                         reset_function_name=f"Hip{self.name}Reset")
+                                                         reset_function_name=self._kernel_name("Reset"))
         # an env whose rollout kernel draws from the reset pool itself asks the resetter whether its generator is ready
         self.env.cuda_env_resetter = self.env_resetter
+
+    def _kernel_name(self, what):
+        """`Hip<name><what>` when some code object has it, else -- a source ported from the reference keeps its entry
+        names -- `Cuda<name><what>` when some object has that; else the Hip spelling (whoever asks for it reports it)"""
+        has = self.cuda_function_manager.has_function
+        hip, cuda = f"Hip{self.name}{what}", f"Cuda{self.name}{what}"
+        return cuda if not has(hip) and has(cuda) else hip
 
     # ------------------------------------------------------------------------- reset
     def _push_initial_data(self):

@@ -13,7 +13,10 @@ pycuda_managers/pycuda_function_manager.py and numba_managers/numba_function_man
 Kernel sizes are runtime arguments, so there is no per-run templating/compilation
 (pycuda_function_manager.py:133-232): `compile_and_load_hip` only (re)builds the
 in-tree code object when its sources are newer, rank 0 only, with the same
-multiprocessing-Event hand-shake as the reference (:170-181,:227-228).
+multiprocessing-Event hand-shake as the reference (:170-181,:227-228).  A CUSTOM environment -- a registrar that holds
+a device source for the env's name -- is what the reference compiles next to its core services: here that one file is
+built into a code object of its own (build.build_env_unit) and loaded as the manager's custom module, consulted for
+the names the in-tree objects do not have (docs/custom_environments.md).
 """
 import logging
 import os
@@ -248,6 +251,31 @@ DEFAULT_FUNCTION_NAMES = [
 ]
 
 
+def registered_source_path(registrar, env_name):
+    """the device source `registrar` holds for `env_name` -- the name as given, then lower-cased -- or None (no
+    registrar, a registrar without source paths, no name, nothing registered)"""
+    lookup = getattr(registrar, "get_cuda_env_src_path", None)
+    if lookup is None or not env_name:
+        return None
+    for name in (env_name, env_name.lower()):
+        path = lookup(name)
+        if path is not None:
+            return path
+    return None
+
+
+def check_custom_kernel_names(hsaco, src_path=None):
+    """ValueError when a kernel of the custom code object `hsaco` carries the name of an in-tree kernel (the build's
+    manifest and the main object are asked): nothing shadows anything, in either direction.  Reads files only."""
+    from warp_drive_amd import build as wd_build
+
+    owners = wd_build.in_tree_kernel_owners()
+    for kernel in wd_build.kernels_in(hsaco):
+        if kernel in owners:
+            raise ValueError(f"kernel {kernel} of the custom environment ({src_path or hsaco}, built as {hsaco}) has the "
+                             f"name of an in-tree kernel of {os.path.join(wd_build.CSRC, owners[kernel])}: rename it")
+
+
 class HIPFunctionManager(CUDAFunctionManager):
     def __init__(self, num_agents: int = 1, num_envs: int = 1, blocks_per_env: int = 1, process_id: int = 0,
                  device_id: Optional[int] = None):
@@ -261,6 +289,7 @@ class HIPFunctionManager(CUDAFunctionManager):
         drv.ensure_init(self._device_id)
         self._module = None
         self._extra_modules = None  # {path: Module} of the other code objects, loaded when a function is first asked for
+        self._custom_module = None  # the code object of a custom environment (this manager's alone, never shared)
         self._functions = {}
         self._function_names = []
 
@@ -288,6 +317,9 @@ class HIPFunctionManager(CUDAFunctionManager):
         a fresh code object; who builds is independent of the device a rank drives."""
         from warp_drive_amd import build as wd_build
 
+        # a custom environment: the device source its registrar holds for `env_name` (None: an in-tree env, and the
+        # call does what it always did) is compiled after the in-tree build into a code object of this manager's own
+        src_path = registered_source_path(customized_env_registrar, env_name)
         if event_messenger is not None:
             if self._process_id > 0:
                 event_messenger.wait(timeout=120)
@@ -295,12 +327,27 @@ class HIPFunctionManager(CUDAFunctionManager):
                     raise Exception(f"Process {self._process_id} fails to get the successful compilation message ... ")
             else:
                 wd_build.build_kernels()
+                if src_path is not None:
+                    wd_build.build_env_unit(env_name, src_path)
                 event_messenger.set()
         else:
             wd_build.build_kernels_locked()
         self.load_hip_from_binary_file(default_functions_included=default_functions_included)
+        if src_path is not None:
+            # (process 0 built it before it set the Event; without an Event build_env_unit's own file lock decides who
+            # compiles -- here the object is found by its content hash and nothing is compiled twice)
+            self.load_custom_hip_from_binary_file(wd_build.build_env_unit(env_name, src_path), src_path)
 
     compile_and_load_cuda = compile_and_load_hip
+
+    def load_custom_hip_from_binary_file(self, hsaco, src_path=None):
+        """load the code object of a custom environment as this manager's custom module: its kernels answer for names
+        that neither the main object nor the build's manifest has, its __constant__ symbols are looked up first"""
+        assert self._module is not None, "load the main code object first"
+        assert self._custom_module is None, "a custom code object has already been loaded"
+        check_custom_kernel_names(hsaco, src_path)
+        self._custom_module = drv.Module(hsaco)
+        logging.info(f"loaded the HIP code object {hsaco} of a custom environment")
 
     # ---- kernels
     def initialize_default_functions(self):
@@ -316,16 +363,20 @@ class HIPFunctionManager(CUDAFunctionManager):
             self._functions[fname] = module.get_function(fname)  # (raises with the name when nobody has it)
             self._function_names.append(fname)
 
+    def _custom_has(self, fname):
+        return self._custom_module is not None and self._custom_module.has_function(fname)
+
     def _module_of(self, fname):
         """the loaded code object that holds kernel `fname`: the main one, or -- looked up in the build's manifest and
-        loaded on first use -- one of the others (warp_drive_amd/build.py UNITS); None when no object has it"""
+        loaded on first use -- one of the others (warp_drive_amd/build.py UNITS), or -- for a name none of those has --
+        this manager's custom module; None when no object has it"""
         if self._module.has_function(fname):
             return self._module
         if self._extra_modules is None:
             self._extra_modules = {}
         path = drv.code_object_of(fname)
         if path is None or path == self._module.path:
-            return None
+            return self._custom_module if self._custom_has(fname) else None
         if path not in self._extra_modules:
             self._extra_modules[path] = drv.Module(path)
             logging.info(f"loaded the HIP code object {path}")
@@ -334,24 +385,34 @@ class HIPFunctionManager(CUDAFunctionManager):
     def has_function(self, fname):
         if self._module is None:
             return False
-        return self._module.has_function(fname) or drv.code_object_of(fname) is not None
+        return self._module.has_function(fname) or drv.code_object_of(fname) is not None or self._custom_has(fname)
 
     def code_object_path_of(self, fname):
         """file the kernel `fname` was (or would be) loaded from -- what a counter record is keyed to"""
         if self._module is not None and self._module.has_function(fname):
             return self._module.path
-        return drv.code_object_of(fname)
+        path = drv.code_object_of(fname)
+        if path is None and self._custom_has(fname):
+            return self._custom_module.path
+        return path
 
     def global_address(self, name):
         """device address of a __device__ / __constant__ symbol of the MAIN code object (for kernels of the extra
         code objects that read a table the host uploads there)"""
         return self._module.get_global(name)[0]
 
+    def constant_module_of(self, name):
+        """the module a __constant__ / __device__ symbol is uploaded into: the custom one first, then the main one"""
+        if self._custom_module is not None and self._custom_module.has_global(name):
+            return self._custom_module
+        return self._module
+
     def initialize_shared_constants(self, data_manager, constant_names: list):
-        """Upload DataManager shared constants into __constant__ symbols (:363-379)."""
+        """Upload DataManager shared constants into __constant__ symbols (:363-379): a symbol of the custom module
+        when that has one of the name, else of the main code object."""
         for cname in constant_names:
             value = np.ascontiguousarray(data_manager.shared_constant(cname))
-            dst, nbytes = self._module.get_global(cname)
+            dst, nbytes = self.constant_module_of(cname).get_global(cname)
             assert value.nbytes <= nbytes, f"shared constant {cname}: {value.nbytes} B does not fit {nbytes} B"
             drv.memcpy_htod(dst, value)
 

@@ -320,6 +320,10 @@ class Module:
         f = _vp(0)
         return _lib.wd_get_function(_vp(self.handle), name.encode(), ctypes.byref(f)) == 0
 
+    def has_global(self, name):
+        p, n = _vp(0), _sz(0)
+        return _lib.wd_get_global(_vp(self.handle), name.encode(), ctypes.byref(p), ctypes.byref(n)) == 0
+
     def get_global(self, name):
         p, n = _vp(0), _sz(0)
         _check(_lib.wd_get_global(_vp(self.handle), name.encode(), ctypes.byref(p), ctypes.byref(n)),

@@ -430,6 +430,13 @@ class Trainer:
             self.update_path[pol] = "kernels"
 
     # --------------------------------------------------------------------------- rollout
+    @property
+    def rollout_path(self):
+        """"one launch": the env's kernel runs the whole batch of ticks with the policies inside it; "per tick": the
+        policy forward, then the tick -- the env's fused tick kernel, or (envs without one, custom environments) the
+        launch plan of sampler, step and reset"""
+        return "one launch" if self._batch_rollout is not None else "per tick"
+
     def _inference_model(self, pol):
         return self.models[pol]
 
