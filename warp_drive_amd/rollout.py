@@ -40,7 +40,8 @@ class UnsupportedRolloutShape(RuntimeError):
 TICK_COHORTS = int(os.environ.get("WD_TICK_COHORTS", "2"))
 # Multi-tick form of the fused tick (TagContinuous, the shape-specialised entry): a run(n >= 2) is ONE launch whose
 # blocks loop over the n ticks of their replica, so no replica waits at a kernel boundary for the slowest one
-# (LaunchPlan.set_multi_tick; docs/rounds/r08.md).  0 = the cohort path exactly as before.
+# (LaunchPlan.set_multi_tick; docs/rounds/r08.md).  0 = the cohort path exactly as before.  A custom env's tick written
+# with include/wd_env_tick.h has the same form (its last argument is the tick count): env.rollout_launch().
 TICK_ROLLOUT = int(os.environ.get("WD_TICK_ROLLOUT", "1"))
 ROLLOUT_MAX_TICKS = 2048  # ticks per launch: ~45 ms at the BASELINE shape; longer runs are split
 COHORT_ALIGN = 32  # cohort boundaries at multiples of 32 replicas: 32 rows of 4 * N bytes are N whole 128-byte lines
@@ -166,9 +167,13 @@ class RolloutEngine:
             self.step_entry = 0
             self.step_kernel_name = fn.name
             self.entry_names.append(fn.name)
+            # replica cohorts: envs whose tick takes a replica range (TagContinuous); the multi-tick form: any fused env
+            # that offers rollout_launch(), with or without ranges (a custom env's tick of include/wd_env_tick.h)
+            ranges = bool(getattr(env_wrapper.env, "TICK_ENV_RANGES", False))
             if (not self.presampled and rollout_policy is None and rollout_batch is None and self.ticks_per_launch == 1
-                    and getattr(env_wrapper.env, "TICK_ENV_RANGES", False)):
-                self._add_cohorts(env_wrapper, sampler, probabilities, E, grid[0], dev)
+                    and (ranges or hasattr(env_wrapper.env, "rollout_launch"))):
+                if ranges:
+                    self._add_cohorts(env_wrapper, sampler, probabilities, E, grid[0], dev)
                 if TICK_ROLLOUT and hasattr(env_wrapper.env, "rollout_launch"):
                     multi = env_wrapper.env.rollout_launch(sampler, probabilities, env_wrapper.env_resetter)
                     if multi is not None:
