@@ -623,7 +623,8 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
                  invK, invN, epb == 1);
   WD_TC_PROBE(12);
   // the sparse form pays when few rows are live (late in an episode); wave-uniform choice
-  const int n_live_rows = __popcll(__ballot(lane < wrows && (l.sig[wrow0 + lane] & 1)));
+  const unsigned long long live_rows = __ballot(lane < wrows && (l.sig[wrow0 + lane] & 1));
+  const int n_live_rows = __popcll(live_rows);
   // (LOOP: a constant pair of its own, WD_TC_LOOP_SPARSE_NUM / 16 -- both forms are valid on any tick, the choice is cost
   // alone, and a free-running block pays for latency where the one-tick kernel pays for bytes: docs/rounds/r30.md)
   constexpr int SPARSE_NUM = LOOP ? WD_TC_LOOP_SPARSE_NUM : 9, SPARSE_DEN = 16;
@@ -634,6 +635,11 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
     } else {
       tc_gather_rows_sparse(a, l, tb, stage, env0, wrow0, wrows, lane, K, N, invK, invN);
     }
+  } else if constexpr (LOOP) {
+    // the same chunks, items and flush as below with what the one built shape fixes taken out of the chunk loop
+    // (tc_rows.h, TcLeanDense)
+    static_assert(!LOOP || (EXACTK && KMAX == 10 && IDB == 7 && SN > 64 && SN <= 128), "two wavefronts, one replica per block");
+    tc_gather_rows_dense_lean<KMAX, SN>(a, l, tb, stage, env0, wave, lane, live_rows);
   } else {
     // observation rows, R rows per chunk: work item = (row, neighbour slot) -> 7 values at
     // row*F + c*K + k of the chunk image; then the time column; then the chunk leaves as one run.

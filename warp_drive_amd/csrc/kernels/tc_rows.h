@@ -11,8 +11,9 @@ namespace {
 // The producer placed dword i of the run at stage[mis + i], mis = (address of dst / 4) & 3, so the
 // 16-byte vectors of the run are 16-byte aligned in LDS and in memory alike; the <= 3 dwords before
 // the first / after the last aligned vector go out as single dwords.
-__device__ __forceinline__ void tc_flush_run(const float *stage, float *dst, int n, int lane) {
-  const int mis = (int)(((size_t)dst >> 2) & 3);
+// (tc_flush_run_at: the same with `mis` given by the caller, who advances it from run to run instead of reading it off
+// the address: the dense form of the multi-tick entry, tc_gather_rows_dense_lean below)
+__device__ __forceinline__ void tc_flush_run_at(const float *stage, float *dst, int mis, int n, int lane) {
   const int head = min(n, (4 - mis) & 3);
   const int nvec = (n - head) >> 2;
   const int tail0 = head + 4 * nvec;
@@ -39,6 +40,9 @@ __device__ __forceinline__ void tc_flush_run(const float *stage, float *dst, int
 #undef WD_TC_STORE_WT
   if (lane < head) dst[lane] = stage[mis + lane];
   if (lane < n - tail0) dst[tail0 + lane] = stage[mis + tail0 + lane];
+}
+__device__ __forceinline__ void tc_flush_run(const float *stage, float *dst, int n, int lane) {
+  tc_flush_run_at(stage, dst, (int)(((size_t)dst >> 2) & 3), n, lane);
 }
 
 // nearest_neighbor_ids rows from the block-local 16-bit ids in LDS: n dwords starting at `dst`, dword i =
@@ -272,6 +276,15 @@ __device__ __forceinline__ void tc_gather_rows_sparse(const TcArgs &a, const TcF
       }
     }
   }
+  // LOOP: what depends on the lane alone (the flush's place in a round) is formed in front of the chunks
+  [[maybe_unused]] int fs = 0;
+  [[maybe_unused]] unsigned sh = 0u;
+  if constexpr (LOOP) {
+    typedef TcLeanRows<KC> D;
+    const bool idle = (fsub >= D::RPR);  // the lanes past RPR * NV: they read slot 0's neighbours and a zero field
+    fs = idle ? 0 : fsub;
+    sh = idle ? 10u : (fv == 0) ? 0u : (fv == D::NV - 2) ? 2u : (fv == D::NV - 1) ? 4u : 6u;
+  }
   // ---- rows of agents in the game
   for (int j0 = 0; j0 < n_rows; j0 += rs) {
     const int rc = min(rs, n_rows - j0);
@@ -283,41 +296,20 @@ __device__ __forceinline__ void tc_gather_rows_sparse(const TcArgs &a, const TcF
       sl[NV - 2] = zero;
       sl[NV - 1] = zero;
     }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      if (64 * u < items) {  // wave-uniform
-        if (lane + 64 * u < items) {
-          const int r = rowlist[j0 + rr[u]];  // row of the item inside the wavefront's rows
-          const unsigned jq = idw[r * K + kk[u]];
-          const TcFeat me = tc_feat_load(l.feat, wrow0 + r);
-          // no neighbour in this slot: the agent's own record stands in, so every difference
-          // below is +0.0 without a select
-          const bool valid = (jq != 0xffffu);
-          const TcFeat nb = tc_feat_load(l.feat, valid ? (int)jq : wrow0 + r);
-          unsigned mv = valid ? 0xffffffffu : 0u;
-          asm volatile("" : "+v"(mv));  // (opaque: keeps the AND below from being turned into selects)
-          const unsigned ts = (unsigned)nb.type_sig & mv;
-          const int mis = (int)((bdw + (unsigned)(r * F)) & 3u);
-          float *o = stage + rr[u] * SL + mis + kk[u];
-          o[0] = (float)(nb.nx - me.nx);   // float64 difference, narrowed (:560)
-          o[K] = (float)(nb.ny - me.ny);
-          o[2 * K] = nb.nsp - me.nsp;      // float32 operands: the float64 difference rounds to this
-          o[3 * K] = nb.nac - me.nac;
-          o[4 * K] = nb.ndir - me.ndir;
-          o[5 * K] = __uint_as_float(ts & 0x3f800000u);
-          o[6 * K] = __uint_as_float((0u - (ts & 1u)) & 0x3f800000u);
-        }
-      }
-    }
     [[maybe_unused]] unsigned desc = 0u;  // LOOP: the descriptor of slot `lane` (see TcLeanRows)
-    if (lane < rc) {
-      // time column: float(t) / episode_length (agents in the game, :474,:493,:543)
-      const int r = rowlist[j0 + lane];
-      const int e_m = (int)(((float)(wrow0 + r) + 0.5f) * invN);
-      const int mis = (int)((bdw + (unsigned)(r * F)) & 3u);
-      stage[lane * SL + mis + 7 * K] = tb.tfrac[e_m];
-      if constexpr (LOOP) {
-        typedef TcLeanRows<KC> D;
+    if constexpr (LOOP) {
+      typedef TcLeanRows<KC> D;
+      // What depends on the row alone is formed once per chunk, by lane j for packed slot j: the row list entry, mis, the
+      // time column (one replica per block: the replica of the row is 0, so tfrac[0] at a uniform address; read here, per
+      // chunk -- held in a register from the top of the function it upsets the allocation of the search, which grows by
+      // 80 instructions: docs/rounds/r35.md) and the descriptor.  The item lanes fetch (row | 4 * mis << 8) of their slot
+      // with one ds_bpermute_b32 per item, issued with every lane active (a disabled source lane reads as 0).
+      unsigned rw = 0u;
+      if (lane < rc) {
+        const int r = rowlist[j0 + lane];
+        const int mis = (int)((bdw + (unsigned)(r * F)) & 3u);
+        stage[lane * SL + mis + 7 * K] = tb.tfrac[0];  // float(t) / episode_length (agents in the game, :474,:493,:543)
+        rw = (unsigned)r | ((unsigned)mis << 10);
         // the neighbouring rows: in the game?  known at all (inside this wavefront's rows)?  The packed order is the
         // row order, so a live neighbour is the previous / next slot unless the chunk ends in between.
         const bool prev_known = (r > 0), next_known = (r + 1 < wrows);
@@ -333,6 +325,66 @@ __device__ __forceinline__ void tc_gather_rows_sparse(const TcArgs &a, const TcF
         desc = head | (a_nv2 << 2) | (a_nv1 << 4) | ((unsigned)D::ACT_FULL << 6) | ((unsigned)mis << 8) |
                ((unsigned)(4 * (r * F - mis + 3)) << 16);
       }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (64 * u < items) {  // wave-uniform
+          const unsigned w = (unsigned)__builtin_amdgcn_ds_bpermute(4 * rr[u], (int)rw);
+          if (lane + 64 * u < items) {
+            const int r = (int)(w & 0xffu);  // row of the item inside the wavefront's rows
+            const unsigned jq = idw[r * K + kk[u]];
+            const TcFeat me = tc_feat_load(l.feat, wrow0 + r);
+            // no neighbour in this slot: the agent's own record stands in, so every difference
+            // below is +0.0 without a select
+            const bool valid = (jq != 0xffffu);
+            const TcFeat nb = tc_feat_load(l.feat, valid ? (int)jq : wrow0 + r);
+            unsigned mv = valid ? 0xffffffffu : 0u;
+            asm volatile("" : "+v"(mv));  // (opaque: keeps the AND below from being turned into selects)
+            const unsigned ts = (unsigned)nb.type_sig & mv;
+            float *o = (float *)((char *)(stage + rr[u] * SL + kk[u]) + (w >> 8));  // (+ mis dwords)
+            o[0] = (float)(nb.nx - me.nx);   // float64 difference, narrowed (:560)
+            o[K] = (float)(nb.ny - me.ny);
+            o[2 * K] = nb.nsp - me.nsp;      // float32 operands: the float64 difference rounds to this
+            o[3 * K] = nb.nac - me.nac;
+            o[4 * K] = nb.ndir - me.ndir;
+            o[5 * K] = __uint_as_float(ts & 0x3f800000u);
+            o[6 * K] = __uint_as_float((0u - (ts & 1u)) & 0x3f800000u);
+          }
+        }
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        if (64 * u < items) {  // wave-uniform
+          if (lane + 64 * u < items) {
+            const int r = rowlist[j0 + rr[u]];  // row of the item inside the wavefront's rows
+            const unsigned jq = idw[r * K + kk[u]];
+            const TcFeat me = tc_feat_load(l.feat, wrow0 + r);
+            // no neighbour in this slot: the agent's own record stands in, so every difference
+            // below is +0.0 without a select
+            const bool valid = (jq != 0xffffu);
+            const TcFeat nb = tc_feat_load(l.feat, valid ? (int)jq : wrow0 + r);
+            unsigned mv = valid ? 0xffffffffu : 0u;
+            asm volatile("" : "+v"(mv));  // (opaque: keeps the AND below from being turned into selects)
+            const unsigned ts = (unsigned)nb.type_sig & mv;
+            const int mis = (int)((bdw + (unsigned)(r * F)) & 3u);
+            float *o = stage + rr[u] * SL + mis + kk[u];
+            o[0] = (float)(nb.nx - me.nx);   // float64 difference, narrowed (:560)
+            o[K] = (float)(nb.ny - me.ny);
+            o[2 * K] = nb.nsp - me.nsp;      // float32 operands: the float64 difference rounds to this
+            o[3 * K] = nb.nac - me.nac;
+            o[4 * K] = nb.ndir - me.ndir;
+            o[5 * K] = __uint_as_float(ts & 0x3f800000u);
+            o[6 * K] = __uint_as_float((0u - (ts & 1u)) & 0x3f800000u);
+          }
+        }
+      }
+      if (lane < rc) {
+        // time column: float(t) / episode_length (agents in the game, :474,:493,:543)
+        const int r = rowlist[j0 + lane];
+        const int e_m = (int)(((float)(wrow0 + r) + 0.5f) * invN);
+        const int mis = (int)((bdw + (unsigned)(r * F)) & 3u);
+        stage[lane * SL + mis + 7 * K] = tb.tfrac[e_m];
+      }
     }
     asm volatile("" ::: "memory");
     __builtin_amdgcn_wave_barrier();
@@ -342,9 +394,6 @@ __device__ __forceinline__ void tc_gather_rows_sparse(const TcArgs &a, const TcF
       typedef TcLeanRows<KC> D;
       static_assert(D::RPR == 3 && D::NV == 19 && D::F == 71 && D::SL == 76 && D::RS == 17, "built for K = 10");
       constexpr int W = 3;
-      const bool idle = (fsub >= D::RPR);  // the lanes past RPR * NV: they read slot 0's neighbours and a zero field
-      const int fs = idle ? 0 : fsub;
-      const unsigned sh = idle ? 10u : (fv == 0) ? 0u : (fv == D::NV - 2) ? 2u : (fv == D::NV - 1) ? 4u : 6u;
       for (int sb = 0; sb < rc; sb += W * D::RPR) {
         unsigned dd[W];
         v4f q[W], nx[W];
@@ -434,6 +483,105 @@ __device__ __forceinline__ void tc_gather_rows_sparse(const TcArgs &a, const TcF
     }
     asm volatile("" ::: "memory");
     __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// ---- observation rows of one wavefront, DENSE form, as the multi-tick entry builds them (one shape: SN agents in two
+// wavefronts, one replica per block).  The same items, the same staging image and the same flush (tc_flush_run) as the
+// chunk loop of tc_fast.h, which the one-tick entries keep; what the shape fixes is not worked out per chunk:
+//   * the chunk plan: NCH chunks of R rows, the last one of LAST0 / LAST1 rows.  Every chunk has more than 128 items, so
+//     the first two items of a lane always exist; only the third can lie past the end (lanes 62 and 63 of a full chunk,
+//     more lanes of the last one).  Such a lane computes its second item twice -- the same values to the same place, as
+//     the generic loop recomputes the chunk's last item -- chosen by one compare per chunk; no item index is clamped and
+//     no (row, offset) split is redone.
+//   * whether the row's own agent is in the game: bit r of `live`, the vote over l.sig the caller has just taken, instead
+//     of bit 0 of the own record's type_sig.  Both are written from the same register on the same trip (tc_fast.h:
+//     m.ft.type_sig and l.sig[li] take `sg`), so the neighbour's address no longer waits for the own record, and there is
+//     no branch around the neighbour reads: a row out of the game takes the "own record stands in" select, every
+//     difference is +0.0 and the type bits are masked, as before.
+//   * the time column: one replica per block, so the row's replica is 0 and tfrac[0] is read once; the live test per row
+//     is the same bit of `live`.
+//   * dst, mis, the id row and the first record advance by constants from chunk to chunk.
+template <int KC, int SN>
+struct TcLeanDense {
+  static constexpr int F = 7 * KC + 1;
+  static constexpr int R = WD_TC_STAGE_TARGET / (4 * F);           // tc_stage_rows: blocks of at most four wavefronts
+  static constexpr int ROWS0 = (SN + 1) / 2, ROWS1 = SN - ROWS0;   // the even split of tc_fast.h
+  static constexpr int NCH = (ROWS0 + R - 1) / R;
+  static constexpr int LAST0 = ROWS0 - (NCH - 1) * R, LAST1 = ROWS1 - (NCH - 1) * R;
+  static_assert(R >= 1 && R <= 32 && R * KC <= 192 && R * KC > 128, "at most three items per lane; bit tests on 32 bits");
+  static_assert((ROWS1 + R - 1) / R == NCH && LAST1 >= 1 && LAST1 <= LAST0 && LAST0 <= R, "both wavefronts: NCH chunks");
+  static_assert(LAST1 * KC > 128, "the first two items of a lane exist in every chunk");
+  static_assert(4 * R * F + 12 <= WD_TC_STAGE_TARGET + 16, "a chunk image at any alignment fits the staging buffer");
+};
+
+template <int KC, int SN>
+__device__ __forceinline__ void tc_gather_rows_dense_lean(const TcArgs &a, const TcFastLds &l, const TcTables &tb,
+                                                          float *stage, int env0, int wave, int lane,
+                                                          unsigned long long live) {
+  typedef TcLeanDense<KC, SN> D;
+  constexpr int K = KC, F = D::F, R = D::R, U = 3;
+  const int wrow0 = wave * D::ROWS0;
+  const int last_rows = wave ? D::LAST1 : D::LAST0;  // wave-uniform
+  int t0[U], r0[U], s0[U];  // item, its row in the chunk, offset of its first value in the chunk image
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    t0[u] = lane + 64 * u;
+    r0[u] = (int)((unsigned)t0[u] / (unsigned)K);
+    s0[u] = r0[u] * F + (t0[u] - r0[u] * K);
+  }
+  float *dst = a.obs + ((long)env0 * SN + wrow0) * F;
+  int mis = (int)(((size_t)dst >> 2) & 3);
+  const unsigned short *idp = l.ids + wrow0 * K;  // ids of item t: idp[t]
+  int fp = wrow0;
+  const float tfrac = tb.tfrac[0];
+#pragma nounroll
+  for (int c = 0; c < D::NCH; ++c) {
+    const int rc = (c == D::NCH - 1) ? last_rows : R;
+    // a lane whose third item lies past the end of the chunk computes its second item twice
+    const bool past = lane + 128 >= rc * K;
+    const int tt[U] = {t0[0], t0[1], past ? t0[1] : t0[2]}, rr[U] = {r0[0], r0[1], past ? r0[1] : r0[2]},
+              so[U] = {s0[0], s0[1], past ? s0[1] : s0[2]};
+    const unsigned lv = (unsigned)live;  // bit r: row r of the chunk belongs to an agent in the game
+    // the three ids first; then one item after the other, its two records in flight together.  (All six records of a
+    // lane in flight at once, as the source of tc_fast.h asks for, is what the compiler did NOT build there -- its
+    // branch on the own record serialised them -- and costs 45 registers here: the object then needs 128 VGPRs and the
+    // search, allocated around that peak, grows by 66 instructions.  Read off the object; docs/rounds/r35.md.)
+    unsigned jq[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) jq[u] = idp[tt[u]];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int m = fp + rr[u];
+      const TcFeat me = tc_feat_load(l.feat, m);
+      // no neighbour (or the agent is out of the game): its own record stands in, so every
+      // difference below is +0.0 without a select
+      const bool valid = (((lv >> rr[u]) & 1u) != 0u) && (jq[u] != 0xffffu);
+      const TcFeat nb = tc_feat_load(l.feat, valid ? (int)jq[u] : m);
+      unsigned mv = valid ? 0xffffffffu : 0u;
+      asm volatile("" : "+v"(mv));  // (opaque: keeps the AND below from being turned into selects)
+      const unsigned ts = (unsigned)nb.type_sig & mv;
+      float *o = stage + mis + so[u];
+      o[0] = (float)(nb.nx - me.nx);   // float64 difference, narrowed (:560)
+      o[K] = (float)(nb.ny - me.ny);
+      o[2 * K] = nb.nsp - me.nsp;      // float32 operands: the float64 difference rounds to this
+      o[3 * K] = nb.nac - me.nac;
+      o[4 * K] = nb.ndir - me.ndir;
+      o[5 * K] = __uint_as_float(ts & 0x3f800000u);
+      o[6 * K] = __uint_as_float((0u - (ts & 1u)) & 0x3f800000u);
+    }
+    // time column: float(t) / episode_length for agents in the game, else 0 (:474,:493,:543)
+    if (lane < rc) stage[mis + lane * F + 7 * K] = ((lv >> lane) & 1u) ? tfrac : 0.0f;
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    tc_flush_run_at(stage, dst, mis, rc * F, lane);
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    dst += R * F;
+    mis = (mis + R * F) & 3;
+    idp += R * K;
+    fp += R;
+    live >>= R;
   }
 }
 
