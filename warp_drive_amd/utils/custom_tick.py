@@ -110,3 +110,134 @@ class FusedTickMixin:
         """the same launch as the multi-tick form of a launch plan: its last argument, the tick count, is rewritten per
         run (LaunchPlan.set_multi_tick)"""
         return self.tick_launch(sampler, probabilities, resetter)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The ONE-LAUNCH ROLLOUT with the policy inside the kernel (docs/custom_environments.md, "A policy inside the kernel"):
+# the launch of a `Hip<Name>Rollout_H<width>` entry written with include/wd_env_rollout.h.
+MAX_ACTIONS = 8  # WD_ROLLOUT_MAX_ACTIONS of include/wd_env_rollout.h
+
+
+def rollout_policy_floats(obs_size, width, n_actions):
+    """elements of the packed policy (training.policy_kernel.pack_rollout_policy; wd_rollout_policy_floats of the header)"""
+    F, H, A = int(obs_size), int(width), int(n_actions)
+    return F * H + H + H * H + H + A * H + A
+
+
+def custom_rollout_launch(env, kernel_name, step_args, sampler, n_actions, packed, width, resetter, batch, ticks):
+    """(function, arguments, block, grid, dynamic LDS bytes) of `kernel_name`, an entry whose parameters are the step's
+    own -- `step_args` -- followed by WD_ROLLOUT_PARAMS: RNG state, packed policy, action count, reset table and its entry
+    count, stream tag, the four batch tensors (observations [T, E, N, F] float32, actions [T, E, N, 1] int32, rewards
+    [T, E, N] float32, done [T, E] int32, T >= ticks), and the tick count LAST (np.int32).  packed: the contiguous float32
+    CUDA tensor of pack_rollout_policy for hidden width `width`.  Dynamic LDS: 4 bytes per packed float, rounded up
+    to 16."""
+    import torch
+
+    from warp_drive_amd.managers.function_manager import _stream_tag
+    from warp_drive_amd.utils.constants import Constants
+
+    who = f"{type(env).__name__} ({kernel_name})"
+    width, n_actions, ticks = int(width), int(n_actions), int(ticks)
+    if not 1 <= n_actions <= MAX_ACTIONS:
+        raise UnsupportedRolloutShape(f"{who}: {n_actions} actions were asked of the in-kernel policy of "
+                                      f"wd_env_rollout.h (1 to {MAX_ACTIONS})")
+    if ticks < 1:
+        raise UnsupportedRolloutShape(f"{who}: a launch of {ticks} ticks was asked")
+    fm, dm = env.cuda_function_manager, env.cuda_data_manager
+    E, N = int(dm.meta_info("n_envs")), int(env.num_agents)
+    F = int(dm.get_shape(Constants.OBSERVATIONS)[-1])
+    n_w = rollout_policy_floats(F, width, n_actions)
+    if not (getattr(packed, "is_cuda", False) and packed.dtype == torch.float32 and packed.is_contiguous()
+            and packed.numel() == n_w):
+        raise UnsupportedRolloutShape(f"{who}: the packed policy must be a contiguous float32 CUDA tensor of {n_w} elements "
+                                      f"(observation {F}, width {width}, {n_actions} actions)")
+    if batch is None:
+        raise UnsupportedRolloutShape(f"{who}: the batch tensors are missing; the rollout records every tick")
+    want = {"obs": ((E, N, F), torch.float32), "actions": ((E, N, 1), torch.int32), "rewards": ((E, N), torch.float32),
+            "done": ((E,), torch.int32)}
+    for key, (shape, dtype) in want.items():
+        t = batch.get(key) if hasattr(batch, "get") else None
+        if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and t.shape[0] >= ticks
+                and tuple(t.shape[1:]) == shape):
+            got = None if t is None else (tuple(getattr(t, "shape", ())), getattr(t, "dtype", None))
+            raise UnsupportedRolloutShape(f"{who}: batch[{key!r}] must be a contiguous {dtype} CUDA tensor "
+                                          f"[>= {ticks}, {', '.join(map(str, shape))}], not {got}")
+    fm.initialize_functions([kernel_name])
+    fn = fm.get_function(kernel_name)
+    _, reset_args, _, _ = resetter.fused_launch(dm, 0, 0)  # builds / refreshes the descriptor table
+    table, n_arrays = reset_args[0], reset_args[1]
+    args = list(env.cuda_step_function_feed(step_args))
+    args += [sampler.rng_state, packed, np.int32(n_actions), table, np.int32(n_arrays), _stream_tag("tick"),
+             batch["obs"], batch["actions"], batch["rewards"], batch["done"], np.int32(ticks)]
+    return fn, args, tick_block(N), fm.grid, (4 * n_w + 15) // 16 * 16
+
+
+class FusedRolloutMixin(FusedTickMixin):
+    """`has_live_policy_rollout()` and the `tick_launch(batch=..., policy=...)` form for an env class whose device source
+    has, next to its fused tick entry, the entries `Hip<Name>Rollout_H<width>` written with include/wd_env_rollout.h.
+    The class says ROLLOUT_KERNEL, a pattern with `{width}`; the entries' parameters are TICK_STEP_ARGS followed by
+    WD_ROLLOUT_PARAMS.  `Trainer` takes the one launch under `trainer.fused_rollout_policy: "all"` only."""
+
+    ROLLOUT_KERNEL = None
+    ROLLOUT_POLICY_WIDTHS = (32, 64)
+    ROLLOUT_MAX_THREADS = {32: 1024, 64: 512}  # the entries' __launch_bounds__: override to match the source
+    ROLLOUT_POLICY_OPT_IN = True
+    ticks_per_launch = 1
+
+    def _rollout_refusal(self, width, n_actions):
+        """why this env / shape has no in-kernel policy of hidden width `width` with `n_actions` actions; None: it has"""
+        space = self.action_space[0]
+        if not isinstance(space, Discrete):
+            return f"an action space of type {type(space).__name__} (one Discrete head only)"
+        if not 1 <= int(n_actions) <= MAX_ACTIONS:
+            return f"{int(n_actions)} actions (1 to {MAX_ACTIONS})"
+        if int(width) not in tuple(self.ROLLOUT_POLICY_WIDTHS) or int(width) not in self.ROLLOUT_MAX_THREADS:
+            return f"a hidden width of {int(width)} (entries: {sorted(self.ROLLOUT_POLICY_WIDTHS)})"
+        threads = tick_block(self.num_agents)[0]
+        if threads > int(self.ROLLOUT_MAX_THREADS[int(width)]):
+            return (f"a block of {threads} threads ({self.num_agents} agents) over the launch bound "
+                    f"{self.ROLLOUT_MAX_THREADS[int(width)]} of the width-{int(width)} entry")
+        if len(self.cuda_data_manager.reset_target_to_pool) > 0:
+            return "a reset pool"
+        name = self.ROLLOUT_KERNEL.format(width=int(width))
+        if not self.cuda_function_manager.has_function(name):
+            return f"the entry {name}, which the env's code object does not have"
+        return None
+
+    def has_live_policy_rollout(self, width, n_actions):
+        """does an entry exist that evaluates a policy of hidden width `width` with `n_actions` actions for this env's
+        shape?  (RolloutEngine and Trainer ask before they call `tick_launch(policy=...)`)"""
+        return self._rollout_refusal(width, n_actions) is None
+
+    def tick_launch(self, sampler, probabilities, resetter, env_range=None, batch=None, policy=None, **extra):
+        """with `batch` and `policy` = (packed weights, hidden width): `ticks_per_launch` ticks in ONE launch of the
+        Rollout entry of that width; with neither: the parent's fused tick"""
+        if batch is None and policy is None:
+            return super().tick_launch(sampler, probabilities, resetter, env_range=env_range, **extra)
+        who = f"{type(self).__name__} ({self.ROLLOUT_KERNEL})"
+        if env_range is not None:
+            raise UnsupportedRolloutShape(f"{who}: a replica range {tuple(env_range)} was asked; the rollout of "
+                                          "wd_env_rollout.h runs all replicas")
+        asked = {"actor": "an in-kernel actor", "mean_batch": "an in-kernel actor's record of means",
+                 "ou_params": "a Box action space (the OU draw)"}
+        for key in extra:
+            raise UnsupportedRolloutShape(f"{who}: {asked.get(key, repr(key))} was asked; the rollout of "
+                                          "wd_env_rollout.h has no such variant")
+        if batch is None:
+            raise UnsupportedRolloutShape(f"{who}: an in-kernel policy without the batch tensors was asked; the rollout "
+                                          "records every tick")
+        if policy is None:
+            raise UnsupportedRolloutShape(f"{who}: a batch recorded inside the kernel without an in-kernel policy was "
+                                          "asked; the fused tick of wd_env_tick.h records nothing")
+        try:
+            packed, width = policy
+            width = int(width)
+        except (TypeError, ValueError) as err:
+            raise UnsupportedRolloutShape(f"{who}: policy = (packed weights, hidden width), not {policy!r}") from err
+        space = self.action_space[0]
+        n_actions = int(space.n) if isinstance(space, Discrete) else 0
+        why = self._rollout_refusal(width, n_actions)
+        if why is not None:
+            raise UnsupportedRolloutShape(f"{who}: {why} was asked of the in-kernel policy of wd_env_rollout.h")
+        return custom_rollout_launch(self, self.ROLLOUT_KERNEL.format(width=width), self.TICK_STEP_ARGS, sampler,
+                                     n_actions, packed, width, resetter, batch, int(self.ticks_per_launch))
