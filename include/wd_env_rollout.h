@@ -45,7 +45,10 @@
 // The launch asks for 4 bytes of dynamic LDS per float, rounded up to 16.
 //
 // PARITY CONTRACT (what a host restatement reproduces; tests/custom_rollout_model.py is one):
-//   * every unit: acc = bias, then ONE fmaf per input in index order (float32); ReLU as fmaxf(acc, 0);
+//   * every unit: acc = bias, then ONE fmaf per input in index order (float32); ReLU as fmaxf(acc, 0) -- C's fmaxf, which
+//     returns the other operand for a NaN: a NaN activation (non-finite weights) becomes 0, on the device and in a host
+//     build alike, where numpy's maximum hands the NaN on; the contract is stated for finite weights, and whatever the
+//     sums are, the pick stays in [0, A);
 //   * softmax: the logits as above, their maximum subtracted, expf, the sum of the terms in action order starting from
 //     0, ONE division e[a] / sum per action;
 //   * running sums: cum = p[0], then cum + p[a] in action order;
@@ -64,8 +67,10 @@
 // restart) stored.  A row is read back by the same block that wrote it, behind the two barriers of wd_rollout_end (each
 // also a memory fence over the block): what the step stored is visible to the restart, what the restart stored -- by
 // whichever thread -- is visible to the next tick's read.  wd_rollout_end records `rewards_arr[row]` BEFORE the restart
-// restores anything, as an author may have registered `rewards` for reset: the restart copies element i of a row with
-// thread i, so the thread that restores an agent's reward is the thread that has just recorded it.  The notes of
+// restores anything, as an author may have registered `rewards` for reset (create_and_push_data_placeholders and Trainer
+// register it WITHOUT a reset copy; an author who pushes the placeholders by hand may give it one): the restart copies
+// element i of a row with thread i, so the thread that restores an agent's reward is the thread that has just recorded
+// it.  The notes of
 // wd_env_tick.h on `__restrict__` and on hand-overs through global memory within a tick hold here as well.
 #ifndef WD_ENV_ROLLOUT_H_
 #define WD_ENV_ROLLOUT_H_

@@ -53,12 +53,20 @@ static int rows(const float *w, int A, int R) {
 int main() {
   int H, F, A, R;
   if (scanf("%d %d %d %d", &H, &F, &A, &R) != 4) return 2;
-  if (A < 1 || A > WD_ROLLOUT_MAX_ACTIONS || R < 0 || (H != 32 && H != 64) || (F != 2 && F != 5)) return 3;
+  if (A < 1 || A > WD_ROLLOUT_MAX_ACTIONS || R < 0 || H < 4 || H > 64 || F < 1 || F > 7) return 3;
   std::vector<float> w(wd_rollout_policy_floats(F, H, A));
   for (float &v : w)
     if (!read_float(&v)) return 2;
+  // the worked example (F = 5), tests/custom_envs/policy_probe.hip (F = 2) ...
   if (H == 32 && F == 5) return rows<32, 5>(w.data(), A, R);
   if (H == 64 && F == 5) return rows<64, 5>(w.data(), A, R);
   if (H == 32 && F == 2) return rows<32, 2>(w.data(), A, R);
-  return rows<64, 2>(w.data(), A, R);
+  if (H == 64 && F == 2) return rows<64, 2>(w.data(), A, R);
+  // ... and the (F, H) of tests/custom_envs/contract_probe.hip
+  if (H == 4 && F == 1) return rows<4, 1>(w.data(), A, R);
+  if (H == 32 && F == 1) return rows<32, 1>(w.data(), A, R);
+  if (H == 32 && F == 4) return rows<32, 4>(w.data(), A, R);
+  if (H == 32 && F == 7) return rows<32, 7>(w.data(), A, R);
+  if (H == 64 && F == 7) return rows<64, 7>(w.data(), A, R);
+  return 3;
 }
