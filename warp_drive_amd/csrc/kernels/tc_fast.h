@@ -225,6 +225,13 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
           l.xy[N] = make_float2(__builtin_nanf(""), 0.0f);     // what a remembered id of 0xffff (none) reads
         }
       }
+      if constexpr (LOOP) {
+        // the pad candidates of wavefront 1's two half chains (the search below, "LANE HALVES"): places n_live ..
+        // 2 h - 1, at most seven, one per lane of the first eight.  2 h <= 96 and the chain's last prefetch ends at
+        // 2 h + 7 <= 103: inside the NP = 116 places of xyc
+        if (tc_lane_halves(compact, n_waves, n_live) && ag < 8 && n_live + ag < 2 * tc_half_len(n_live))
+          l.xyc[n_live + ag] = make_float2(WD_BIG, WD_BIG);
+      }
     }
     tc_feat_store(l.feat, li, m.ft);
     // bit 0: in the game before this tick's tagging; bit 1: the observation row in HBM is all zeros already
@@ -423,13 +430,61 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
       WD_TC_PROBE(8);
     }
   }
-  if (!prefiltered && (searcher || (helper && lane < n_live))) {
+  bool half_lane = false;  // LOOP: this lane chains half of the candidates for a searcher of wavefront 1 (LANE HALVES)
+  int half_up = 0;         //       and its candidates start here
+  if constexpr (LOOP) {
+    // LANE HALVES (the multi-tick entry, 65 .. 96 agents in the game): wavefront 1 holds n_live - 64 <= 32 searchers, and
+    // ran the chain over all n_live candidates with at most half of its lanes at work -- on a VALU that the other
+    // wavefronts of its SIMD are waiting for.  Lane l + 32 now works for the searcher of lane l: the lower lanes chain
+    // the candidates [0, h), the upper lanes [h, 2 h), h = tc_half_len(n_live), in ONE call of the chain -- the same
+    // groups for every lane, from a per-lane base, so that the indices in the upper lanes' keys are h too low until h
+    // is added to the L keys that come out (they stay ascending: all L slots hold candidates, h >= 36 > L, and an index
+    // of at most 2 h - 1 <= 95 carries nothing out of the low 7 bits).  The places n_live .. 2 h - 1 hold pad candidates
+    // at (BIG, BIG) (the move phase): their keys are +inf with an index, behind the key of every candidate there is --
+    // the candidates are the agents IN the game, whose positions are clipped to the arena, so no two of them are
+    // infinitely far apart -- and at least 65 > L keys are real: no pad is among the L smallest of the union.  The halves
+    // swap their lists (v_permlane32_swap) and merge them: the L smallest of the union, which is exactly what one chain
+    // over all candidates keeps (the argument of the cross-wavefront split above), ids and their tie-break order
+    // included since they ride in the keys.  Wavefront 0 is as it was; the priority drops where the chain drops it.
+    const bool halves = tc_lane_halves(compact, n_waves, n_live) && (wave == 1);   // wave-uniform
+    const int h_len = tc_half_len(n_live);
+    half_lane = halves && ((lane & 31) < n_live - 64);
+    half_up = (halves && lane >= 32) ? h_len : 0;
+    if (searcher || (helper && lane < n_live) || half_lane) {
+      const int me = helper ? lane : halves ? 64 + (lane & 31) : ag;
+      tc_chain_range<L, IDB>(sxy + half_up, sxy[me].x, sxy[me].y, helper ? j_half : 0,
+                             helper ? n_cand : halves ? h_len : j_half, S);
+    }
+  } else if (!prefiltered && (searcher || (helper && lane < n_live))) {
     // one pass with packed keys (this wavefront's share of the candidates)
     const int me = helper ? lane : ag;
     tc_chain_range<L, IDB>(sxy, sxy[me].x, sxy[me].y, helper ? j_half : 0, helper ? n_cand : j_half, S);
   }
   WD_TC_PROBE(9);
-  if (split) {  // block-uniform
+  if constexpr (LOOP) {
+    // the partner's list comes from wavefront 1 (the split over the wavefronts) or from the other half of the lanes; ONE
+    // merge serves both
+    unsigned P[L];
+    bool merge = false;
+    if (split) {  // block-uniform
+      if (helper && lane < n_live) {
+#pragma unroll
+        for (int k = 0; k < L; ++k) ((unsigned *)stage)[64 * k + lane] = S[k];
+        __builtin_amdgcn_s_setprio(0);
+      }
+      __syncthreads();
+      if (searcher) {
+        const unsigned *const theirs = (const unsigned *)(l.stage + (size_t)l.stage_dwords);  // wavefront 1's buffer
+#pragma unroll
+        for (int k = 0; k < L; ++k) P[k] = theirs[64 * k + lane];
+        merge = true;
+      }
+    } else if (half_lane) {
+      tc_swap_lane_halves<L>(S, P, (unsigned)half_up);
+      merge = true;
+    }
+    if (merge) tc_merge_sorted<L>(S, P);
+  } else if (split) {  // block-uniform
     if (helper && lane < n_live) {
 #pragma unroll
       for (int k = 0; k < L; ++k) ((unsigned *)stage)[64 * k + lane] = S[k];

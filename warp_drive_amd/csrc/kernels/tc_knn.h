@@ -427,6 +427,28 @@ __device__ __forceinline__ void tc_merge_sorted(unsigned (&S)[L], const unsigned
   for (int k = 0; k < L; ++k) S[k] = c[k];
 }
 
+// ---- LANE HALVES (the multi-tick entry only, tc_fast.h): while 65 .. 96 agents are in the game the second wavefront of a
+// two-wavefront block holds at most 32 searchers, and lane l + 32 chains the second half of the candidates for the searcher
+// of lane l.  h = the candidates per half: a multiple of 4 (whole groups of the chain), 2 h >= n_live, 2 h <= n_live + 7.
+__device__ __forceinline__ bool tc_lane_halves(bool compact, int n_waves, int n_live) {
+  return compact && (n_waves == 2) && (n_live > 64) && (n_live <= 96);  // block-uniform
+}
+__device__ __forceinline__ int tc_half_len(int n_live) { return ((n_live + 7) >> 3) << 2; }
+// the upper lanes' keys get their indices' offset `up` (0 in the lower lanes); then v_permlane32_swap of each key with a
+// copy of itself leaves the lower lanes' keys in S and the upper lanes' keys in P, in BOTH halves of the wavefront (the
+// instruction swaps lanes 32 .. 63 of its first register with lanes 0 .. 31 of its second): lane l holds its own list and
+// that of lane l + 32, ready for tc_merge_sorted.  The upper lanes hold the same pair; what they make of it is not used.
+template <int L>
+__device__ __forceinline__ void tc_swap_lane_halves(unsigned (&S)[L], unsigned (&P)[L], unsigned up) {
+#pragma unroll
+  for (int k = 0; k < L; ++k) {
+    const unsigned s = S[k] + up;
+    const auto r = __builtin_amdgcn_permlane32_swap(s, s, false, false);
+    S[k] = r[0];
+    P[k] = r[1];
+  }
+}
+
 // ---- PREFILTERED search for replicas of more than 128 agents (round 4; one replica per block, K <= 12, used while at
 // least WD_TC_PRE_MIN_LIVE agents are in the game).  The chain costs 13 median-of-three (~3 cycles each with the VALU
 // saturated) + 6 cheap instructions per candidate and searcher and is VALU-bound on all sixteen wavefronts of a
