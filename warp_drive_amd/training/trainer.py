@@ -30,6 +30,7 @@ from warp_drive_amd.rollout import RolloutEngine, UnsupportedRolloutShape
 from warp_drive_amd.training.data_loader import create_and_push_data_placeholders
 from warp_drive_amd.training.grad_bucket import GradientBucket
 from warp_drive_amd.training.losses import A2C, PPO
+from warp_drive_amd.training import pg_update_custom_kernels as pgck
 from warp_drive_amd.training import pg_update_gridworld_kernels as pggk
 from warp_drive_amd.training import pg_update_kernels as pguk
 from warp_drive_amd.training import update_kernels
@@ -385,7 +386,10 @@ class Trainer:
         (`_pg_adam`; `self.optimizers[pol]` is then never stepped).  A policy that rule refuses is offered to
         training/pg_update_gridworld_kernels.py::admitted_gridworld_shape -- the policies of the one-launch TagGridWorld
         rollout: any number of them, n agents each, the same five launches per trained policy on its own batch tensors, the
-        refill in pack_gridworld_policy's layout.  Any other policy logs the reason once and stays on today's path;
+        refill in pack_gridworld_policy's layout.  A policy both refuse is offered to
+        training/pg_update_custom_kernels.py::admitted_custom_shape and to the env object's `update_kernels_refusal` -- a
+        custom environment whose code object has the update entries of include/wd_env_update.h, which then builds the
+        launches itself (`update_kernels`).  Any other policy logs the reason once and stays on today's path;
         `update_path` says which, per policy (it may be mixed)."""
         if tcfg.get("fused_update", True) != "all" or self.device.type != "cuda":
             return
@@ -414,14 +418,31 @@ class Trainer:
                     pcfg["algorithm"])
                 if not gridworld and self._batch_rollout is not None and self._batch_rollout["pack"] is pack_gridworld_policy:
                     why = gw_why   # (a gridworld policy is told what the gridworld kernels miss, not that it has 5 agents)
-            if not ok and not gridworld:
+            custom = False
+            offers = getattr(env_wrapper.env, "update_kernels_refusal", None)
+            if not ok and not gridworld and offers is not None:
+                # ... or the policy of a custom environment whose own code object has the update entries of
+                # include/wd_env_update.h (training/pg_update_custom_kernels.py: one policy, n agents, 1 .. 32 observation
+                # floats, 1 .. 8 actions); the env object says whether it has them for this shape
+                custom, why = pgck.admitted_custom_shape(
+                    self._batch_rollout is not None,
+                    self._batch_rollout is not None and self._batch_rollout["pack"] is pack_rollout_policy,
+                    len(self.policies), len(ids), self.head_sizes, pcfg["model"]["fc_dims"], obs_size, dtype,
+                    bool(pcfg["normalize_return"]), bool(pcfg["normalize_advantage"]), self.neg_pos_env_ratio, self.world,
+                    pcfg["algorithm"])
+                if custom:
+                    custom, why = offers(int(pcfg["model"]["fc_dims"][0]), obs_size, int(self.head_sizes[0]))
+            if not ok and not gridworld and not custom:
                 if self.rank == 0:
                     pguk.log_refusal(pol, why)
                 continue
             flat = pguk.FlatPolicy(self.models[pol])
             self._pg_flat[pol] = flat
             self._pg_adam[pol] = {"step": 0, "exp_avg": torch.zeros_like(flat.flat), "exp_avg_sq": torch.zeros_like(flat.flat)}
-            if gridworld:
+            if custom:
+                self._pg_kernels[pol] = env_wrapper.env.update_kernels(self.num_envs, self.batch_len, len(ids), flat.H, flat.O,
+                                                                       flat.A, self.device)
+            elif gridworld:
                 self._pg_kernels[pol] = pggk.PgGridworldUpdateKernels(env_wrapper.cuda_function_manager, self.num_envs,
                                                                       self.batch_len, len(ids), flat.H, self.device)
             else:

@@ -8,6 +8,9 @@ What the kit does not do is refused with `UnsupportedRolloutShape`, never silent
 recorded inside the kernel, a policy or an actor evaluated inside the kernel, presampled actions, Box action spaces,
 more than four heads.  An env with a reset pool needs nothing from here: `RolloutEngine` keeps the per-tick plan for it
 (the mixin does not set TICK_POOL_RESET).
+
+Further down: `FusedRolloutMixin` (the one-launch rollout with the policy inside the kernel, include/wd_env_rollout.h) and
+`FusedUpdateMixin` (the A2C / PPO update as five launches, include/wd_env_update.h).
 """
 import numpy as np
 
@@ -241,3 +244,49 @@ class FusedRolloutMixin(FusedTickMixin):
             raise UnsupportedRolloutShape(f"{who}: {why} was asked of the in-kernel policy of wd_env_rollout.h")
         return custom_rollout_launch(self, self.ROLLOUT_KERNEL.format(width=width), self.TICK_STEP_ARGS, sampler,
                                      n_actions, packed, width, resetter, batch, int(self.ticks_per_launch))
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The UPDATE AS KERNELS (docs/custom_environments.md, "The update as kernels"): the six entries the macro
+# WD_PG_UPDATE_ENTRIES(Name, F) of include/wd_env_update.h defines in the env's own code object.
+class FusedUpdateMixin(FusedRolloutMixin):
+    """`update_kernels_refusal()` and `update_kernels()` for an env class whose device source has, next to its Rollout
+    entries, the update entries of include/wd_env_update.h.  The class says UPDATE_KERNEL_PREFIX -- "Hip<Name>Pg", the
+    macro's first argument between "Hip" and "Pg" -- and UPDATE_OBS_SIZE, the macro's second argument: the observation
+    floats of a row the entries were COMPILED for.  `Trainer` takes the five launches under
+    `trainer.fused_update: "all"` only, on top of the one-launch rollout."""
+
+    UPDATE_KERNEL_PREFIX = None
+    UPDATE_OBS_SIZE = None
+
+    def update_kernels_refusal(self, width, obs_size, n_actions):
+        """(True, "") when this env's code object has update entries for a policy of hidden width `width` on `obs_size`
+        observation floats with `n_actions` actions, else (False, why)"""
+        from warp_drive_amd.training import pg_update_custom_kernels as pgck
+
+        who = type(self).__name__
+        if not self.UPDATE_KERNEL_PREFIX or self.UPDATE_OBS_SIZE is None:
+            return False, f"{who} names no update entries (UPDATE_KERNEL_PREFIX, UPDATE_OBS_SIZE)"
+        if int(width) not in pgck.HIDDEN:
+            return False, f"hidden width {int(width)}: the update entries of wd_env_update.h exist for {list(pgck.HIDDEN)}"
+        if not 1 <= int(n_actions) <= pgck.MAX_ACTIONS:
+            return False, f"{int(n_actions)} actions: the update entries take 1 to {pgck.MAX_ACTIONS}"
+        if not 1 <= int(self.UPDATE_OBS_SIZE) <= pgck.MAX_OBS:
+            return False, f"{who}.UPDATE_OBS_SIZE = {self.UPDATE_OBS_SIZE}: the update entries take 1 to {pgck.MAX_OBS}"
+        if int(obs_size) != int(self.UPDATE_OBS_SIZE):
+            return False, (f"observation size {int(obs_size)}: the update entries of {who} were compiled for "
+                           f"{int(self.UPDATE_OBS_SIZE)}")
+        for name in pgck.all_kernel_names(self.UPDATE_KERNEL_PREFIX):
+            if not self.cuda_function_manager.has_function(name):
+                return False, f"the entry {name}, which the env's code object does not have"
+        return True, ""
+
+    def update_kernels(self, num_envs, batch_len, n_agents, width, obs_size, n_actions, device, **options):
+        """the five launches (training/pg_update_custom_kernels.py::PgCustomUpdateKernels) on this env's entries"""
+        from warp_drive_amd.training import pg_update_custom_kernels as pgck
+
+        ok, why = self.update_kernels_refusal(width, obs_size, n_actions)
+        if not ok:
+            raise UnsupportedRolloutShape(f"{type(self).__name__}: {why}")
+        return pgck.PgCustomUpdateKernels(self.cuda_function_manager, self.UPDATE_KERNEL_PREFIX, num_envs, batch_len,
+                                          n_agents, width, obs_size, n_actions, device, **options)
