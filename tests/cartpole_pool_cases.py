@@ -164,9 +164,9 @@ class HostChoice:
     """the action of a tick on the host alone: the counting draw on the fixed probabilities, or on the float32 restatement
     of the in-kernel network; counts the draws within NEAR_WINDOW of a threshold"""
 
-    def __init__(self, case):
+    def __init__(self, case, packed=None):
         self.case, self.near = case, 0
-        self.packed = case.policy()[1] if case.hidden else None
+        self.packed = (case.policy()[1] if packed is None else packed) if case.hidden else None
         self.probs = None if case.hidden else case.probabilities()
 
     def cum(self, obs):
@@ -189,8 +189,8 @@ class FollowDevice(HostChoice):
     the host's counting draw except where the uniform lies within NEAR_WINDOW of a threshold (that set comes from the
     host's sums and uniforms alone); the model follows the device's action.  Fixed probabilities: no exception."""
 
-    def __init__(self, case, device_actions):
-        super().__init__(case)
+    def __init__(self, case, device_actions, packed=None):
+        super().__init__(case, packed)
         self.got, self.differ = np.asarray(device_actions), 0
 
     def __call__(self, k, obs, u):

@@ -469,8 +469,9 @@ def host_obs(env, state):
     return cc.acrobot_obs(state) if env == "acrobot" else np.asarray(state, F32).copy()
 
 
-def simulate_rollout(case):
-    """the rollout on the host alone (numpy step, the restated network, the Philox replay) -> (Coverage, near draws)"""
+def simulate_rollout(case, packed=None):
+    """the rollout on the host alone (numpy step, the restated network on `packed`, default the case's own policy, the
+    Philox replay) -> (Coverage, near draws)"""
     from tests.classic_control_policy import count_below, running_sums
     from warp_drive_amd.envs.classic_control import apply_done
 
@@ -482,7 +483,8 @@ def simulate_rollout(case):
         pool_states = np.asarray(env_obj.get_reset_pool_dictionary()["state_reset_pool"]["data"], F32)[:, 0]
     obs0 = host_obs(case.env, start[None])[0]
     step = numpy_step(case.env)
-    _, packed = case.policy()
+    if packed is None:
+        _, packed = case.policy()
     state, ts = case.start_states(), case.start_timesteps().astype(np.int64)
     obs = np.broadcast_to(obs0, (E, len(obs0))).astype(F32).copy()   # (the device's observation rows before tick 0)
     if case.env == "cartpole":   # (Cartpole's observation is its state)

@@ -99,8 +99,9 @@ def numpy_step(env):
     return {"acrobot": cc.acrobot_step, "mountain_car": cc.mountain_car_step}[env]
 
 
-def host_rollout(env, hidden, pool, stream_tag):
-    """The parity test's rollout replayed on the host alone: the numpy step, the policy restatement above, the Philox
+def host_rollout(env, hidden, pool, stream_tag, packed=None):
+    """The parity test's rollout replayed on the host alone: the numpy step, the policy restatement above (on `packed`
+    float32 numpy weights; default: the parity test's policy), the Philox
     draws of the sampler and of the pool key from their seeds.  (The numpy step may differ from the device's by an ulp:
     this replay sizes the test, it is not its yardstick.)  Returns {"finished", "action_counts" [3], "pool_rows"}."""
     from oracle.core_np import pool_pick, seed_words, single_head_tick_uniform
@@ -114,8 +115,8 @@ def host_rollout(env, hidden, pool, stream_tag):
     if pool:
         pool_states = np.asarray(e.get_reset_pool_dictionary()["state_reset_pool"]["data"], f32)[:, 0]
     step = numpy_step(env)
-    _, packed = make_policy(env, hidden)
-    packed = packed.numpy()
+    if packed is None:
+        packed = make_policy(env, hidden)[1].numpy()
     k0, k1 = seed_words(c["sampler_seed"])
     p0, p1 = seed_words(c["pool_seed"])
     state = np.broadcast_to(start, (E, start.size)).astype(f32).copy()
