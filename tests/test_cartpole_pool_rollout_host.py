@@ -243,6 +243,12 @@ def test_tick_launch_without_a_pool_builds_what_it_built_before(width):
         assert len(args) == len(want) == 31
         for i, (got, w) in enumerate(zip(args, want)):
             assert type(got) is type(w) and got == w, (i, got, w)
+    if width:   # a packed policy of another size, or of the right size and not float32: the caller's bug
+        import torch
+
+        for bad in (_tensor((_n_w(width, A) + 1,), torch.float32), _tensor((_n_w(width, A),), torch.float64)):
+            with pytest.raises(AssertionError):
+                env.tick_launch(sampler, [probs], resetter, batch=batch, policy=(bad, width))
 
 
 def test_refusals_name_their_reason():
@@ -287,8 +293,11 @@ def test_refusals_name_their_reason():
     env.ticks_per_launch = T
     probs, batch, packed = _launch_inputs(E, T, 2, 32)
     _, _, wrong = _launch_inputs(E, T, 3, 32)
-    with pytest.raises(UnsupportedRolloutShape, match="packed policy"):
-        env.tick_launch(sampler, [probs], env.cuda_env_resetter, batch=batch, policy=(wrong, 32))
+    import torch
+
+    for bad in (wrong, _tensor((_n_w(32, 2),), torch.float64)):   # ... or of the right size and not float32
+        with pytest.raises(UnsupportedRolloutShape, match="packed policy"):
+            env.tick_launch(sampler, [probs], env.cuda_env_resetter, batch=batch, policy=(bad, 32))
     # the evaluation never restarts: its answer does not depend on the pool
     assert env.has_live_policy_evaluate(32, 2) and env.has_live_policy_evaluate(64, 8)
 

@@ -16,6 +16,8 @@ from warp_drive_amd.utils import spaces
 from warp_drive_amd.utils.constants import Constants
 from warp_drive_amd.utils.data_feed import DataFeed
 from warp_drive_amd.utils.gpu_environment_context import CUDAEnvironmentContext
+from warp_drive_amd.utils.launch_checks import (NULL, SingleAgentDeviceEnv, UnsupportedRolloutShape, batch_arguments,
+                                                rp_pad4, rp_policy_floats, tick_tag, unpack_policy)
 
 _OBSERVATIONS = Constants.OBSERVATIONS
 _ACTIONS = Constants.ACTIONS
@@ -101,7 +103,13 @@ class ClassicControlCartPoleEnv:
         return {0: self.state.copy()}, {0: 1.0}, done, {}
 
 
-class CUDAClassicControlCartPoleEnv(CUDAEnvironmentContext, ClassicControlCartPoleEnv):
+class CUDAClassicControlCartPoleEnv(SingleAgentDeviceEnv, CUDAEnvironmentContext, ClassicControlCartPoleEnv):
+    """The device side.  Step, reset pool, `has_live_policy_evaluate` and `evaluate_launch`
+    (HipClassicControlCartPoleEnvEvaluate_H<width>: the network runs on the state, which is Cartpole's observation) are
+    utils/launch_checks.py::SingleAgentDeviceEnv's."""
+    STATE_DIM = 4
+    _PACKED_DETAIL = "width {width}, {n_act} actions"
+
     def __init__(self, *args, **kwargs):
         ClassicControlCartPoleEnv.__init__(self, *args, **kwargs)
         CUDAEnvironmentContext.__init__(self)
@@ -120,27 +128,15 @@ class CUDAClassicControlCartPoleEnv(CUDAEnvironmentContext, ClassicControlCartPo
         ])
         return feed
 
-    def get_reset_pool_dictionary(self):
-        pool = DataFeed()
-        if self.reset_pool_size >= 2:
-            states = np.stack([np.atleast_2d(self._draw_initial_state(fixed=False))
-                               for _ in range(self.reset_pool_size)], axis=0)
-            assert states.ndim == 3 and states.shape[2] == 4
-            pool.add_pool_for_reset(name="state_reset_pool", data=states, reset_target="state")
-        return pool
-
     _STEP_ARGS = ["state", _ACTIONS, "_done_", _REWARDS, _OBSERVATIONS, "gravity", "masspole", "total_mass",
                   "length", "polemass_length", "force_mag", "tau", "theta_threshold_radians", "x_threshold",
                   "_timestep_", ("episode_length", "meta"), ("n_envs", "meta")]
 
-    def step_launch(self):
-        n_envs = int(self.cuda_data_manager.meta_info("n_envs"))
-        block = (256, 1, 1)
-        grid = (max(1, min(4096, (n_envs + 255) // 256)), 1)
-        return self.cuda_step, self.cuda_step_function_feed(self._STEP_ARGS), block, grid, 0
+    def _step_args(self):
+        return self._STEP_ARGS
 
-    TICK_HEADS = 1          # action heads the fused tick kernel samples (RolloutEngine)
-    ticks_per_launch = 1    # > 1: fixed-policy rollout, T ticks fused per launch (the HBM-ceiling run)
+    def _obs_size(self):
+        return 4   # the state is the observation: no data-manager query
 
     ROLLOUT_POLICY_WIDTHS = (32, 64)   # HipClassicControlCartPoleEnvRollout_H<width>
 
@@ -176,9 +172,8 @@ class CUDAClassicControlCartPoleEnv(CUDAEnvironmentContext, ClassicControlCartPo
     def pool_rollout_lds_bytes(width, n_actions, n_pool, staged):
         """dynamic LDS of the ..._P entries: the packed policy (width 0, the fixed-probability entry: none) rounded up
         to whole float4, then -- staged -- the pool's rows of 16 bytes"""
-        width, n_actions = int(width), int(n_actions)
-        n_w = 4 * width + width + width * width + width + n_actions * width + n_actions if width else 0
-        return 4 * (-(-n_w // 4) * 4) + (16 * int(n_pool) if staged else 0)
+        n_w = rp_policy_floats(4, width, n_actions) if int(width) else 0
+        return 4 * rp_pad4(n_w) + (16 * int(n_pool) if staged else 0)
 
     def _pool_rollout(self, width, n_actions):
         """(pool array's name, rows, staged) when the pooled rollout of this width (0: fixed probabilities) serves the env as
@@ -226,59 +221,8 @@ class CUDAClassicControlCartPoleEnv(CUDAEnvironmentContext, ClassicControlCartPo
         `tick_launch(policy=...)`)"""
         if self._has_pool():
             return bool(int(width) in self.ROLLOUT_POLICY_WIDTHS and not isinstance(self._pool_rollout(width, n_actions), str))
-        name = self.cuda_step.name.replace("Step", f"Rollout_H{int(width)}")
-        return int(width) in self.ROLLOUT_POLICY_WIDTHS and int(n_actions) <= 8 and self.cuda_function_manager.has_function(name)
-
-    def has_live_policy_evaluate(self, width, n_actions):
-        """does an evaluation kernel exist that runs one episode of every replica with the policy network inside it
-        (HipClassicControlCartPoleEnvEvaluate_H<width>, Trainer.evaluate_episodes)?"""
-        name = self.cuda_step.name.replace("Step", f"Evaluate_H{int(width)}")
-        return bool(int(width) in self.ROLLOUT_POLICY_WIDTHS and 1 <= int(n_actions) <= 8
-                    and self.cuda_function_manager.has_function(name))
-
-    def evaluate_launch(self, sampler, policy, use_argmax, outputs, action_trace=None, ticks=None, n_actions=None):
-        """One episode of every replica in ONE launch (HipClassicControlCartPoleEnvEvaluate_H<width>): from the state
-        and timestep the arrays hold, at most `ticks` (default: episode_length) ticks of policy network (on the state,
-        which is Cartpole's observation) -> action (use_argmax: the first maximum of the probabilities; else the
-        counting draw of the fused tick) -> Euler step, up to the first done.  policy = (packed float32 CUDA tensor,
-        hidden width) as in `tick_launch`; `n_actions` defaults to the env's two.  outputs = {"reward_sum": float32,
-        "steps": int32, "done": int32}, CUDA tensors of at least n_envs elements; `action_trace` (optional) int32
-        [>= ticks, n_envs]: row k = tick k's actions.  The launch writes those, and in sampled mode the sampler's epoch
-        words; the env's arrays are read only.  Returns (function, arguments, block, grid, shared bytes)."""
-        from warp_drive_amd.managers.function_manager import _stream_tag
-        from warp_drive_amd.rollout import UnsupportedRolloutShape
-        import torch
-
-        fm, dm = self.cuda_function_manager, self.cuda_data_manager
-        try:
-            packed, width = policy
-            width = int(width)
-            n_act = int(self.action_space[0].n if n_actions is None else n_actions)
-        except (TypeError, ValueError) as err:
-            raise UnsupportedRolloutShape(f"policy = (packed weights, hidden width), not {policy!r}") from err
-        if not self.has_live_policy_evaluate(width, n_act):
-            raise UnsupportedRolloutShape(f"no in-kernel evaluation of width {width} with {n_act} actions")
-        E = int(dm.meta_info("n_envs"))
-        n_w = 4 * width + width + width * width + width + n_act * width + n_act
-        if not (getattr(packed, "is_cuda", False) and packed.dtype == torch.float32 and packed.is_contiguous()
-                and packed.numel() == n_w):
-            raise UnsupportedRolloutShape(f"the packed policy must be a contiguous float32 CUDA tensor of {n_w} "
-                                          f"elements (width {width}, {n_act} actions)")
-        T = int(self.episode_length if ticks is None else ticks)
-        for key, dtype in (("reward_sum", torch.float32), ("steps", torch.int32), ("done", torch.int32)):
-            t = outputs[key]
-            assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.numel() >= E, (key, tuple(t.shape), t.dtype)
-        if action_trace is not None:
-            t = action_trace
-            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and t.shape[0] >= T and \
-                int(np.prod(t.shape[1:])) == E, ("action_trace", tuple(t.shape), t.dtype)
-        name = self.cuda_step.name.replace("Step", f"Evaluate_H{width}")
-        fm.initialize_functions([name])
-        _, args, block, grid, _ = self.step_launch()
-        args = list(args) + [sampler.rng_state, np.int32(n_act), _stream_tag("tick"), np.int32(T), packed, np.int32(width),
-                             np.int32(1 if use_argmax else 0), outputs["reward_sum"], outputs["steps"], outputs["done"],
-                             np.uint64(0) if action_trace is None else action_trace]
-        return fm.get_function(name), args, block, grid, 4 * n_w
+        return int(width) in self.ROLLOUT_POLICY_WIDTHS and int(n_actions) <= 8 and \
+            self.cuda_function_manager.has_function(self._entry(f"Rollout_H{int(width)}"))
 
     def tick_launch(self, sampler, probabilities, resetter, env_range=None, batch=None, policy=None):
         """Fused rollout tick(s): sample + step + reset of a finished replica, `ticks_per_launch`
@@ -290,48 +234,31 @@ class CUDAClassicControlCartPoleEnv(CUDAEnvironmentContext, ClassicControlCartPo
         CUDA tensor from training.policy_kernel.pack_rollout_policy, hidden width): the launch evaluates the
         policy network on every tick's observation itself (HipClassicControlCartPoleEnvRollout_H<width>)
         instead of reading `probabilities`.  An env with a reset pool: `_pool_tick_launch` (the ..._P entries)."""
-        from warp_drive_amd.managers.function_manager import _stream_tag
-
         assert env_range is None and len(probabilities) == 1
         fm, dm = self.cuda_function_manager, self.cuda_data_manager
         if self._has_pool():
             return self._pool_tick_launch(sampler, probabilities, resetter, batch, policy)
-        name = self.cuda_step.name.replace("Step", "Tick")
-        shared, pol_args = 0, [np.uint64(0), np.int32(0)]
+        name = self._entry("Tick")
+        shared, pol_args = 0, [NULL, np.int32(0)]
         if policy is not None:
-            packed, width = policy
+            packed, width = policy   # (as given: a malformed `policy` is the caller's bug here, not a refusal)
             n_act = int(probabilities[0].shape[-1])
             if not self.has_live_policy_rollout(width, n_act):
-                from warp_drive_amd.rollout import UnsupportedRolloutShape
-
                 raise UnsupportedRolloutShape(f"no in-kernel policy of width {width} with {n_act} actions")
-            n_w = 4 * width + width + width * width + width + n_act * width + n_act
-            assert packed.is_cuda and packed.dtype.is_floating_point and packed.numel() == n_w and packed.is_contiguous()
-            name = self.cuda_step.name.replace("Step", f"Rollout_H{width}")
+            n_w = self._checked_policy(packed, width, n_act, AssertionError)
+            name = self._entry(f"Rollout_H{width}")
             shared, pol_args = 4 * n_w, [packed, np.int32(width)]
         fm.initialize_functions([name])
         _, reset_args, _, _ = resetter.fused_launch(dm, 0, 0)  # builds / refreshes the descriptor table
         _, args, block, grid, _ = self.step_launch()
         args = list(args) + [sampler.rng_state, probabilities[0], np.int32(probabilities[0].shape[-1]), reset_args[0],
-                             reset_args[1], _stream_tag("tick"), np.int32(self.ticks_per_launch)] + \
+                             reset_args[1], tick_tag(), np.int32(self.ticks_per_launch)] + \
             self._batch_arguments(batch) + pol_args + [np.int32(self.invariant_divide_ok())]
         return fm.get_function(name), args, block, grid, shared
 
     def _batch_arguments(self, batch):
         """the four `*_batch` arguments of a tick / rollout entry (nulls without batch tensors), their shapes checked"""
-        null = np.uint64(0)
-        if batch is None:
-            return [null, null, null, null]
-        import torch
-
-        E, T = int(self.cuda_data_manager.meta_info("n_envs")), int(self.ticks_per_launch)
-        want = {"obs": ((E, 1, 4), torch.float32), "actions": ((E, 1, 1), torch.int32),
-                "rewards": ((E, 1), torch.float32), "done": ((E,), torch.int32)}
-        for key, (shape, dtype) in want.items():
-            t = batch[key]
-            assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.shape[0] >= T and \
-                tuple(t.shape[1:]) == shape, (key, tuple(t.shape), t.dtype)
-        return [batch["obs"], batch["actions"], batch["rewards"], batch["done"]]
+        return batch_arguments(batch, int(self.ticks_per_launch), self._n_envs(), 1, 4)
 
     def _pool_tick_launch(self, sampler, probabilities, resetter, batch, policy):
         """`tick_launch` for the env with a reset pool: HipClassicControlCartPoleEnvRollout_P (fixed probabilities) or
@@ -339,9 +266,6 @@ class CUDAClassicControlCartPoleEnv(CUDAEnvironmentContext, ClassicControlCartPo
         entry's, then the pool generator's words, the pool, its row count and 1 / 0 = the kernel stages the pool in LDS /
         reads it from global memory (`pool_placement`).  Whatever the entries do not serve raises
         UnsupportedRolloutShape with the reason."""
-        from warp_drive_amd.managers.function_manager import _stream_tag
-        from warp_drive_amd.rollout import UnsupportedRolloutShape
-
         fm, dm = self.cuda_function_manager, self.cuda_data_manager
         if batch is None or int(self.ticks_per_launch) < 2:
             raise UnsupportedRolloutShape("Cartpole with a reset pool has no fused single tick: its one-launch rollout "
@@ -349,11 +273,7 @@ class CUDAClassicControlCartPoleEnv(CUDAEnvironmentContext, ClassicControlCartPo
         n_act = int(probabilities[0].shape[-1])
         width, packed = 0, None
         if policy is not None:
-            try:
-                packed, width = policy
-                width = int(width)
-            except (TypeError, ValueError) as err:
-                raise UnsupportedRolloutShape(f"policy = (packed weights, hidden width), not {policy!r}") from err
+            packed, width = unpack_policy(policy)
             if width not in self.ROLLOUT_POLICY_WIDTHS:
                 raise UnsupportedRolloutShape(f"no in-kernel policy of width {width} with {n_act} actions")
         shape = self._pool_rollout(width, n_act)
@@ -363,20 +283,16 @@ class CUDAClassicControlCartPoleEnv(CUDAEnvironmentContext, ClassicControlCartPo
         if getattr(resetter, "_pool_rng", None) is None:
             raise UnsupportedRolloutShape("the pool generator is not initialised: call init_reset_pool() before "
                                           "building the rollout")
-        pol_args = [np.uint64(0), np.int32(0)]
+        pol_args = [NULL, np.int32(0)]
         if policy is not None:
-            n_w = 4 * width + width + width * width + width + n_act * width + n_act
-            if not (getattr(packed, "is_cuda", False) and packed.dtype.is_floating_point and packed.is_contiguous()
-                    and packed.numel() == n_w):
-                raise UnsupportedRolloutShape(f"the packed policy must be a contiguous float32 CUDA tensor of {n_w} "
-                                              f"elements (width {width}, {n_act} actions)")
+            self._checked_policy(packed, width, n_act, UnsupportedRolloutShape)
             pol_args = [packed, np.int32(width)]
-        name = self.cuda_step.name.replace("Step", f"Rollout_P_H{width}" if width else "Rollout_P")
+        name = self._entry(f"Rollout_P_H{width}" if width else "Rollout_P")
         fm.initialize_functions([name])
         _, reset_args, _, _ = resetter.fused_launch(dm, 0, 0)  # builds / refreshes the descriptor table
         _, args, block, grid, _ = self.step_launch()
         args = list(args) + [sampler.rng_state, probabilities[0], np.int32(n_act), reset_args[0], reset_args[1],
-                             _stream_tag("tick"), np.int32(self.ticks_per_launch)] + self._batch_arguments(batch) + \
+                             tick_tag(), np.int32(self.ticks_per_launch)] + self._batch_arguments(batch) + \
             pol_args + [np.int32(self.invariant_divide_ok()), resetter._pool_rng, dm.device_data(pool_name),
                         np.int32(n_pool), np.int32(1 if staged else 0)]
         return fm.get_function(name), args, block, grid, self.pool_rollout_lds_bytes(width, n_act, n_pool, staged)
@@ -397,10 +313,3 @@ class CUDAClassicControlCartPoleEnv(CUDAEnvironmentContext, ClassicControlCartPo
                                                                 block=(256, 1, 1), grid=(4096, 1), shared=0)
             self._inv_div_ok = int(ok.item())
         return self._inv_div_ok
-
-    def step(self, actions=None):
-        self.timestep += 1
-        if self.env_backend != "hip":
-            raise Exception("CUDAClassicControlCartPoleEnv expects env_backend = 'hip'")
-        fn, args, block, grid, shared = self.step_launch()
-        fn(*args, block=block, grid=grid, shared=shared)

@@ -26,6 +26,9 @@ from warp_drive_amd.utils import spaces
 from warp_drive_amd.utils.constants import Constants
 from warp_drive_amd.utils.data_feed import DataFeed
 from warp_drive_amd.utils.gpu_environment_context import CUDAEnvironmentContext
+from warp_drive_amd.utils.launch_checks import (NULL, SingleAgentDeviceEnv, UnsupportedRolloutShape, batch_arguments,
+                                                check_packed, check_record, evaluation_outputs, on_device, rp_actor_floats,
+                                                tick_tag, unpack_actor, unpack_ou, unpack_policy)
 
 _OBSERVATIONS = Constants.OBSERVATIONS
 _ACTIONS = Constants.ACTIONS
@@ -335,16 +338,13 @@ class ClassicControlPendulumEnv(_ClassicControlEnv):
 
 # ---------------------------------------------------------------------------------------------------- device envs
 def rollout_actor_floats(obs_size, width):
-    """floats of the packed actor the ...Rollout_A<width> entries read (csrc/kernels/rollout_policy.h::rp_actor_floats): W0
-    [H][OP], b0 [H], W1 [H][H], b1 [H], Wa [H], ba [1], OP = the observation size rounded up to even"""
-    op = (int(obs_size) + 1) // 2 * 2
-    return op * width + width + width * width + width + width + 1
+    """floats of the packed actor the ...Rollout_A<width> entries read: rp_actor_floats(width, obs_size)"""
+    return rp_actor_floats(width, obs_size)
 
 
-class _CUDAClassicControlEnv(CUDAEnvironmentContext):
-    """shared device side: data, reset pool, step launch and fused tick launch"""
-    TICK_HEADS = 1          # action heads the fused tick kernel samples (RolloutEngine)
-    ticks_per_launch = 1    # > 1: fixed-policy rollout, T ticks fused per launch
+class _CUDAClassicControlEnv(SingleAgentDeviceEnv, CUDAEnvironmentContext):
+    """shared device side: data and the fused tick launch; step, reset pool, `has_live_policy_evaluate` and
+    `evaluate_launch` (HipClassicControl<X>EnvEvaluate_H<width>) are utils/launch_checks.py::SingleAgentDeviceEnv's"""
     TICK_POOL_RESET = True  # the tick kernel restarts a finished replica from the reset pool itself
     CONSTANTS = ()          # names of the physics constants the kernels take, in argument order
     # the trainer runs a whole batch in one launch on these envs only when asked to
@@ -354,89 +354,36 @@ class _CUDAClassicControlEnv(CUDAEnvironmentContext):
     def __init__(self, *args, **kwargs):
         CUDAEnvironmentContext.__init__(self)
 
+    def _has_entry(self, suffix, width, box):
+        """is `width` among the widths the class lists for its (Box: actor, else: policy) entries, and the entry
+        ...<suffix><width> in the manifest?"""
+        widths = getattr(self, "ROLLOUT_ACTOR_WIDTHS" if box else "ROLLOUT_POLICY_WIDTHS", ())
+        if isinstance(self.action_space[0], spaces.Box) != box or int(width) not in widths:
+            return False
+        return bool(self.cuda_function_manager.has_function(self._entry(f"{suffix}{int(width)}")))
+
     def has_live_policy_rollout(self, width, n_actions):
         """does a rollout kernel exist that evaluates the policy network itself (...Rollout_H<width>)?  (RolloutEngine asks
         before it calls `tick_launch(policy=...)`)  The Box envs have none."""
-        widths = getattr(self, "ROLLOUT_POLICY_WIDTHS", ())
-        if isinstance(self.action_space[0], spaces.Box) or int(width) not in widths or not 1 <= int(n_actions) <= 8:
-            return False
-        name = self.cuda_step.name.replace("Step", f"Rollout_H{int(width)}")
-        return bool(self.cuda_function_manager.has_function(name))
+        return 1 <= int(n_actions) <= 8 and self._has_entry("Rollout_H", width, box=False)
 
     def has_live_actor_rollout(self, width):
         """does a rollout kernel exist that evaluates a deterministic actor itself (...Rollout_A<width>)?  (RolloutEngine
         asks before it calls `tick_launch(actor=...)`)  Only the Box envs have one."""
-        widths = getattr(self, "ROLLOUT_ACTOR_WIDTHS", ())
-        if not isinstance(self.action_space[0], spaces.Box) or int(width) not in widths:
-            return False
-        name = self.cuda_step.name.replace("Step", f"Rollout_A{int(width)}")
-        return bool(self.cuda_function_manager.has_function(name))
-
-    def has_live_policy_evaluate(self, width, n_actions):
-        """does an evaluation kernel exist that runs one episode of every replica with the policy network inside it
-        (...Evaluate_H<width>, Trainer.evaluate_episodes)?  The same widths and action counts as the rollout entries;
-        the Box envs have none."""
-        widths = getattr(self, "ROLLOUT_POLICY_WIDTHS", ())
-        if isinstance(self.action_space[0], spaces.Box) or int(width) not in widths or not 1 <= int(n_actions) <= 8:
-            return False
-        name = self.cuda_step.name.replace("Step", f"Evaluate_H{int(width)}")
-        return bool(self.cuda_function_manager.has_function(name))
-
-    def evaluate_launch(self, sampler, policy, use_argmax, outputs, action_trace=None, ticks=None, n_actions=None):
-        """One episode of every replica in ONE launch (HipClassicControl<X>EnvEvaluate_H<width>): from the state,
-        observation and timestep the arrays hold, at most `ticks` (default: episode_length) ticks of policy network ->
-        action (use_argmax: the first maximum of the probabilities; else the counting draw of the fused tick) -> step,
-        up to the first done.  policy = (packed float32 CUDA tensor, hidden width) as in `tick_launch`; `n_actions`
-        defaults to the env's action count.  outputs = {"reward_sum": float32, "steps": int32, "done": int32}, CUDA
-        tensors of at least n_envs elements; `action_trace` (optional) int32 [>= ticks, n_envs]: row k = tick k's
-        actions.  The launch writes those, and in sampled mode the sampler's epoch words; the env's arrays are read only.
-        Returns (function, arguments, block, grid, shared bytes)."""
-        from warp_drive_amd.managers.function_manager import _stream_tag
-        from warp_drive_amd.rollout import UnsupportedRolloutShape
-        import torch
-
-        fm, dm = self.cuda_function_manager, self.cuda_data_manager
-        try:
-            packed, width = policy
-            width = int(width)
-            n_act = int(self.action_space[0].n if n_actions is None else n_actions)
-        except (TypeError, ValueError, AttributeError) as err:
-            raise UnsupportedRolloutShape(f"policy = (packed weights, hidden width), not {policy!r}") from err
-        if not self.has_live_policy_evaluate(width, n_act):
-            raise UnsupportedRolloutShape(f"{type(self).__name__} has no in-kernel evaluation of width {width} with "
-                                          f"{n_act} actions")
-        E = int(dm.meta_info("n_envs"))
-        O = int(dm.get_shape(_OBSERVATIONS)[-1])
-        n_w = O * width + width + width * width + width + n_act * width + n_act
-        if not (getattr(packed, "is_cuda", False) and packed.dtype == torch.float32 and packed.is_contiguous()
-                and packed.numel() == n_w):
-            raise UnsupportedRolloutShape(f"the packed policy must be a contiguous float32 CUDA tensor of {n_w} "
-                                          f"elements (observation {O}, width {width}, {n_act} actions)")
-        T = int(self.episode_length if ticks is None else ticks)
-        for key, dtype in (("reward_sum", torch.float32), ("steps", torch.int32), ("done", torch.int32)):
-            t = outputs[key]
-            assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.numel() >= E, (key, tuple(t.shape), t.dtype)
-        if action_trace is not None:
-            t = action_trace
-            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and t.shape[0] >= T and \
-                int(np.prod(t.shape[1:])) == E, ("action_trace", tuple(t.shape), t.dtype)
-        name = self.cuda_step.name.replace("Step", f"Evaluate_H{width}")
-        fm.initialize_functions([name])
-        _, args, block, grid, _ = self.step_launch()
-        args = list(args) + [sampler.rng_state, np.int32(n_act), _stream_tag("tick"), np.int32(T), packed, np.int32(width),
-                             np.int32(1 if use_argmax else 0), outputs["reward_sum"], outputs["steps"], outputs["done"],
-                             np.uint64(0) if action_trace is None else action_trace]
-        return fm.get_function(name), args, block, grid, 4 * n_w
+        return self._has_entry("Rollout_A", width, box=True)
 
     def has_live_actor_evaluate(self, width):
         """does an evaluation kernel exist that runs one episode of every replica with the deterministic actor inside it
         (...Evaluate_A<width>, TrainerDDPG.evaluate_episodes)?  The widths of the Rollout_A entries; only the Box envs
         have one."""
-        widths = getattr(self, "ROLLOUT_ACTOR_WIDTHS", ())
-        if not isinstance(self.action_space[0], spaces.Box) or int(width) not in widths:
-            return False
-        name = self.cuda_step.name.replace("Step", f"Evaluate_A{int(width)}")
-        return bool(self.cuda_function_manager.has_function(name))
+        return self._has_entry("Evaluate_A", width, box=True)
+
+    def _checked_actor(self, packed, width):
+        """floats of the packed actor of this env, `packed` checked against them"""
+        O = self._obs_size()
+        n_w = rp_actor_floats(width, O)
+        check_packed(packed, n_w, UnsupportedRolloutShape, "the packed actor", f"observation {O}, width {width}")
+        return n_w
 
     def evaluate_actor_launch(self, sampler, actor, ou, outputs, mean_trace=None, action_trace=None, ticks=None):
         """One episode of every replica of a Box env in ONE launch (HipClassicControl<X>EnvEvaluate_A<width>): from the
@@ -448,50 +395,25 @@ class _CUDAClassicControlEnv(CUDAEnvironmentContext):
         (optional) float32 [>= ticks, n_envs]: row k = tick k's means / actions.  The launch writes those, and when it
         draws the OU state and the sampler's epoch words; the env's arrays are read only.
         Returns (function, arguments, block, grid, shared bytes)."""
-        from warp_drive_amd.managers.function_manager import _stream_tag
-        from warp_drive_amd.rollout import UnsupportedRolloutShape
-        import torch
-
         fm, dm = self.cuda_function_manager, self.cuda_data_manager
-        try:
-            packed, width, action_scale, action_bias = actor
-            width, action_scale, action_bias = int(width), float(action_scale), float(action_bias)
-        except (TypeError, ValueError) as err:
-            raise UnsupportedRolloutShape("actor = (packed weights, hidden width, action_scale, action_bias), "
-                                          f"not {actor!r}") from err
+        packed, width, action_scale, action_bias = unpack_actor(actor)
         if not self.has_live_actor_evaluate(width):
             raise UnsupportedRolloutShape(f"{type(self).__name__} has no in-kernel evaluation of an actor of width {width}")
-        try:
-            damping, stddev, scale = (float(v) for v in ou)
-        except (TypeError, ValueError) as err:
-            raise UnsupportedRolloutShape(f"ou = (damping, stddev, scale), not {ou!r}") from err
-        E = int(dm.meta_info("n_envs"))
-        O = int(dm.get_shape(_OBSERVATIONS)[-1])
-        n_w = rollout_actor_floats(O, width)
-        if not (getattr(packed, "is_cuda", False) and packed.dtype == torch.float32 and packed.is_contiguous()
-                and packed.numel() == n_w):
-            raise UnsupportedRolloutShape(f"the packed actor must be a contiguous float32 CUDA tensor of {n_w} "
-                                          f"elements (observation {O}, width {width})")
+        damping, stddev, scale = unpack_ou(ou)
+        E = self._n_envs()
+        n_w = self._checked_actor(packed, width)
         T = int(self.episode_length if ticks is None else ticks)
-        for key, dtype in (("reward_sum", torch.float32), ("steps", torch.int32), ("done", torch.int32)):
-            t = outputs[key]
-            if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and t.numel() >= E):
-                raise UnsupportedRolloutShape(f"outputs[{key!r}] must be a contiguous {dtype} CUDA tensor of at least "
-                                              f"{E} elements")
+        out_args = evaluation_outputs(outputs, E, UnsupportedRolloutShape)
         for key, t in (("mean_trace", mean_trace), ("action_trace", action_trace)):
-            if t is not None and not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == torch.float32
-                                      and len(t.shape) >= 2 and t.shape[0] >= T
-                                      and int(np.prod(t.shape[1:])) == E):
-                raise UnsupportedRolloutShape(f"{key} must be a contiguous float32 CUDA tensor [>= {T}, {E}]")
-        name = self.cuda_step.name.replace("Step", f"Evaluate_A{width}")
+            if t is not None:
+                check_record(t, key, "float32", T, E, UnsupportedRolloutShape, min_dims=2)
+        name = self._entry(f"Evaluate_A{width}")
         fm.initialize_functions([name])
         _, args, block, grid, _ = self.step_launch()
-        null = np.uint64(0)
-        args = list(args) + [sampler.rng_state, _stream_tag("tick"), np.int32(T), packed, np.int32(width),
+        args = list(args) + [sampler.rng_state, tick_tag(), np.int32(T), packed, np.int32(width),
                              np.float32(action_scale), np.float32(action_bias), dm.device_data(f"{_ACTIONS}_ou_state"),
-                             np.float32(damping), np.float32(stddev), np.float32(scale), outputs["reward_sum"],
-                             outputs["steps"], outputs["done"], null if mean_trace is None else mean_trace,
-                             null if action_trace is None else action_trace]
+                             np.float32(damping), np.float32(stddev), np.float32(scale)] + out_args + \
+            [NULL if mean_trace is None else mean_trace, NULL if action_trace is None else action_trace]
         return fm.get_function(name), args, block, grid, 4 * n_w
 
     def get_data_dictionary(self):
@@ -502,24 +424,9 @@ class _CUDAClassicControlEnv(CUDAEnvironmentContext):
             feed.add_data_list([(name, float(getattr(self.physics, name))) for name in self.CONSTANTS])
         return feed
 
-    def get_reset_pool_dictionary(self):
-        pool = DataFeed()
-        if self.reset_pool_size >= 2:
-            states = np.stack([np.atleast_2d(self._draw_initial_state(fixed=False))
-                               for _ in range(self.reset_pool_size)], axis=0)
-            assert states.ndim == 3 and states.shape[2] == self.STATE_DIM
-            pool.add_pool_for_reset(name="state_reset_pool", data=states, reset_target="state")
-        return pool
-
     def _step_args(self):
         return (["state", _ACTIONS, "_done_", _REWARDS, _OBSERVATIONS] + list(self.CONSTANTS)
                 + ["_timestep_", ("episode_length", "meta"), ("n_envs", "meta")])
-
-    def step_launch(self):
-        n_envs = int(self.cuda_data_manager.meta_info("n_envs"))
-        block = (256, 1, 1)
-        grid = (max(1, min(4096, (n_envs + 255) // 256)), 1)
-        return self.cuda_step, self.cuda_step_function_feed(self._step_args()), block, grid, 0
 
     def tick_launch(self, sampler, probabilities, resetter, env_range=None, batch=None, policy=None,
                     ou_params=(0.15, 0.2, 1.0), actor=None, mean_batch=None):
@@ -538,89 +445,44 @@ class _CUDAClassicControlEnv(CUDAEnvironmentContext):
         deterministic actor on every tick's observation itself (HipClassicControl<X>EnvRollout_A<width>), mean =
         action_scale * tanh(z) + action_bias, instead of reading the means; `mean_batch` (optional, float32 [T, E]): tick
         k writes its means to row k."""
-        from warp_drive_amd.managers.function_manager import _stream_tag
-        from warp_drive_amd.rollout import UnsupportedRolloutShape
-
         assert env_range is None and len(probabilities) == 1
         fm, dm = self.cuda_function_manager, self.cuda_data_manager
-        name = self.cuda_step.name.replace("Step", "Tick")
+        who = type(self).__name__
+        name = self._entry("Tick")
         shared, pol_args = 0, []
         if policy is not None:
-            try:
-                packed, width = policy
-                width, n_act = int(width), int(probabilities[0].shape[-1])
-            except (TypeError, ValueError) as err:
-                raise UnsupportedRolloutShape(f"policy = (packed weights, hidden width), not {policy!r}") from err
+            packed, width, n_act = unpack_policy(policy, lambda: probabilities[0].shape[-1])
             if not self.has_live_policy_rollout(width, n_act):
-                raise UnsupportedRolloutShape(f"{type(self).__name__} has no in-kernel policy of width {width} with "
-                                              f"{n_act} actions")
-            import torch
-
-            O = int(dm.get_shape(_OBSERVATIONS)[-1])
-            n_w = O * width + width + width * width + width + n_act * width + n_act
-            if not (getattr(packed, "is_cuda", False) and packed.dtype == torch.float32 and packed.is_contiguous()
-                    and packed.numel() == n_w):
-                raise UnsupportedRolloutShape(f"the packed policy must be a contiguous float32 CUDA tensor of {n_w} "
-                                              f"elements (observation {O}, width {width}, {n_act} actions)")
-            name = self.cuda_step.name.replace("Step", f"Rollout_H{width}")
-            shared, pol_args = 4 * n_w, [packed, np.int32(width)]
+                raise UnsupportedRolloutShape(f"{who} has no in-kernel policy of width {width} with {n_act} actions")
+            shared = 4 * self._checked_policy(packed, width, n_act, UnsupportedRolloutShape)
+            name, pol_args = self._entry(f"Rollout_H{width}"), [packed, np.int32(width)]
         if actor is not None:
             if policy is not None:
                 raise UnsupportedRolloutShape("a launch evaluates a policy or an actor, not both")
-            try:
-                packed, width, action_scale, action_bias = actor
-                width, action_scale, action_bias = int(width), float(action_scale), float(action_bias)
-            except (TypeError, ValueError) as err:
-                raise UnsupportedRolloutShape("actor = (packed weights, hidden width, action_scale, action_bias), "
-                                              f"not {actor!r}") from err
+            packed, width, action_scale, action_bias = unpack_actor(actor)
             if not self.has_live_actor_rollout(width):
-                raise UnsupportedRolloutShape(f"{type(self).__name__} has no in-kernel actor of width {width}")
-            import torch
-
-            O = int(dm.get_shape(_OBSERVATIONS)[-1])
-            n_w = rollout_actor_floats(O, width)
-            if not (getattr(packed, "is_cuda", False) and packed.dtype == torch.float32 and packed.is_contiguous()
-                    and packed.numel() == n_w):
-                raise UnsupportedRolloutShape(f"the packed actor must be a contiguous float32 CUDA tensor of {n_w} "
-                                              f"elements (observation {O}, width {width})")
-            n_envs, ticks = int(dm.meta_info("n_envs")), int(self.ticks_per_launch)
-            if mean_batch is not None and not (
-                    getattr(mean_batch, "is_cuda", False) and mean_batch.dtype == torch.float32
-                    and mean_batch.is_contiguous() and mean_batch.shape[0] >= ticks
-                    and int(np.prod(mean_batch.shape[1:])) == n_envs):
-                raise UnsupportedRolloutShape(f"mean_batch must be a contiguous float32 CUDA tensor [>= {ticks}, {n_envs}]")
-            name = self.cuda_step.name.replace("Step", f"Rollout_A{width}")
-            shared = 4 * n_w
+                raise UnsupportedRolloutShape(f"{who} has no in-kernel actor of width {width}")
+            shared = 4 * self._checked_actor(packed, width)
+            if mean_batch is not None:
+                check_record(mean_batch, "mean_batch", "float32", int(self.ticks_per_launch), self._n_envs(),
+                             UnsupportedRolloutShape)
+            name = self._entry(f"Rollout_A{width}")
             pol_args = [packed, np.int32(width), np.float32(action_scale), np.float32(action_bias),
-                        np.uint64(0) if mean_batch is None else mean_batch]
+                        NULL if mean_batch is None else mean_batch]
         elif mean_batch is not None:
             raise UnsupportedRolloutShape("mean_batch is what the in-kernel actor records: it needs `actor`")
         fm.initialize_functions([name])
         _, reset_args, _, _ = resetter.fused_launch(dm, 0, 0)  # builds / refreshes the descriptor table
         _, args, block, grid, _ = self.step_launch()
-        null = np.uint64(0)
         probs = probabilities[0]
         continuous = isinstance(self.action_space[0], spaces.Box)
-        E, T = int(dm.meta_info("n_envs")), int(self.ticks_per_launch)
-        assert probs.is_cuda and probs.is_contiguous() and probs.shape[0] == E
+        E, T = self._n_envs(), int(self.ticks_per_launch)
+        assert on_device(probs) and probs.shape[0] == E
         if continuous:
             assert tuple(probs.shape) == (E, 1, 1)
         else:
             assert 1 <= int(probs.shape[-1]) <= 8
-        if batch is not None:
-            import torch
-
-            O = int(dm.get_shape(_OBSERVATIONS)[-1])
-            want = {"obs": ((E, 1, O), torch.float32),
-                    "actions": ((E, 1, 1), torch.float32 if continuous else torch.int32),
-                    "rewards": ((E, 1), torch.float32), "done": ((E,), torch.int32)}
-            for key, (shape, dtype) in want.items():
-                t = batch[key]
-                assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.shape[0] >= T and \
-                    tuple(t.shape[1:]) == shape, (key, tuple(t.shape), t.dtype)
-            batch_args = [batch["obs"], batch["actions"], batch["rewards"], batch["done"]]
-        else:
-            batch_args = [null, null, null, null]
+        batch_args = batch_arguments(batch, T, E, 1, self._obs_size(), actions="float32" if continuous else "int32")
         pools = dict(dm.reset_target_to_pool)
         if pools:
             assert set(pools) == {"state"}, f"the tick kernel restarts `state` from a pool, not {sorted(pools)}"
@@ -629,23 +491,16 @@ class _CUDAClassicControlEnv(CUDAEnvironmentContext):
             pool_args = [resetter._pool_rng, dm.device_data(pools["state"]),
                          np.int32(dm.get_shape(pools["state"])[0])]
         else:
-            pool_args = [null, null, np.int32(0)]
+            pool_args = [NULL, NULL, np.int32(0)]
         if continuous:
             damping, stddev, scale = ou_params
             ou_args = [dm.device_data(f"{_ACTIONS}_ou_state"), np.float32(damping), np.float32(stddev),
                        np.float32(scale)]
         else:
-            ou_args = [null, np.float32(0), np.float32(0), np.float32(0)]
+            ou_args = [NULL, np.float32(0), np.float32(0), np.float32(0)]
         args = list(args) + [sampler.rng_state, probs, np.int32(probs.shape[-1]), reset_args[0], reset_args[1],
-                             _stream_tag("tick"), np.int32(T)] + batch_args + pool_args + ou_args + pol_args
+                             tick_tag(), np.int32(T)] + batch_args + pool_args + ou_args + pol_args
         return fm.get_function(name), args, block, grid, shared
-
-    def step(self, actions=None):
-        self.timestep += 1
-        if self.env_backend != "hip":
-            raise Exception(f"{type(self).__name__} expects env_backend = 'hip'")
-        fn, args, block, grid, shared = self.step_launch()
-        fn(*args, block=block, grid=grid, shared=shared)
 
 
 class CUDAClassicControlAcrobotEnv(_CUDAClassicControlEnv, ClassicControlAcrobotEnv):

@@ -14,6 +14,8 @@ from warp_drive_amd.utils import spaces
 from warp_drive_amd.utils.constants import Constants
 from warp_drive_amd.utils.data_feed import DataFeed
 from warp_drive_amd.utils.gpu_environment_context import CUDAEnvironmentContext
+from warp_drive_amd.utils.launch_checks import (NULL, UnsupportedRolloutShape, batch_arguments, check_packed, check_record,
+                                                evaluation_outputs, rp_pad4, rp_policy_floats, tick_tag, unpack_policy_pair)
 
 _OBSERVATIONS = Constants.OBSERVATIONS
 _ACTIONS = Constants.ACTIONS
@@ -132,42 +134,13 @@ class TagGridWorld:
 def gridworld_policy_floats(hidden):
     """floats of one packed policy of the live-policy rollout kernel (gw5_policy_floats in tag_gridworld_n5_common.h):
     W0 [H][24], b0 [H], W1 [H][H], b1 [H], Wp [5][H], bp [5], rounded up to whole 16-byte vectors"""
-    H = int(hidden)
-    return (H * 24 + H + H * H + H + 5 * H + 5 + 3) // 4 * 4
-
-
-def _unpack_policy(policy):
-    """((packed tagger policy, packed runner policy), hidden width) -> tagger, runner, width"""
-    from warp_drive_amd.rollout import UnsupportedRolloutShape
-
-    try:
-        (tagger, runner), width = policy
-        return tagger, runner, int(width)
-    except (TypeError, ValueError) as err:
-        raise UnsupportedRolloutShape("policy = ((packed tagger policy, packed runner policy), hidden width), "
-                                      f"not {policy!r}") from err
+    return rp_pad4(rp_policy_floats(24, hidden, 5))
 
 
 def _check_packed_policies(tensors, width, error):
     """every packed policy is a contiguous float32 CUDA tensor of gridworld_policy_floats(width) elements, else `error`"""
-    import torch
-
-    n_w = gridworld_policy_floats(width)
     for t in tensors:
-        if not (getattr(t, "is_cuda", False) and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n_w):
-            raise error(f"a packed policy must be a contiguous float32 CUDA tensor of {n_w} elements (width {width})")
-
-
-def _check_batch(batch, E, N, F, T):
-    """the env-level batch tensors of a T-tick rollout: at least T rows of the shapes `tick_launch` documents"""
-    import torch
-
-    want = {"obs": ((E, N, F), torch.float32), "actions": ((E, N, 1), torch.int32),
-            "rewards": ((E, N), torch.float32), "done": ((E,), torch.int32)}
-    for key, (shape, dtype) in want.items():
-        t = batch[key]
-        assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.shape[0] >= T and \
-            tuple(t.shape[1:]) == shape, (key, tuple(t.shape), t.dtype)
+        check_packed(t, gridworld_policy_floats(width), error, "a packed policy", f"width {width}")
 
 
 _STEP_ARGS = [
@@ -306,30 +279,22 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
         [E]}, CUDA tensors (at least that many elements); `action_trace` (optional) int32 [>= ticks, E, 5]: row k = tick
         k's actions of the replicas still running.  The launch writes those and, in sampled mode, the sampler's epoch
         words; the env's arrays are read only.  Returns (function, arguments, block, grid, shared bytes)."""
-        from warp_drive_amd.managers.function_manager import _stream_tag
-        from warp_drive_amd.rollout import UnsupportedRolloutShape
-        import torch
-
         fm, dm = self.cuda_function_manager, self.cuda_data_manager
-        tagger, runner, width = _unpack_policy(policy)
+        tagger, runner, width = unpack_policy_pair(policy)
         if not self.has_live_policy_evaluate(width, len(self.step_actions)):
             raise UnsupportedRolloutShape(self._EVALUATE_SHAPES)
         _check_packed_policies((tagger, runner), width, UnsupportedRolloutShape)
         E, N = int(dm.meta_info("n_envs")), self.num_agents
         T = int(self.episode_length if ticks is None else ticks)
-        for key, dtype, n in (("reward_sum", torch.float32, E * N), ("steps", torch.int32, E), ("done", torch.int32, E)):
-            t = outputs[key]
-            assert t.is_cuda and t.is_contiguous() and t.dtype == dtype and t.numel() >= n, (key, tuple(t.shape), t.dtype)
+        out_args = evaluation_outputs(outputs, E, AssertionError, reward_elements=E * N)
         if action_trace is not None:
-            t = action_trace
-            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and t.shape[0] >= T and \
-                int(np.prod(t.shape[1:])) == E * N, ("action_trace", tuple(t.shape), t.dtype)
+            check_record(action_trace, "action_trace", "int32", T, E * N, AssertionError)
         name = self._evaluate_entry(width)
         fm.initialize_functions([name])
         args = self._step_args() + [
-            sampler.rng_state, _stream_tag("tick"), np.int32(T), fm.global_address("kIndexToActionArr"), tagger, runner,
-            np.int32(1 if use_argmax else 0), outputs["reward_sum"], outputs["steps"], outputs["done"],
-            np.uint64(0) if action_trace is None else action_trace] + self._extra_launch_args()
+            sampler.rng_state, tick_tag(), np.int32(T), fm.global_address("kIndexToActionArr"), tagger, runner,
+            np.int32(1 if use_argmax else 0)] + out_args + \
+            [NULL if action_trace is None else action_trace] + self._extra_launch_args()
         return fm.get_function(name), args, (64, 1, 1), ((E + 11) // 12, 1), self.live_policy_evaluate_lds_bytes(width)
 
     def image_fits(self, epb):
@@ -349,8 +314,6 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
         fits = [g for g in (fm.packed_geometry(self.num_agents, max_threads=max(m, self.num_agents))
                             for m in (256, 128, 64)) if self.image_fits(g[0])]
         if not fits:
-            from warp_drive_amd.rollout import UnsupportedRolloutShape
-
             raise UnsupportedRolloutShape(f"{self.num_agents} agents: the observation rows of one replica do not fit "
                                           "the LDS image the rollout kernel needs")
         with_cache = [g for g in fits if self.lds_bytes(g[0]) + 4 * g[0] * cache_dwords <= 60000]
@@ -367,8 +330,6 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
         width) -- float32 CUDA tensors from training.policy_kernel.pack_gridworld_policy: the launch evaluates the two
         policy networks itself on every tick's observation rows (HipTagGridWorldRollout_N5_H<width>) instead of reading
         `probabilities`."""
-        from warp_drive_amd.managers.function_manager import _stream_tag
-
         assert env_range is None, "replica ranges are a TagContinuous experiment"
         assert len(probabilities) == 1
         fm, dm = self.cuda_function_manager, self.cuda_data_manager
@@ -384,13 +345,13 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
             epb, block, grid = 12, (64, 1, 1), ((int(dm.meta_info("n_envs")) + 11) // 12, 1)
         args = self._step_args() + [
             sampler.rng_state, probabilities[0], np.int32(probabilities[0].shape[-1]), reset_args[0], reset_args[1],
-            _stream_tag("tick")]
+            tick_tag()]
         if rollout:
             E, N, T = int(dm.meta_info("n_envs")), self.num_agents, int(self.ticks_per_launch)
             F = 4 * N + 1 if self.use_full_observation else 6
             assert int(probabilities[0].shape[-1]) <= 8 and self.image_fits(epb) and len(self.step_actions) == 5, \
                 "the rollout kernel needs the LDS observation image and at most 8 actions"
-            _check_batch(batch, E, N, F, T)
+            batch_args = batch_arguments(batch, T, E, N, F)
             # the rows finished replicas are restored from are kept in LDS for the whole launch (no loads inside the
             # tick loop): the sum of the registered arrays' row lengths per replica, 0 = no room
             lds = self.lds_bytes(epb)
@@ -398,12 +359,10 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
                 lds += 4 * epb * cache_dwords
             else:
                 cache_dwords = 0
-            args += [np.int32(T), batch["obs"], batch["actions"], batch["rewards"], batch["done"], np.int32(cache_dwords)]
+            args += [np.int32(T)] + batch_args + [np.int32(cache_dwords)]
             special = self._specialised_rollout(name, block, cache_dwords)
             if policy is not None:
-                from warp_drive_amd.rollout import UnsupportedRolloutShape
-
-                (tagger, runner), width = policy
+                (tagger, runner), width = policy   # (as given: a malformed `policy` is the caller's bug here)
                 if special is None or not self.has_live_policy_rollout(width, int(probabilities[0].shape[-1])):
                     raise UnsupportedRolloutShape("the live-policy rollout exists for 5 agents with full observations, "
                                                   "5 actions and hidden widths 32 / 64 only")
@@ -423,8 +382,6 @@ class _DeviceStepMixin(CUDAEnvironmentContext):
                         self.n5_lds_bytes(64, cache_dwords, 0, None, round_time_table=False))
             return fm.get_function(name), args, block, grid, lds
         if policy is not None:
-            from warp_drive_amd.rollout import UnsupportedRolloutShape
-
             raise UnsupportedRolloutShape("the live-policy rollout needs ticks_per_launch > 1 and the batch tensors")
         return fm.get_function(name), args, block, grid, self.lds_bytes(epb)
 
@@ -586,9 +543,6 @@ class CUDATagGridWorldWithResetPool(_DeviceStepMixin, TagGridWorld):
         HipTagGridWorldRollout_N5P on `probabilities`, or, with `policy` = ((packed tagger policy, packed runner policy),
         hidden width) -- a shared policy is the same tensor twice -- HipTagGridWorldRollout_N5P_H<width>.  Arguments: the
         N5 entry's, then the pool generator's words, the two pools and their row count."""
-        from warp_drive_amd.managers.function_manager import _stream_tag
-        from warp_drive_amd.rollout import UnsupportedRolloutShape
-
         assert env_range is None, "replica ranges are a TagContinuous experiment"
         assert len(probabilities) == 1
         fm, dm = self.cuda_function_manager, self.cuda_data_manager
@@ -605,7 +559,7 @@ class CUDATagGridWorldWithResetPool(_DeviceStepMixin, TagGridWorld):
                                               "observations, grid_length <= 255 and the loc_x / loc_y pools only")
             pol_args = []
         else:
-            tagger, runner, width = _unpack_policy(policy)
+            tagger, runner, width = unpack_policy_pair(policy)
             if not self.has_live_policy_rollout(width, n_actions):
                 raise UnsupportedRolloutShape("the live-policy rollout with a reset pool exists for 5 agents with full "
                                               "observations, 5 actions, grid_length <= 255 and hidden widths 32 / 64 only")
@@ -615,10 +569,10 @@ class CUDATagGridWorldWithResetPool(_DeviceStepMixin, TagGridWorld):
         _, reset_args, _, _ = resetter.fused_launch(dm, 0, 0)  # builds / refreshes the descriptor table
         E, N, T = int(dm.meta_info("n_envs")), self.num_agents, int(self.ticks_per_launch)
         F = 4 * N + 1
-        _check_batch(batch, E, N, F, T)
+        batch_args = batch_arguments(batch, T, E, N, F)
         cache_dwords = N * F   # the registered reset arrays are exactly the observations (_pool_rollout_shape)
         args = self._step_args() + [
-            sampler.rng_state, probabilities[0], np.int32(n_actions), reset_args[0], reset_args[1], _stream_tag("tick"),
-            np.int32(T), batch["obs"], batch["actions"], batch["rewards"], batch["done"], np.int32(cache_dwords),
-            fm.global_address("kIndexToActionArr")] + pol_args + self._extra_launch_args()
+            sampler.rng_state, probabilities[0], np.int32(n_actions), reset_args[0], reset_args[1], tick_tag(),
+            np.int32(T)] + batch_args + [np.int32(cache_dwords), fm.global_address("kIndexToActionArr")] + pol_args + \
+            self._extra_launch_args()
         return fm.get_function(name), args, (64, 1, 1), ((E + 11) // 12, 1), self.pool_rollout_lds_bytes(width)

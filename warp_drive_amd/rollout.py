@@ -22,15 +22,10 @@ import torch
 from warp_drive_amd.managers import hip_driver as drv
 from warp_drive_amd.managers.function_manager import HIPSampler, _stream_tag
 from warp_drive_amd.utils.constants import Constants
+from warp_drive_amd.utils.launch_checks import UnsupportedRolloutShape  # noqa: F401  (its home; re-exported from here)
 from warp_drive_amd.utils.spaces import Box, Discrete, MultiDiscrete
 
 _ACTIONS = Constants.ACTIONS
-
-
-class UnsupportedRolloutShape(RuntimeError):
-    """an env's tick entry was asked for a variant (live in-kernel policy, presampled actions, ...) that does not exist
-    for this env shape -- a capability answer, raised explicitly (never an `assert`: it must survive `python -O` and must
-    not be confused with an assertion that caught a bug)"""
 
 
 # Replica cohorts of the fused tick (TagContinuous): a multi-tick run() splits the replicas into C ranges, each

@@ -331,7 +331,7 @@ def pack_gridworld_policy(model, out=None):
     network of rollout_policy.h behind a first layer at stride 24): W0
     [H][24] (the 21 inputs of a row padded to 24 floats: every row starts on a 16-byte boundary), b0 [H], W1 [H][H],
     b1 [H], Wp [5][H], bp [5], float32, the block padded to a multiple of four floats.  `out`: refill in place."""
-    from warp_drive_amd.envs.tag_gridworld import gridworld_policy_floats
+    from warp_drive_amd.utils.launch_checks import rp_pad4, rp_policy_floats
 
     w0, b0 = model.fc["0"][0].weight, model.fc["0"][0].bias
     H = w0.shape[0]
@@ -340,7 +340,7 @@ def pack_gridworld_policy(model, out=None):
     w0p[:, :21] = w0.detach().float()
     parts = [w0p, b0, model.fc["1"][0].weight, model.fc["1"][0].bias, model.policy_head[0].weight, model.policy_head[0].bias]
     flat = torch.cat([t.detach().float().reshape(-1) for t in parts])
-    n = gridworld_policy_floats(H)
+    n = rp_pad4(rp_policy_floats(24, H, 5))   # envs/tag_gridworld.py::gridworld_policy_floats
     if out is None:
         out = torch.zeros(n, dtype=torch.float32, device=w0.device)
     assert out.numel() == n

@@ -14,7 +14,9 @@ Further down: `FusedRolloutMixin` (the one-launch rollout with the policy inside
 """
 import numpy as np
 
-from warp_drive_amd.rollout import UnsupportedRolloutShape
+from warp_drive_amd.utils.constants import Constants
+from warp_drive_amd.utils.launch_checks import (NULL, UnsupportedRolloutShape, batch_arguments, check_packed,
+                                                rp_policy_floats, tick_tag, unpack_policy)
 from warp_drive_amd.utils.spaces import Box, Discrete, MultiDiscrete
 
 MAX_HEADS = 4  # WD_TICK_MAX_HEADS of include/wd_env_tick.h
@@ -50,8 +52,6 @@ def custom_tick_launch(env, tick_kernel_name, step_args, sampler, probabilities,
     RNG state, number of heads, four probability pointers and four head sizes (unused ones null / 0), reset table and
     its entry count, stream tag, and the tick count LAST (np.int32: a launch plan's multi-tick form rewrites it).
     probabilities: one contiguous float32 tensor [n_envs, n_agents, actions of the head] per head."""
-    from warp_drive_amd.managers.function_manager import _stream_tag
-
     if probabilities is None:
         raise UnsupportedRolloutShape(f"{type(env).__name__}: presampled actions were asked of {tick_kernel_name}, "
                                       "which draws its actions itself")
@@ -63,13 +63,12 @@ def custom_tick_launch(env, tick_kernel_name, step_args, sampler, probabilities,
     fn = fm.get_function(tick_kernel_name)
     _, reset_args, _, _ = resetter.fused_launch(dm, 0, 0)  # builds / refreshes the descriptor table
     table, n_arrays = reset_args[0], reset_args[1]
-    null = np.uint64(0)
     pad = MAX_HEADS - len(sizes)
     args = list(env.cuda_step_function_feed(step_args))
     args += [sampler.rng_state, np.int32(len(sizes))]
-    args += list(probabilities) + [null] * pad
+    args += list(probabilities) + [NULL] * pad
     args += [np.int32(a) for a in sizes] + [np.int32(0)] * pad
-    args += [table, np.int32(n_arrays), _stream_tag("tick"), np.int32(ticks)]
+    args += [table, np.int32(n_arrays), tick_tag(), np.int32(ticks)]
     return fn, args, tick_block(env.num_agents), fm.grid, 0
 
 
@@ -123,8 +122,7 @@ MAX_ACTIONS = 8  # WD_ROLLOUT_MAX_ACTIONS of include/wd_env_rollout.h
 
 def rollout_policy_floats(obs_size, width, n_actions):
     """elements of the packed policy (training.policy_kernel.pack_rollout_policy; wd_rollout_policy_floats of the header)"""
-    F, H, A = int(obs_size), int(width), int(n_actions)
-    return F * H + H + H * H + H + A * H + A
+    return rp_policy_floats(obs_size, width, n_actions)
 
 
 def custom_rollout_launch(env, kernel_name, step_args, sampler, n_actions, packed, width, resetter, batch, ticks):
@@ -134,11 +132,6 @@ def custom_rollout_launch(env, kernel_name, step_args, sampler, n_actions, packe
     [T, E, N] float32, done [T, E] int32, T >= ticks), and the tick count LAST (np.int32).  packed: the contiguous float32
     CUDA tensor of pack_rollout_policy for hidden width `width`.  Dynamic LDS: 4 bytes per packed float, rounded up
     to 16."""
-    import torch
-
-    from warp_drive_amd.managers.function_manager import _stream_tag
-    from warp_drive_amd.utils.constants import Constants
-
     who = f"{type(env).__name__} ({kernel_name})"
     width, n_actions, ticks = int(width), int(n_actions), int(ticks)
     if not 1 <= n_actions <= MAX_ACTIONS:
@@ -150,28 +143,18 @@ def custom_rollout_launch(env, kernel_name, step_args, sampler, n_actions, packe
     E, N = int(dm.meta_info("n_envs")), int(env.num_agents)
     F = int(dm.get_shape(Constants.OBSERVATIONS)[-1])
     n_w = rollout_policy_floats(F, width, n_actions)
-    if not (getattr(packed, "is_cuda", False) and packed.dtype == torch.float32 and packed.is_contiguous()
-            and packed.numel() == n_w):
-        raise UnsupportedRolloutShape(f"{who}: the packed policy must be a contiguous float32 CUDA tensor of {n_w} elements "
-                                      f"(observation {F}, width {width}, {n_actions} actions)")
+    check_packed(packed, n_w, UnsupportedRolloutShape, f"{who}: the packed policy",
+                 f"observation {F}, width {width}, {n_actions} actions")
     if batch is None:
         raise UnsupportedRolloutShape(f"{who}: the batch tensors are missing; the rollout records every tick")
-    want = {"obs": ((E, N, F), torch.float32), "actions": ((E, N, 1), torch.int32), "rewards": ((E, N), torch.float32),
-            "done": ((E,), torch.int32)}
-    for key, (shape, dtype) in want.items():
-        t = batch.get(key) if hasattr(batch, "get") else None
-        if not (getattr(t, "is_cuda", False) and t.is_contiguous() and t.dtype == dtype and t.shape[0] >= ticks
-                and tuple(t.shape[1:]) == shape):
-            got = None if t is None else (tuple(getattr(t, "shape", ())), getattr(t, "dtype", None))
-            raise UnsupportedRolloutShape(f"{who}: batch[{key!r}] must be a contiguous {dtype} CUDA tensor "
-                                          f"[>= {ticks}, {', '.join(map(str, shape))}], not {got}")
+    batch_args = batch_arguments(batch, ticks, E, N, F, error=UnsupportedRolloutShape, who=f"{who}: ")
     fm.initialize_functions([kernel_name])
     fn = fm.get_function(kernel_name)
     _, reset_args, _, _ = resetter.fused_launch(dm, 0, 0)  # builds / refreshes the descriptor table
     table, n_arrays = reset_args[0], reset_args[1]
     args = list(env.cuda_step_function_feed(step_args))
-    args += [sampler.rng_state, packed, np.int32(n_actions), table, np.int32(n_arrays), _stream_tag("tick"),
-             batch["obs"], batch["actions"], batch["rewards"], batch["done"], np.int32(ticks)]
+    args += [sampler.rng_state, packed, np.int32(n_actions), table, np.int32(n_arrays), tick_tag()] + batch_args + \
+        [np.int32(ticks)]
     return fn, args, tick_block(N), fm.grid, (4 * n_w + 15) // 16 * 16
 
 
@@ -232,11 +215,7 @@ class FusedRolloutMixin(FusedTickMixin):
         if policy is None:
             raise UnsupportedRolloutShape(f"{who}: a batch recorded inside the kernel without an in-kernel policy was "
                                           "asked; the fused tick of wd_env_tick.h records nothing")
-        try:
-            packed, width = policy
-            width = int(width)
-        except (TypeError, ValueError) as err:
-            raise UnsupportedRolloutShape(f"{who}: policy = (packed weights, hidden width), not {policy!r}") from err
+        packed, width = unpack_policy(policy, who=f"{who}: ")
         space = self.action_space[0]
         n_actions = int(space.n) if isinstance(space, Discrete) else 0
         why = self._rollout_refusal(width, n_actions)
