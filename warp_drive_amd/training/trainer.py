@@ -993,7 +993,10 @@ class Trainer:
         this trainer is one launch and the env has an Evaluate entry (Cartpole by default; Acrobot / MountainCar under
         `fused_rollout_policy: "all"`, which is what makes their training rollout one launch; TagGridWorld with 5
         agents, full observations and [32, 32] / [64, 64] policies ALSO only under `fused_rollout_policy: "all"` -- its
-        training rollout is one launch by default, its evaluation is opt-in: EVALUATE_POLICY_OPT_IN), one kernel runs
+        training rollout is one launch by default, its evaluation is opt-in: EVALUATE_POLICY_OPT_IN; a CUSTOM env whose
+        class has the evaluate mixin of `utils/custom_tick.py` and whose code object has the Evaluate entries of
+        include/wd_env_evaluate.h, again only under `fused_rollout_policy: "all"`, one Discrete head, no reset pool,
+        [32, 32] / [64, 64] policies -- examples/rendezvous_evaluate/), one kernel runs
         the whole episode of every replica with the policies inside it -- one per agent group of the env, each packed
         from its owning policy's current weights -- and writes a reward sum per agent and a step count per replica.
         "per tick": everything else -- policy forward, (one-hot rows when greedy,) the single-tick engine, HipEvaluateAccumulate on `rewards` / `_done_`, `episode_length` times, with no host

@@ -9,14 +9,15 @@ recorded inside the kernel, a policy or an actor evaluated inside the kernel, pr
 more than four heads.  An env with a reset pool needs nothing from here: `RolloutEngine` keeps the per-tick plan for it
 (the mixin does not set TICK_POOL_RESET).
 
-Further down: `FusedRolloutMixin` (the one-launch rollout with the policy inside the kernel, include/wd_env_rollout.h) and
-`FusedUpdateMixin` (the A2C / PPO update as five launches, include/wd_env_update.h).
+Further down: `FusedRolloutMixin` (the one-launch rollout with the policy inside the kernel, include/wd_env_rollout.h),
+`FusedUpdateMixin` (the A2C / PPO update as five launches, include/wd_env_update.h) and `FusedEvaluateMixin` (one episode of
+every replica in one launch, greedy or sampled, include/wd_env_evaluate.h).
 """
 import numpy as np
 
 from warp_drive_amd.utils.constants import Constants
-from warp_drive_amd.utils.launch_checks import (NULL, UnsupportedRolloutShape, batch_arguments, check_packed,
-                                                rp_policy_floats, tick_tag, unpack_policy)
+from warp_drive_amd.utils.launch_checks import (NULL, UnsupportedRolloutShape, batch_arguments, check_packed, check_record,
+                                                evaluation_outputs, rp_policy_floats, tick_tag, unpack_policy)
 from warp_drive_amd.utils.spaces import Box, Discrete, MultiDiscrete
 
 MAX_HEADS = 4  # WD_TICK_MAX_HEADS of include/wd_env_tick.h
@@ -170,25 +171,32 @@ class FusedRolloutMixin(FusedTickMixin):
     ROLLOUT_POLICY_OPT_IN = True
     ticks_per_launch = 1
 
-    def _rollout_refusal(self, width, n_actions):
-        """why this env / shape has no in-kernel policy of hidden width `width` with `n_actions` actions; None: it has"""
+    def _policy_entry_refusal(self, pattern, widths, bounds, width, n_actions):
+        """why this env / shape has no entry `pattern` (with `{width}`) that evaluates a policy of hidden width `width`
+        with `n_actions` actions inside the kernel -- `widths`: the widths the entries exist for, `bounds`: their
+        `__launch_bounds__` by width; None: it has"""
         space = self.action_space[0]
         if not isinstance(space, Discrete):
             return f"an action space of type {type(space).__name__} (one Discrete head only)"
         if not 1 <= int(n_actions) <= MAX_ACTIONS:
             return f"{int(n_actions)} actions (1 to {MAX_ACTIONS})"
-        if int(width) not in tuple(self.ROLLOUT_POLICY_WIDTHS) or int(width) not in self.ROLLOUT_MAX_THREADS:
-            return f"a hidden width of {int(width)} (entries: {sorted(self.ROLLOUT_POLICY_WIDTHS)})"
+        if int(width) not in tuple(widths) or int(width) not in bounds:
+            return f"a hidden width of {int(width)} (entries: {sorted(widths)})"
         threads = tick_block(self.num_agents)[0]
-        if threads > int(self.ROLLOUT_MAX_THREADS[int(width)]):
+        if threads > int(bounds[int(width)]):
             return (f"a block of {threads} threads ({self.num_agents} agents) over the launch bound "
-                    f"{self.ROLLOUT_MAX_THREADS[int(width)]} of the width-{int(width)} entry")
+                    f"{bounds[int(width)]} of the width-{int(width)} entry")
         if len(self.cuda_data_manager.reset_target_to_pool) > 0:
             return "a reset pool"
-        name = self.ROLLOUT_KERNEL.format(width=int(width))
+        name = pattern.format(width=int(width))
         if not self.cuda_function_manager.has_function(name):
             return f"the entry {name}, which the env's code object does not have"
         return None
+
+    def _rollout_refusal(self, width, n_actions):
+        """why this env / shape has no in-kernel policy of hidden width `width` with `n_actions` actions; None: it has"""
+        return self._policy_entry_refusal(self.ROLLOUT_KERNEL, self.ROLLOUT_POLICY_WIDTHS, self.ROLLOUT_MAX_THREADS, width,
+                                          n_actions)
 
     def has_live_policy_rollout(self, width, n_actions):
         """does an entry exist that evaluates a policy of hidden width `width` with `n_actions` actions for this env's
@@ -269,3 +277,93 @@ class FusedUpdateMixin(FusedRolloutMixin):
             raise UnsupportedRolloutShape(f"{type(self).__name__}: {why}")
         return pgck.PgCustomUpdateKernels(self.cuda_function_manager, self.UPDATE_KERNEL_PREFIX, num_envs, batch_len,
                                           n_agents, width, obs_size, n_actions, device, **options)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# EVALUATION IN ONE LAUNCH (docs/custom_environments.md, "Evaluation in one launch"): the launch of a
+# `Hip<Name>Evaluate_H<width>` entry written with include/wd_env_evaluate.h.
+def custom_evaluate_launch(env, kernel_name, step_args, sampler, n_actions, packed, width, resetter, use_argmax, outputs,
+                           action_trace, ticks):
+    """(function, arguments, block, grid, dynamic LDS bytes) of `kernel_name`, an entry whose parameters are the step's
+    own -- `step_args` -- followed by WD_EVALUATE_PARAMS: RNG state, packed policy, action count, reset table and its entry
+    count, stream tag, use_argmax, reward_sum (float32, at least E * N elements), steps and done (int32, at least E), the
+    action trace (int32 [>= ticks, E, N], or null), and the tick count LAST (np.int32).  Dynamic LDS: 4 bytes per packed
+    float, rounded up to 16.  Whatever is not served is an `UnsupportedRolloutShape` that names the request."""
+    who = f"{type(env).__name__} ({kernel_name})"
+    width, n_actions, ticks = int(width), int(n_actions), int(ticks)
+    if not 1 <= n_actions <= MAX_ACTIONS:
+        raise UnsupportedRolloutShape(f"{who}: {n_actions} actions were asked of the in-kernel policy of "
+                                      f"wd_env_evaluate.h (1 to {MAX_ACTIONS})")
+    if ticks < 1:
+        raise UnsupportedRolloutShape(f"{who}: an evaluation of {ticks} ticks was asked")
+    fm, dm = env.cuda_function_manager, env.cuda_data_manager
+    E, N = int(dm.meta_info("n_envs")), int(env.num_agents)
+    F = int(dm.get_shape(Constants.OBSERVATIONS)[-1])
+    n_w = rollout_policy_floats(F, width, n_actions)
+    check_packed(packed, n_w, UnsupportedRolloutShape, f"{who}: the packed policy",
+                 f"observation {F}, width {width}, {n_actions} actions")
+    if not hasattr(outputs, "__getitem__") or any(key not in outputs for key in ("reward_sum", "steps", "done")):
+        raise UnsupportedRolloutShape(f"{who}: outputs = {{'reward_sum': ..., 'steps': ..., 'done': ...}}, not {outputs!r}")
+    out_args = evaluation_outputs(outputs, E, UnsupportedRolloutShape, reward_elements=E * N)
+    if action_trace is not None:
+        got = (tuple(getattr(action_trace, "shape", ())), getattr(action_trace, "dtype", None))
+        check_record(action_trace, "action_trace", "int32", ticks, (E, N), UnsupportedRolloutShape,
+                     f"{who}: action_trace must be a contiguous torch.int32 CUDA tensor [>= {ticks}, {E}, {N}], not {got}")
+    if resetter is None:
+        raise UnsupportedRolloutShape(f"{who}: the env has no resetter (EnvWrapper sets `cuda_env_resetter`); the "
+                                      "evaluation restores every replica from the reset table")
+    fm.initialize_functions([kernel_name])
+    fn = fm.get_function(kernel_name)
+    _, reset_args, _, _ = resetter.fused_launch(dm, 0, 0)  # builds / refreshes the descriptor table
+    table, n_arrays = reset_args[0], reset_args[1]
+    args = list(env.cuda_step_function_feed(step_args))
+    args += [sampler.rng_state, packed, np.int32(n_actions), table, np.int32(n_arrays), tick_tag(),
+             np.int32(1 if use_argmax else 0)] + out_args + [NULL if action_trace is None else action_trace, np.int32(ticks)]
+    return fn, args, tick_block(N), fm.grid, (4 * n_w + 15) // 16 * 16
+
+
+class FusedEvaluateMixin(FusedRolloutMixin):
+    """`has_live_policy_evaluate()` and `evaluate_launch()` for an env class whose device source has, next to its Rollout
+    entries, the entries `Hip<Name>Evaluate_H<width>` written with include/wd_env_evaluate.h.  The class says
+    EVALUATE_KERNEL, a pattern with `{width}`; the entries' parameters are TICK_STEP_ARGS followed by WD_EVALUATE_PARAMS.
+    Combines with `FusedUpdateMixin` in one class.  `Trainer.evaluate_episodes` takes the one launch under
+    `trainer.fused_rollout_policy: "all"` only (EVALUATE_POLICY_OPT_IN)."""
+
+    EVALUATE_KERNEL = None
+    EVALUATE_MAX_THREADS = None  # the entries' __launch_bounds__ by width; None: the class's ROLLOUT_MAX_THREADS
+    EVALUATE_POLICY_OPT_IN = True
+
+    def _evaluate_refusal(self, width, n_actions):
+        """why this env / shape has no one-launch evaluation of hidden width `width` with `n_actions` actions; None: it
+        has"""
+        if not self.EVALUATE_KERNEL:
+            return f"an Evaluate entry, which {type(self).__name__} does not name (EVALUATE_KERNEL)"
+        bounds = self.ROLLOUT_MAX_THREADS if self.EVALUATE_MAX_THREADS is None else self.EVALUATE_MAX_THREADS
+        return self._policy_entry_refusal(self.EVALUATE_KERNEL, self.ROLLOUT_POLICY_WIDTHS, bounds, width, n_actions)
+
+    def has_live_policy_evaluate(self, width, n_actions):
+        """does an entry exist that runs one episode of every replica with a policy of hidden width `width` and
+        `n_actions` actions inside it, for this env's shape?  (Trainer.evaluate_episodes asks before `evaluate_launch`)"""
+        return self._evaluate_refusal(width, n_actions) is None
+
+    def evaluate_launch(self, sampler, policy, use_argmax, outputs, action_trace=None, ticks=None):
+        """One episode of every replica in ONE launch of the Evaluate entry of the policy's width: from the state,
+        observation, `_timestep_` and `_done_` the arrays hold, at most `ticks` (default: episode_length) ticks of policy
+        network -> action (use_argmax: the first maximum of the probabilities; else the rollout's counting draw) -> step,
+        up to the replica's first done.  policy = (packed float32 CUDA tensor, hidden width) as in `tick_launch`.
+        outputs = {"reward_sum": float32 [E, N], "steps": int32 [E], "done": int32 [E]}, CUDA tensors (at least that many
+        elements); `action_trace` (optional) int32 [>= ticks, E, N]: row k = tick k's actions of the replicas still
+        running.  The launch writes those, in sampled mode the sampler's epoch words, and the env's arrays: every replica
+        is left as `reset_when_done(mode="force_reset")` leaves it (the table of `self.cuda_env_resetter`).
+        Returns (function, arguments, block, grid, shared bytes)."""
+        who = f"{type(self).__name__} ({self.EVALUATE_KERNEL})"
+        packed, width = unpack_policy(policy, who=f"{who}: ")
+        space = self.action_space[0]
+        n_actions = int(space.n) if isinstance(space, Discrete) else 0
+        why = self._evaluate_refusal(width, n_actions)
+        if why is not None:
+            raise UnsupportedRolloutShape(f"{who}: {why} was asked of the one-launch evaluation of wd_env_evaluate.h")
+        T = int(self.episode_length if ticks is None else ticks)
+        return custom_evaluate_launch(self, self.EVALUATE_KERNEL.format(width=width), self.TICK_STEP_ARGS, sampler,
+                                      n_actions, packed, width, getattr(self, "cuda_env_resetter", None), use_argmax,
+                                      outputs, action_trace, T)
