@@ -66,6 +66,7 @@
 
 // phases (each header: its own anonymous-namespace block; order = dependency order)
 #include "tc_types.h"
+#include "tc_kernarg.h"
 #include "tc_fetch.h"
 #include "tc_sample.h"
 #include "tc_move.h"
@@ -76,51 +77,11 @@
 #include "tc_fast.h"
 #include "tc_generic.h"
 
-#define WD_TC_PARAMS                                                                              \
-  float *loc_x_arr, float *loc_y_arr, float *speed_arr, float *direction_arr,                     \
-      float *acceleration_arr, const int *agent_types_arr, float *edge_hit_reward_penalty,        \
-      float kEdgeHitPenalty, float kGridLength, const float *acceleration_actions_arr,            \
-      const float *turn_actions_arr, float kMaxSpeed, int kNumOtherAgentsObserved,                \
-      const float *skill_levels_arr, int kRunnerExitsGameAfterTagged, int *still_in_the_game_arr, \
-      int kUseFullObservation, float *obs_arr, const int *action_indices_arr,                     \
-      float *neighbor_distances_arr, int *neighbor_ids_sorted_by_distance_arr,                    \
-      int *nearest_neighbor_ids, float *rewards_arr, const float *step_rewards_arr,               \
-      int *num_runners_arr, float kDistanceMarginForReward, float kTagRewardForTagger,            \
-      float kTagPenaltyForRunner, float kEndOfGameRewardForRunner, int *done_arr,                 \
-      int *env_timestep_arr, int kNumAgents, int kEpisodeLength, int kNumEnvs,                    \
-      int kNumAccelerationActions, int kNumTurnActions, int *obs_rows_cleared_arr,                 \
-      unsigned *knn_prev_arr, int kEnvBegin
-
-#define WD_TC_PACK()                                                                              \
-  TcArgs a;                                                                                       \
-  a.loc_x = loc_x_arr; a.loc_y = loc_y_arr; a.speed = speed_arr; a.direction = direction_arr;     \
-  a.acceleration = acceleration_arr; a.agent_types = agent_types_arr;                             \
-  a.edge_pen_arr = edge_hit_reward_penalty; a.edge_hit_penalty = kEdgeHitPenalty;                 \
-  a.grid_length = kGridLength; a.acc_actions = acceleration_actions_arr;                          \
-  a.turn_actions = turn_actions_arr; a.max_speed = kMaxSpeed; a.K = kNumOtherAgentsObserved;      \
-  a.skill_levels = skill_levels_arr; a.runner_exits = kRunnerExitsGameAfterTagged;                \
-  a.sig_arr = still_in_the_game_arr; a.use_full_obs = kUseFullObservation; a.obs = obs_arr;       \
-  a.actions = action_indices_arr; a.nearest_ids = nearest_neighbor_ids; a.rewards = rewards_arr;  \
-  a.step_rewards = step_rewards_arr; a.num_runners = num_runners_arr;                             \
-  a.margin = kDistanceMarginForReward; a.tag_reward = kTagRewardForTagger;                        \
-  a.tag_penalty = kTagPenaltyForRunner; a.end_reward = kEndOfGameRewardForRunner;                 \
-  a.done = done_arr; a.timestep = env_timestep_arr; a.N = kNumAgents; a.T = kEpisodeLength;       \
-  a.E = kNumEnvs; a.env_begin = kEnvBegin; a.obs_rows_cleared = obs_rows_cleared_arr;              \
-  a.knn_prev = knn_prev_arr;                                                                      \
-  (void)neighbor_distances_arr; (void)neighbor_ids_sorted_by_distance_arr;
-
-// Fused rollout tick: sample both action heads + step + reset finished replicas in ONE launch
-// (the reference needs 2 sampler launches, the step, and 13 reset launches per tick,
-// trainer_base.py:392-426).  Same arguments as the step plus the sampler / reset inputs.
-#define WD_TC_FUSE_PARAMS                                                                      \
-  , uint32_t *rng_state, const float *probs_acc, const float *probs_turn, const void *reset_table, \
-      int n_reset_arrays, int stream_tag
-#define WD_TC_FUSE_PACK()                                                                      \
-  TcFuse fz;                                                                                   \
-  fz.rng_state = rng_state; fz.probs_acc = probs_acc; fz.probs_turn = probs_turn;              \
-  fz.actions_out = const_cast<int *>(action_indices_arr);                                      \
-  fz.reset_table = (const wd_reset_entry *)reset_table; fz.n_reset_arrays = n_reset_arrays;      \
-  fz.stream_tag = stream_tag;
+// The arguments of the entries are listed ONCE, in tc_kernarg.h: WD_TC_PARAMS (a Step entry's), WD_TC_FUSE_PARAMS (what a
+// Tick entry takes behind them: the reference needs 2 sampler launches, the step, and 13 reset launches per tick,
+// trainer_base.py:392-426; the fused tick samples both action heads, steps and restores finished replicas in ONE launch)
+// and WD_TC_ROLLOUT_PARAMS (the number of ticks of the multi-tick entry), with WD_TC_PACK / WD_TC_FUSE_PACK, which put
+// them into TcArgs / TcFuse.
 
 // ---- entries.  This file is compiled into SEVERAL code objects (warp_drive_amd/build.py UNITS; a build of all of them
 // runs in parallel, and tuning one specialisation rebuilds one small object):
@@ -227,8 +188,8 @@ static_assert(WD_TC_SHAPE_N <= 128, "the shape-specialised entries use the 7-bit
 // plus the number of ticks; every block takes its replica through that many ticks (tc_fast_rollout, tc_fast.h).  A separate
 // object, so that the one-tick entries below (and the records keyed to their object) never move with it.
 static_assert(WD_TC_SHAPE_N > 64 && WD_TC_SHAPE_THREADS == 128, "one replica per 128-thread block");
-__global__ void __launch_bounds__(512, 4) WD_TC_SHAPE_NAME(HipTagContinuousRollout_K)(WD_TC_PARAMS WD_TC_FUSE_PARAMS,
-                                                                                      int kNumTicks) {
+__global__ void __launch_bounds__(512, 4) WD_TC_SHAPE_NAME(HipTagContinuousRollout_K)(WD_TC_PARAMS WD_TC_FUSE_PARAMS
+                                                                                          WD_TC_ROLLOUT_PARAMS) {
   WD_TC_SMEM();
   WD_TC_PACK();
   WD_TC_FUSE_PACK();

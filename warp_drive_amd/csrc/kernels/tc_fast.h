@@ -3,6 +3,7 @@
 // and the kernel entries); split by phase in round 6 with every shipped code object byte-identical before / after.
 #pragma once
 #include "wd_common.h"
+#include "tc_kernarg.h"
 #include "tc_fetch.h"
 #include "tc_sample.h"
 #include "tc_move.h"
@@ -93,7 +94,8 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
     in = cy->in;
     reloaded = cy->reload != 0;
     if (reloaded) {
-      tc_load_state(in, a, fz, env0, epb, N, n_acc, n_turn, tid, tick == 0);
+      const TcPhase pv(a, fz);  // (a view of its own: cold)
+      tc_load_state(in, pv.a, pv.fz, env0, epb, N, n_acc, n_turn, tid, tick == 0);
       cy->in.type = in.type; cy->in.skill = in.skill; cy->in.step_reward = in.step_reward;  // (no trip writes these)
     }
   } else {
@@ -102,7 +104,7 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   const bool tab_in_lds = (n_acc <= WD_TC_TAB) && (n_turn <= WD_TC_TAB);
   int n_taggers_ = n_taggers_in;
   if constexpr (LOOP) {
-    if (tick == 0) n_taggers_ = tc_build_tables(tb, a, N, n_acc, n_turn, tab_in_lds, in);
+    if (tick == 0) n_taggers_ = tc_build_tables(tb, a, N, n_acc, n_turn, tab_in_lds, in, tid);
   } else {
     n_taggers_ = tc_build_tables(tb, a, N, n_acc, n_turn, tab_in_lds, in);
   }
@@ -116,13 +118,16 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   const int li = tid;           // index into LDS arrays (= el * N + ag)
   const int agents_here = min(epb, a.E - env0) * N;
   if constexpr (LOOP) {
+    // the pointers of this phase, taken behind the trip-end barrier and BEFORE the first piece of the slabs: the wait for
+    // them stands in front of the store below, not inside the slab window
+    const TcPhase pv(a, fz);
     // (a store between the slab issue and the slab wait would be waited for with the slabs: this one goes first)
-    if (active && ag == 0) a.done[env] = 0;  // a replica that finished (and was reset) last tick
+    if (active && ag == 0) pv.a.done[env] = 0;  // a replica that finished (and was reset) last tick
     // the slabs alias the work area: issued here, after the trip-end barrier, never earlier
     // (straight-line code: the shape is a constant of this object -- a.N == SN, n_acc == n_turn == SA, one replica per
     // block, all set by the entry -- and so is where the slabs lie)
     static_assert(!LOOP || (SN > 0 && SA > 0 && ST == WD_TC_BLOCKDIM), "the multi-tick entry is built for one shape");
-    tc_fetch_slabs_straight<SN, SA, ST>(slab_acc, slab_turn, fz.probs_acc, fz.probs_turn, env0, wave, lane);
+    tc_fetch_slabs_straight<SN, SA, ST>(slab_acc, slab_turn, pv.fz.probs_acc, pv.fz.probs_turn, env0, wave, lane);
     WD_TC_PROBE(1);
   }
   int2 sampled = in.sampled;
@@ -136,7 +141,7 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   if constexpr (LOOP) {
     // (two slabs side by side, no tc_one_slab path: replicas of at most 128 agents, which is what the 7-bit ids mean)
     static_assert(!LOOP || IDB == 7, "tc_sample_heads_carried samples from two slabs: replicas of at most 128 agents");
-    sampled = tc_sample_heads_carried<SA>(fz, in.epoch, cy->k0, cy->k1, active, gi, li, slab_acc, slab_turn, n_acc, n_turn);
+    sampled = tc_sample_heads_carried<SA>(a, fz, in.epoch, cy->k0, cy->k1, active, gi, li, slab_acc, slab_turn, n_acc, n_turn);
     if (compact && lane == 0) tb.live_cnt[wave] = __popcll(live_mask);  // (no LDS access between slab issue and slab wait)
   } else if (FUSED) {
     if (active && ag == 0) a.done[env] = 0;  // a replica that finished (and was reset) last tick
@@ -145,6 +150,8 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   WD_TC_PROBE(2);
   __syncthreads();  // tables are published; every wavefront is done with the slabs
   WD_TC_PROBE(3);
+  // (LOOP: the state arrays the move stores to, from a view taken behind the barrier)
+  typename TcPhaseArgs<LOOP>::type pv_move = tc_phase<LOOP>(a, fz);
   // packed index of this lane's agent among the agents in the game, and their number
   int my_c = ag, n_live = N;
   if (compact) {
@@ -187,7 +194,7 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   const int sg = in.sg;
   const bool is_runner = active && (in.type == 0) && (sg != 0);  // member of self.runners
   if (active) {
-    const TcMoved m = tc_move<LOOP>(a, tb, in, sampled, gi, tab_in_lds, LOOP ? cy : nullptr, LOOP ? lc : nullptr);
+    const TcMoved m = tc_move<LOOP>(tc_phase_a(pv_move), tb, in, sampled, gi, tab_in_lds, LOOP ? cy : nullptr, LOOP ? lc : nullptr);
     edge_pen = m.edge_pen; my_x = m.x; my_y = m.y;
     if constexpr (LOOP) {  // what the next trip would read back
       cy->in.x = m.x; cy->in.y = m.y;
@@ -237,11 +244,11 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
     // bit 0: in the game before this tick's tagging; bit 1: the observation row in HBM is all zeros already
     l.sig[li] = (sg ? 1 : 0) | (in.cleared ? 2 : 0);
     // after this tick's gather (either form) the row of an agent out of the game is zeros, the row of one in it is not
-    if ((in.cleared != 0) != (sg == 0)) a.obs_rows_cleared[gi] = sg ? 0 : 1;
+    if ((in.cleared != 0) != (sg == 0)) tc_phase_a(pv_move).obs_rows_cleared[gi] = sg ? 0 : 1;
     l.tagcnt[li] = 0;
     if (ag == 0) {
       const int t = in.tstep + 1;  // :800
-      a.timestep[env] = t;
+      tc_phase_a(pv_move).timestep[env] = t;
       tb.tstep[el] = t;
       // float(t) / episode_length, :474 (LOOP: by the reciprocal, proved for t = 1 .. T by the same verifier)
       if constexpr (LOOP) tb.tfrac[el] = (float)tc_div_const((double)t, (double)a.T, lc->r_T);
@@ -285,7 +292,7 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
     // the roots are taken only by a wavefront with a runner near enough for them to matter; lanes that are not runners
     // take no part in that vote
     if (is_runner)
-      tagged = tc_find_tag<true>(a, tb, l.xy + el * NP, l.tagcnt + el * N, &tb.nrun[el], n_taggers, my_x, my_y, lc->Bc);
+      tagged = tc_find_tag<true>(tc_phase_a(pv_move), tb, l.xy + el * NP, l.tagcnt + el * N, &tb.nrun[el], n_taggers, my_x, my_y, lc->Bc);
   } else {
     if (is_runner)
       tagged = tc_find_tag(a, tb, l.xy + el * NP, l.tagcnt + el * N, &tb.nrun[el], n_taggers, my_x, my_y);
@@ -613,6 +620,7 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
     // ((env0 * N + row_agent) * K) int32, 8-byte aligned.  Nothing reads the 16-bit LDS copies back for it
     // (tc_flush_ids, which the one-tick entries keep, did so for every row on every tick).
     const bool any_out_of_order = __ballot(!in_order) != 0ull;  // wave-uniform
+    const TcPhase pv_ids(a, fz);  // (nearest_ids alone)
     if (searcher) {
       // the LDS row, for the gather: ten halfwords as five dwords (rows are 20 bytes apart; -1 gives 0xffff)
       unsigned *const idrow = (unsigned *)(l.ids + row_agent * KMAX);
@@ -629,7 +637,7 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
 #pragma unroll
         for (int k = 0; k < KMAX; ++k) nid[k] = (int)((const short *)hrow)[k];
       }
-      tc_store_id_row<false>(a.nearest_ids + (long)env0 * (SN * KMAX), __umul24((unsigned)row_agent, 4u * KMAX), nid);
+      tc_store_id_row<false>(pv_ids.a.nearest_ids + (long)env0 * (SN * KMAX), __umul24((unsigned)row_agent, 4u * KMAX), nid);
     }
     // An agent out of the game has the row ten times -1, and so it had on the tick before -- unless this is the first
     // tick it is out (an agent tagged on trip t is in the game, and a searcher, on t; on t + 1 it arrives here with
@@ -641,7 +649,7 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
       int none[KMAX];
 #pragma unroll
       for (int k = 0; k < KMAX; ++k) none[k] = -1;
-      tc_store_id_row<true>(a.nearest_ids + (long)env0 * (SN * KMAX), __umul24((unsigned)ag, 4u * KMAX), none);
+      tc_store_id_row<true>(pv_ids.a.nearest_ids + (long)env0 * (SN * KMAX), __umul24((unsigned)ag, 4u * KMAX), none);
     }
   } else {
     const int ebase = el * N;
@@ -668,6 +676,7 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   // evenly over its wavefronts (105 agents: 53 + 52 rows instead of 64 + 41: one chunk less on the
   // longer side), so a wavefront also gathers rows whose neighbours another wavefront found
   __syncthreads();
+  typename TcPhaseArgs<LOOP>::type pv_rows = tc_phase<LOOP>(a, fz);  // (LOOP: the observation array, from a view taken behind the barrier)
   const int rpw = (agents_here + n_waves - 1) / n_waves;
   const int wrow0 = wave * rpw;
   const int wrows = max(0, min(rpw, agents_here - wrow0));
@@ -686,7 +695,7 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   if (n_live_rows * SPARSE_DEN <= wrows * SPARSE_NUM) {
     if constexpr (LOOP) {
       static_assert(!LOOP || (EXACTK && KMAX == 10), "the descriptor flush of the multi-tick entry is built for K = 10");
-      tc_gather_rows_sparse<true, KMAX>(a, l, tb, stage, env0, wrow0, wrows, lane, K, N, invK, invN);
+      tc_gather_rows_sparse<true, KMAX>(tc_phase_a(pv_rows), l, tb, stage, env0, wrow0, wrows, lane, K, N, invK, invN);
     } else {
       tc_gather_rows_sparse(a, l, tb, stage, env0, wrow0, wrows, lane, K, N, invK, invN);
     }
@@ -694,7 +703,7 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
     // the same chunks, items and flush as below with what the one built shape fixes taken out of the chunk loop
     // (tc_rows.h, TcLeanDense)
     static_assert(!LOOP || (EXACTK && KMAX == 10 && IDB == 7 && SN > 64 && SN <= 128), "two wavefronts, one replica per block");
-    tc_gather_rows_dense_lean<KMAX, SN>(a, l, tb, stage, env0, wave, lane, live_rows);
+    tc_gather_rows_dense_lean<KMAX, SN>(tc_phase_a(pv_rows), l, tb, stage, env0, wave, lane, live_rows);
   } else {
     // observation rows, R rows per chunk: work item = (row, neighbour slot) -> 7 values at
     // row*F + c*K + k of the chunk image; then the time column; then the chunk leaves as one run.
@@ -776,14 +785,15 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   WD_TC_PROBE(14);
 
   // ------------------------------------------------------------ rewards / done
-  if (active) tc_finish_agent(a, tb, el, ag, gi, env, sg, is_runner, tagged, l.tagcnt[li], edge_pen, in.step_reward, FUSED);
+  typename TcPhaseArgs<LOOP>::type pv_fin = tc_phase<LOOP>(a, fz);  // (LOOP: rewards, still_in_the_game, num_runners, done, behind the barrier)
+  if (active) tc_finish_agent(tc_phase_a(pv_fin), tb, el, ag, gi, env, sg, is_runner, tagged, l.tagcnt[li], edge_pen, in.step_reward, FUSED);
   if (FUSED) {
     __syncthreads();  // doneflag
     bool any = false;
     for (int e = 0; e < min(epb, a.E - env0); ++e) any = any || (tb.doneflag[e] != 0);
     if constexpr (LOOP) {
       if (active) {
-        cy->in.sg = (tagged && a.runner_exits) ? 0 : sg;
+        cy->in.sg = (tagged && tc_phase_a(pv_fin).runner_exits) ? 0 : sg;
         cy->in.epoch = in.epoch + 1u;
       }
       cy->reload = __builtin_amdgcn_readfirstlane(any ? 1 : 0);  // the next trip reads the restored rows from memory
@@ -791,7 +801,12 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
     if (any) {  // block-uniform, rare (once per episode)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wavefront's stores are complete ...
       __syncthreads();                                  // ... before any wavefront rewrites the rows
-      tc_reset_finished(a, fz, tb, env0, epb);
+      if constexpr (LOOP) {  // (the reset table and the time steps: a view of its own, behind the guard)
+        const TcPhase pv_rst(a, fz);
+        tc_reset_finished(pv_rst.a, pv_rst.fz, tb, env0, epb, tid);
+      } else {
+        tc_reset_finished(a, fz, tb, env0, epb);
+      }
       if constexpr (LOOP) {
         // (Redundant TODAY: tc_fast_rollout's trip-end drain and barrier follow at once.  The pair is here so that the
         // restore is safe by itself -- the reload does not depend on the trip-end drain, which the steady-state trip no

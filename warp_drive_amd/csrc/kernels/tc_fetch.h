@@ -82,7 +82,10 @@ __device__ __forceinline__ void tc_fetch_slabs_straight(float *slab_acc, float *
   static_assert(64 * A % 4 == 0, "wavefront 1's rows start on a 16-byte boundary of the slab");
   const float *const pa = probs_acc + (size_t)env * (N * A), *const pt = probs_turn + (size_t)env * (N * A);
   // (an LDS pointer, not the low half of the generic one: that conversion carries a null check per use)
-  const unsigned la = (unsigned)(size_t)WD_LDS_PTR(slab_acc), lt = (unsigned)(size_t)WD_LDS_PTR(slab_turn);
+  unsigned la = (unsigned)(size_t)WD_LDS_PTR(slab_acc), lt = (unsigned)(size_t)WD_LDS_PTR(slab_turn);
+  // (opaque per trip: the LDS base of every group of pieces, the M0 of its loads, is then an s_add_i32 off these two; seen
+  // through, the bases are launch constants that the compiler holds in lanes of a vector register and reads back one by one)
+  asm volatile("" : "+s"(la), "+s"(lt));
   if (wave == 0) tc_fetch_slabs_wave<N, A, 0>(la, lt, pa, pt, lane);
   else tc_fetch_slabs_wave<N, A, 1>(la, lt, pa, pt, lane);
 }
@@ -186,8 +189,9 @@ __device__ __forceinline__ void tc_load_state(TcIn &in, const TcArgs &a, const T
 // ---- replica-independent tables: ascending tagger list, action tables.
 // Returns the number of taggers.  Ends WITHOUT a barrier: the caller's next barrier publishes them.
 __device__ __forceinline__ int tc_build_tables(const TcTables &tb, const TcArgs &a, int N, int n_acc, int n_turn,
-                                               bool tab_in_lds, const TcIn &in) {
-  const int tid = threadIdx.x, T_ = WD_TC_BLOCKDIM;
+                                               bool tab_in_lds, const TcIn &in, int tid_in = threadIdx.x) {
+  // (tid_in: the multi-tick entry passes its per-trip opaque copy of the thread index, see tc_reset_finished)
+  const int tid = tid_in, T_ = WD_TC_BLOCKDIM;
   const int my_type = in.type;
   if (tab_in_lds) {  // (entries loaded up front, before the probability slabs)
     if (tid < n_acc) tb.acc_tab[tid] = in.tab_acc;

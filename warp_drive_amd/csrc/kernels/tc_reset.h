@@ -12,8 +12,10 @@ namespace {
 // clears it.  Must be entered by the whole block after a barrier that follows every store of the
 // tick to these rows (the caller drains its own stores first).
 __device__ __forceinline__ void tc_reset_finished(const TcArgs &a, const TcFuse &fz, const TcTables &tb, int env0,
-                                                  int epb) {
-  const int tid = threadIdx.x, T_ = WD_TC_BLOCKDIM;
+                                                  int epb, int tid_in = threadIdx.x) {
+  // (tid_in: the multi-tick entry passes the per-trip opaque copy of the thread index -- from threadIdx.x itself the masks
+  // `tid == 0` and `tid < row_elems` are launch constants that the compiler computes in the prologue and parks)
+  const int tid = tid_in, T_ = WD_TC_BLOCKDIM;
   const int envs_here = min(epb, a.E - env0);
   for (int e = 0; e < envs_here; ++e) {
     if (tb.doneflag[e] == 0) continue;  // block-uniform

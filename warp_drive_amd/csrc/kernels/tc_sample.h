@@ -3,6 +3,7 @@
 // and the kernel entries); split by phase in round 6 with every shipped code object byte-identical before / after.
 #pragma once
 #include "wd_common.h"
+#include "tc_kernarg.h"
 #include "tc_fetch.h"
 
 namespace {
@@ -56,17 +57,25 @@ __device__ __forceinline__ int2 tc_sample_heads(const TcArgs &a, const TcFuse &f
 // SA: the size of both heads as a constant (n_acc == n_turn == SA, set by the entry): SA entries read and scanned per
 // head, not WD_SLAB_CH of which the last are masked off.
 template <int SA>
-__device__ __forceinline__ int2 tc_sample_heads_carried(const TcFuse &fz, uint32_t epoch, uint32_t k0, uint32_t k1,
+__device__ __forceinline__ int2 tc_sample_heads_carried(const TcArgs &a, const TcFuse &fz_, uint32_t epoch, uint32_t k0, uint32_t k1,
                                                         bool active, int gi, int li, const float *slab_acc,
                                                         const float *slab_turn, int n_acc, int n_turn) {
   uint32_t e = epoch;
   asm volatile("" : "+v"(e));  // (opaque, ordered after the slab issue: the rounds are not hoisted in front of it ...)
-  wd_u4 rnd = wd_philox4x32_10(wd_u4{(uint32_t)gi, e, (uint32_t)fz.stream_tag, 3u}, k0, k1);  // (every lane: no branch)
+  // (the key too, per trip: seen through, its ten round keys -- and the first round's products, which depend on nothing
+  // else -- are worked out once per launch, 17 values that only fit lanes of a vector register and come back by
+  // v_readlane_b32 on every trip; from an opaque key they are ten pairs of s_add_i32 on the scalar unit)
+  uint32_t tag = (uint32_t)fz_.stream_tag;  // (and the stream tag: its first-round product is such a value too)
+  asm volatile("" : "+s"(k0), "+s"(k1), "+s"(tag));
+  wd_u4 rnd = wd_philox4x32_10(wd_u4{(uint32_t)gi, e, tag, 3u}, k0, k1);  // (every lane: no branch)
   asm volatile("" : "+v"(rnd.x), "+v"(rnd.y));  // (... and not sunk behind the wait)
   // every global_load_lds of this wavefront has landed once its vmcnt drains; the rows a lane reads were all fetched by
   // its own wavefront
   __builtin_amdgcn_s_waitcnt(WD_WAIT_VMCNT0);
   __builtin_amdgcn_wave_barrier();
+  // where the actions and the epoch word go: a view of the kernel arguments taken behind the wait (tc_kernarg.h); its
+  // scalar loads return under the two scans
+  const TcFuse fz = TcPhase(a, fz_).fz;
   int2 sampled = make_int2(0, 0);
   if (active) {
     sampled.x = wd_slab_sample<SA>(slab_acc + (size_t)li * SA, wd_u01_open_closed(rnd.x));
