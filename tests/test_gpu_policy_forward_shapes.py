@@ -238,9 +238,12 @@ def test_plain_forward_entry_vs_float64(H, kt1, arithmetic):
 # --------------------------------------------------------------------------------------------------------------------
 #   B. the Act entries: actions drawn in the epilogue, batch rows, stored activations
 # --------------------------------------------------------------------------------------------------------------------
-def _act_launch(H, F, heads, arithmetic, E, N, id_sets, seed, T=3, stored=True, check_untouched=True):
+def _act_launch(H, F, heads, arithmetic, E, N, id_sets, seed, T=3, stored=True, check_untouched=True, only=None):
     """one HipPolicyMlpAct* launch of FusedRolloutTick on synthetic tensors: one policy per id set (all of one network
-    shape, different weights); every replica's batch row = T - 1.  Returns what the launch wrote and its inputs."""
+    shape, different weights); every replica's batch row = T - 1.  Returns what the launch wrote and its inputs.
+    only = "obs" / "act" / "out": that batch tensor alone has T rows (all of them the sentinel) and is written; every
+    other batch tensor has ONE row and reaches the launch as a null pointer, which the kernel skips -- so T can be what
+    takes a narrow tensor past 2^32 elements without 256-wide activations of the same T."""
     from warp_drive_amd.training.policy_kernel import FusedPolicyForward, FusedRolloutTick
 
     dev = torch.device("cuda:0")
@@ -264,28 +267,34 @@ def _act_launch(H, F, heads, arithmetic, E, N, id_sets, seed, T=3, stored=True, 
     batch_row = torch.full((E,), T - 1, dtype=torch.int64, device=dev)
     ns = [len(ids) for ids in id_sets]
     W = sum(heads) + 1
+    rows = lambda kind: T if only in (None, kind) else 1  # noqa: E731
+
     def alloc(shape, fill, **kw):
-        if check_untouched:
+        if check_untouched or only is not None:
             return torch.full(shape, fill, **kw)
         t = torch.empty(shape, **kw)  # (huge: only rows 0 and T - 2 get the sentinel)
         t[0].fill_(fill)
         t[T - 2].fill_(fill)
         return t
 
-    obs_b = [alloc((T, E, n, F), -7.0, device=dev) for n in ns]
-    act_b = [alloc((T, E, n, 2), -9, dtype=torch.int32, device=dev) for n in ns]
-    rew_b = [torch.zeros((T, E, n), device=dev) for n in ns]
-    done_b = torch.zeros((T, E), dtype=torch.int32, device=dev)
+    obs_b = [alloc((rows("obs"), E, n, F), -7.0, device=dev) for n in ns]
+    act_b = [alloc((rows("act"), E, n, 2), -9, dtype=torch.int32, device=dev) for n in ns]
+    rew_b = [torch.zeros((rows(None), E, n), device=dev) for n in ns]
+    done_b = torch.zeros((rows(None), E), dtype=torch.int32, device=dev)
     ep_r, ep_s, ep_c = [torch.zeros((E, n), device=dev) for n in ns], [torch.zeros(E, device=dev) for _ in ns], torch.zeros(E, device=dev)
     st = None
     if bx3 and stored:
-        st = [tuple(alloc((T, E, n, c), -7.0, device=dev) for c in (H, H, W)) for n in ns]
+        st = [tuple(alloc((rows(kind), E, n, c), -7.0, device=dev) for kind, c in (("h1", H), ("h2", H), ("out", W))) for n in ns]
     probs = [torch.full((E, N, a), -7.0, device=dev) for a in heads]
     ids_t = [torch.tensor(ids, dtype=torch.int32, device=dev) for ids in id_sets]
     tick = FusedRolloutTick(_fm(), forwards, ids_t, obs, actions, rewards, done, rng_state, stream_tag, batch_row,
                             obs_b, act_b, rew_b, done_b, ep_r, ep_s, ep_c, stored=st, probs=probs)
     name = f"HipPolicyMlpAct{'Bx3' if bx3 else ''}_{H}x{H}_k{(F + 31) // 32}"
     assert tick.fwd_name == name
+    if only is not None:
+        short = [t for t in obs_b + act_b + [x for s in st or [] for x in s] if t.shape[0] != T]
+        assert len(short) == len(ns) * (4 if st else 1)
+        tick.fwd_args = [np.uint64(0) if any(a is t for t in short) else a for a in tick.fwd_args]
     before = _launches(name)
     tick.forward()
     torch.cuda.synchronize()
@@ -424,6 +433,72 @@ def test_act_stores_activations_beyond_two_to_the_32_elements():
     assert res.pop("untouched"), "a row other than T - 1 was written"
     assert res.pop("rows"), "batch copy of the rows / actions"
     print("HipPolicyMlpActBx3_256x256_k3 at element offset > 2^32: err / err_f32",
+          {k: f"{e / e32:.2f}" if e32 else f"{e:.1e} / 0" for k, (e, e32, _) in res.items()})
+    for k, (e, e32, scale) in res.items():
+        assert _within_bound(e, e32, scale), (k, e, e32, scale)
+
+
+def _equals_everywhere(t, fill):
+    """every element of t == fill, in pieces: no temporary the size of t"""
+    flat, bad = t.reshape(-1), torch.zeros((), dtype=torch.int64, device=t.device)
+    for a in range(0, flat.numel(), 1 << 27):
+        bad += (flat[a:a + (1 << 27)] != fill).sum()
+    return int(bad) == 0
+
+
+def _one_store_past(kind, boundary, H, F, heads, E, N):
+    """one HipPolicyMlpActBx3 launch that writes ONLY the batch tensor `kind`, at the row that holds element `boundary`;
+    scalars and booleans leave this function, nothing of what it allocates"""
+    width = {"obs": F, "out": sum(heads) + 1, "act": 2}[kind]
+    T = boundary // (E * N * width) + 1
+    assert (T - 1) * E * N * width <= boundary < T * E * N * width
+    r = _act_launch(H, F, heads, "bf16x3", E, N, [list(range(N))], seed=5, T=T, check_untouched=False, only=kind)
+    t = {"obs": r["obs_b"][0], "act": r["act_b"][0], "out": r["stored"][0][2]}[kind]
+    assert t.shape[0] == T and t.numel() > boundary
+    res = {"bytes": t.numel() * 4, "untouched": _equals_everywhere(t[:T - 1], -9 if kind == "act" else -7.0)}
+    if kind == "obs":
+        res["row"] = torch.equal(t[T - 1], r["obs"])
+    elif kind == "act":
+        a = r["actions"]
+        res["row"] = torch.equal(t[T - 1], a) and bool((a >= 0).all()) and bool((a < torch.tensor(heads, device=a.device)).all())
+    else:
+        want, f32 = _reference(r["models"][0], r["obs"], heads)
+        for (s, _), z64, z32 in zip(_heads_of(want["out"], heads), want["shifted"], f32["shifted"]):
+            res[f"out[{s}:{s + z64.shape[-1]}]"] = _errors(t[T - 1][..., s:s + z64.shape[-1]], z64, z32)
+        res["value"] = _errors(t[T - 1][..., sum(heads)], want["values"], f32["values"])
+    return res
+
+
+@pytest.mark.parametrize("boundary", (31, 32))
+@pytest.mark.parametrize("kind", ("obs", "out", "act"))
+def test_act_stores_batch_rows_beyond_two_to_the_31_and_32_elements(kind, boundary):
+    """The trainer's observation batch [T, E, n, 71], stored outputs [T, E, n, 43] and action batch [T, E, n, 2] pass 2^31
+    elements at configs[2] (3.6e9, 2.2e9; the action batch stays below there, and is taken past both boundaries here because
+    17.2 GB fit): E x N = 8 x 100 rows, T such that row T - 1 HOLDS element 2^31 / 2^32 of the one tensor the launch
+    writes (8.6 / 17.2 GB); a store whose offset wrapped lands in the rows before it, which must all keep the sentinel"""
+    _fm()
+    H, F, heads, E, N = 256, 71, [21, 21], 8, 100
+    need = 4 * (2 ** boundary) + 3 * 2 ** 30
+    free, _ = torch.cuda.mem_get_info()
+    if free < need:
+        pytest.skip(f"needs {need / 2 ** 30:.0f} GB of free device memory, {free / 2 ** 30:.1f} GB free")
+    torch.cuda.synchronize()
+    reserved = torch.cuda.memory_reserved()
+    res, failure = None, None
+    try:
+        res = _one_store_past(kind, 2 ** boundary, H, F, heads, E, N)
+    except Exception as err:  # noqa: BLE001 -- only its text is kept: its traceback would hold the frames and their tensors
+        failure = f"{type(err).__name__}: {err}"
+    gc.collect()
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    assert torch.cuda.memory_reserved() <= reserved + 2 ** 28, (torch.cuda.memory_reserved(), reserved)
+    assert failure is None, failure
+    assert res.pop("bytes") > 4 * 2 ** boundary
+    assert res.pop("untouched"), "a row other than T - 1 was written"
+    if kind != "out":
+        assert res.pop("row"), "batch copy of the rows / actions"
+    print(f"HipPolicyMlpActBx3_256x256_k3 {kind} batch at element offset 2^{boundary}: err / err_f32",
           {k: f"{e / e32:.2f}" if e32 else f"{e:.1e} / 0" for k, (e, e32, _) in res.items()})
     for k, (e, e32, scale) in res.items():
         assert _within_bound(e, e32, scale), (k, e, e32, scale)
