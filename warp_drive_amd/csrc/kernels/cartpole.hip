@@ -179,10 +179,11 @@ __device__ __forceinline__ void cp_tick_impl(float *cp_weights,
     };
     if (lazy) {  // (uniform) every tick but the last: the branch-free body
       // cp_euler<true>'s preconditions, checked ONCE per launch and wavefront: the division shortcut is proved for this total
-      // mass (host flag), a running replica's angle stays inside 0.75 (threshold), and so do the angles the wavefront starts
-      // from and restarts from.  A middle tick then only ever sees the restart state or a state that did not terminate.
+      // mass in one binade (host flag) and the masses carry that proof over the whole dividend window (cp_fast_masses_ok), a
+      // running replica's angle stays inside 0.75 (threshold), and so do the angles the wavefront starts from and
+      // restarts from.  A middle tick then only ever sees the restart state or a state that did not terminate.
       const bool small = (p.theta_threshold_radians <= 0.75f) && (fabsf(s.z) <= 0.75f) && (fabsf(s_restart.z) <= 0.75f);
-      const bool mass_ok = (p.masspole >= 0x1.0p-60f) && (p.masspole <= 0x1.0p60f);
+      const bool mass_ok = cp_fast_masses_ok(p.masspole, p.total_mass);
       const bool fast = (invariant_divide_ok != 0) && mass_ok && (__ballot(!small) == 0ull);  // (wave-uniform)
       if (fast) for (int k = 0; k < ticks - 1; ++k) tick(k, CpTrueFast{}, false);
       else for (int k = 0; k < ticks - 1; ++k) tick(k, CpTrue{}, false);
@@ -270,9 +271,11 @@ __device__ __forceinline__ void cp_evaluate_impl(float *cp_weights, const float4
 extern "C" {
 
 // Exhaustive proof for ONE divisor c (the env's total mass) that cp_div_invariant(x, c, RN(1 / c)) == x / c for every
-// float32 x of one binade, both signs (2^24 values; all other normal x follow by scaling): `ok` (preset to 1 by the host)
-// is cleared on the first mismatch (a test hands it a reciprocal that is one ulp off: it must notice).  Run once per env
-// object (envs/cartpole.py::invariant_divide_ok).
+// float32 x of one binade, both signs (2^24 values).  Every other x follows by scaling ONLY while x / c stays a normal
+// float32: the proof says nothing about a quotient that overflows or is subnormal, so the tick kernels use the form only
+// with this proof AND masses that keep the quotients of their dividend window normal (cartpole_common.h::
+// cp_fast_masses_ok).  `ok` (preset to 1 by the host) is cleared on the first mismatch (a test hands it a reciprocal that
+// is one ulp off: it must notice).  Run once per total mass (envs/cartpole.py::invariant_divide_ok).
 __global__ void HipCartPoleVerifyInvariantDivide(float c, float y, int *ok) {  // y: RN(1 / c), formed by the host
   if (y != 1.0f / c && threadIdx.x == 0 && blockIdx.x == 0) *ok = 0;  // (not what the tick kernels use: 1.0f / total_mass)
   // bits 0 .. 22: the significand; bit 23: a second binade (x 2^40: the scaling argument, spot-checked); bit 24: the sign

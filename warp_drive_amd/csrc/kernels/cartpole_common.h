@@ -17,15 +17,33 @@ struct CpPhysics {
 
 // x / c for a divisor that is the same on every tick of every replica (the total mass): q = RN(x * y), r = x - c * q
 // (exact: one FMA), RN(q + r * y), y = RN(1 / c) -- three instructions instead of the ~10 of the correctly rounded division.
-// Equal to RN(x / c) for ALL normal x away from underflow / overflow iff it is for the 2^24 values of one binade and both signs
-// (scaling x by a power of two scales q, r and the result exactly): HipCartPoleVerifyInvariantDivide checks exactly that for
-// the env's own c, exhaustively, once per env object (no float32 divisor tried so far fails it; the proof is per divisor all the
-// same: the classical guarantee has exceptions, and an exhaustive check costs one launch); the launch
-// uses this form only with that proof in hand, and only for dividends inside [2^-90, 2^90] (cp_euler<true>).
+// WHAT IS PROVED, per divisor: HipCartPoleVerifyInvariantDivide compares this form with `/` for the 2^24 significands of the
+// binade [1, 2) (and of [2^40, 2^41)), both signs, once per total mass (no float32 divisor tried so far fails it; the
+// classical guarantee has exceptions, and an exhaustive check costs one launch).  Scaling x by a power of two scales q, r
+// and the result exactly AS LONG AS q AND THE QUOTIENT STAY NORMAL float32 -- then, and only then, one binade speaks for
+// the others.  Where the quotient overflows the form returns NaN (q = inf, r = -inf, inf - inf) and where it is subnormal
+// it is off by one place (q is rounded at the subnormal quantum and the correction vanishes below it):
+// tests/cartpole_divide_cases.py lists divisors that pass the proof and fail there.
+// WHERE IT IS USED: cp_euler<true>, for dividends with |x| in [2^-90, 2^90) (cp_div_in_window) and a total mass in
+// [2^-32, 2^32] (cp_fast_masses_ok): the quotient's magnitude then lies in [2^-122, 2^122), q within a place of it, and the
+// scaling argument holds for every such pair.
 __device__ __forceinline__ float cp_div_invariant(float x, float c, float y) {
   const float q = x * y;
   const float r = __builtin_fmaf(-c, q, x);
   return __builtin_fmaf(r, y, q);
+}
+
+// the dividends cp_euler<true> hands to cp_div_invariant: |x| inside [2^-90, 2^90) by its exponent field (zero, subnormal,
+// infinite, NaN: outside)
+__device__ __forceinline__ bool cp_div_in_window(float x) {
+  return ((__float_as_uint(x) & 0x7fffffffu) - 0x12800000u) < 0x5a000000u;
+}
+
+// the masses a launch may run cp_euler<true> with (part of the `fast` predicates of cartpole.hip and cartpole_pool.hip):
+// the pole's mass keeps the second dividend, masspole * cos^2, inside the window; the total mass keeps every quotient of
+// a window dividend normal (cp_div_invariant)
+__device__ __forceinline__ bool cp_fast_masses_ok(float masspole, float total_mass) {
+  return (masspole >= 0x1.0p-60f) && (masspole <= 0x1.0p60f) && (total_mass >= 0x1.0p-32f) && (total_mass <= 0x1.0p32f);
 }
 
 // numpy's float32 sin / cos kernel (wd_np_sincosf) for |x| <= 0.75: the quadrant is 0 -- RN(x * 2/pi + magic) - magic = 0
@@ -52,7 +70,7 @@ __device__ __forceinline__ void cp_sincos_small(float x, float &sin_out, float &
 // FAST (compile time; the middle ticks of a recorded launch whose PRECONDITIONS the kernel checked once, cp_tick_impl):
 // |theta| <= 0.75 on entry -> the quadrant-free sin / cos; the two float32 divisions by the total mass in three
 // instructions each.  Bit-identical to the general form: the one data-dependent condition left -- a dividend outside the
-// range the division shortcut was proved for (the force term's dividend; the other one is the pole's mass times cos^2) --
+// window the division shortcut is used in (the force term's dividend; the other one is the pole's mass times cos^2) --
 // redoes both divisions in a cold block behind a branch that is never taken in practice (the dividends are ~10 and ~0.1).
 template <bool FAST = false>
 __device__ __forceinline__ bool cp_euler(float4 &s, int action, const CpPhysics &p) {
@@ -67,9 +85,8 @@ __device__ __forceinline__ bool cp_euler(float4 &s, int action, const CpPhysics 
   if (FAST) {
     temp = cp_div_invariant(temp_num, p.total_mass, p.inv_total_mass);
     frac = cp_div_invariant(frac_num, p.total_mass, p.inv_total_mass);
-    // |temp_num| inside [2^-90, 2^90) by its exponent field (zero, subnormal, infinite, NaN: outside); frac_num is the pole's
-    // mass (inside [2^-60, 2^60]: a precondition of the launch) times cos^2 >= 0.53: always inside
-    const bool in_range = ((__float_as_uint(temp_num) & 0x7fffffffu) - 0x12800000u) < 0x5a000000u;
+    // frac_num is the pole's mass (inside [2^-60, 2^60]: a precondition of the launch) times cos^2 >= 0.53: always inside
+    const bool in_range = cp_div_in_window(temp_num);
     if (__builtin_expect(__ballot(!in_range) != 0ull, 0)) {
       temp = temp_num / p.total_mass;
       frac = frac_num / p.total_mass;

@@ -80,7 +80,7 @@ __device__ __forceinline__ void cp_pool_rollout(float *lds,
   const uint32_t k0 = rng_state[0], k1 = rng_state[1];
   const uint32_t pk0 = pa.pool_rng[0], pk1 = pa.pool_rng[1];
   const bool batch = obs_batch != nullptr;
-  const bool mass_ok = (p.masspole >= 0x1.0p-60f) && (p.masspole <= 0x1.0p60f);
+  const bool mass_ok = cp_fast_masses_ok(p.masspole, p.total_mass);
   const bool launch_fast = (invariant_divide_ok != 0) && mass_ok && (p.theta_threshold_radians <= 0.75f) && pool_small;
   for (int env = blockIdx.x * blockDim.x + threadIdx.x; env < n_envs; env += gridDim.x * blockDim.x) {
     int t = env_timestep_arr[env];
@@ -162,7 +162,7 @@ __device__ __forceinline__ void cp_pool_rollout(float *lds,
         pool_epoch += fin ? 1u : 0u;
       }
     };
-    // cp_euler<true>'s preconditions: the launch's (division proof, pole mass, threshold, every pool row) and the angles
+    // cp_euler<true>'s preconditions: the launch's (division proof, both masses, threshold, every pool row) and the angles
     // this wavefront starts from; a tick then only ever sees a pool row or a state that did not terminate
     const bool fast = launch_fast && (__ballot(!(fabsf(s.z) <= 0.75f)) == 0ull);  // (wave-uniform)
     if (fast) for (int k = 0; k < ticks; ++k) tick(k, CpPoolFast{});

@@ -91,6 +91,37 @@ __global__ void wd_write_probe(float *out, long slice_stride, int floats_per_blo
   }
 }
 
+// ------------------------------------------------------------- Cartpole's division shortcut, counted
+// tests/test_gpu_cartpole_divide.py: for every float32 magnitude pattern first_pattern .. first_pattern + n_patterns - 1
+// (below 2^31) and its negation, the shipping window test (cp_div_in_window) and, inside the window, the shipping
+// cp_div_invariant(x, c, y) against x / c.  out[0] += dividends inside the window, out[1] += those whose two results differ
+// (NaN against NaN is equal, NaN against infinity is not).  Independent of HipCartPoleVerifyInvariantDivide: no binade is
+// chosen here, the caller sweeps what it likes (the whole window is 0x5a000000 patterns).
+__global__ void wd_test_cartpole_divide(float c, float y, uint32_t first_pattern, uint32_t n_patterns,
+                                        unsigned long long *out) {
+  unsigned long long inside = 0ull, differ = 0ull;
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n_patterns; i += stride) {
+    const uint32_t bits = first_pattern + (uint32_t)i;
+#pragma unroll
+    for (int sgn = 0; sgn < 2; ++sgn) {
+      const float x = __uint_as_float(bits | (sgn ? 0x80000000u : 0u));
+      if (!cp_div_in_window(x)) continue;
+      const float want = x / c, got = cp_div_invariant(x, c, y);
+      inside += 1ull;
+      if (__float_as_uint(want) != __float_as_uint(got) && !(want != want && got != got)) differ += 1ull;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    inside += __shfl_down(inside, off);
+    differ += __shfl_down(differ, off);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicAdd(out, inside);
+    atomicAdd(out + 1, differ);
+  }
+}
+
 // ------------------------------------------------------------- math self-test hook
 // Evaluates the device restatements of numpy's float32 routines so the GPU parity
 // suite can compare them bit-for-bit with numpy on the host (tests/test_gpu_math.py).

@@ -236,6 +236,8 @@ class CUDAClassicControlCartPoleEnv(SingleAgentDeviceEnv, CUDAEnvironmentContext
         instead of reading `probabilities`.  An env with a reset pool: `_pool_tick_launch` (the ..._P entries)."""
         assert env_range is None and len(probabilities) == 1
         fm, dm = self.cuda_function_manager, self.cuda_data_manager
+        if int(self.ticks_per_launch) < 1:   # (cp_tick_impl's last tick runs whatever `ticks` says: tick -1 of a launch of none)
+            raise UnsupportedRolloutShape(f"ticks_per_launch must be at least 1, not {self.ticks_per_launch}")
         if self._has_pool():
             return self._pool_tick_launch(sampler, probabilities, resetter, batch, policy)
         name = self._entry("Tick")
@@ -298,18 +300,27 @@ class CUDAClassicControlCartPoleEnv(SingleAgentDeviceEnv, CUDAEnvironmentContext
         return fm.get_function(name), args, block, grid, self.pool_rollout_lds_bytes(width, n_act, n_pool, staged)
 
     def invariant_divide_ok(self):
-        """1 when the device PROVED, exhaustively, that the tick kernels' three-instruction division by this env's total mass
-        (csrc/kernels/cartpole.hip::cp_div_invariant) equals the correctly rounded division for every float32 dividend of two
-        binades, both signs -- one launch of HipCartPoleVerifyInvariantDivide, once per env object; 0: the kernels divide.
-        (True for the classic 1.1 and for every other mass tried so far.)"""
-        if getattr(self, "_inv_div_ok", None) is None:
+        """1 when the device found the tick kernels' three-instruction division by this env's total mass
+        (csrc/kernels/cartpole_common.h::cp_div_invariant) equal to the correctly rounded division for every float32
+        dividend of two binades, [1, 2) and [2^40, 2^41), both signs -- one launch of HipCartPoleVerifyInvariantDivide per
+        total mass (the verdicts are kept by the mass's float32 bits: `physics` may be replaced); 0: the kernels divide.
+        That is a proof for the other binades only where the quotient stays a normal float32, which the flag does not
+        say: the kernels take the fast ticks with this flag AND masses that keep it so for every dividend they hand to
+        the shortcut (cp_fast_masses_ok).  (1 for the classic 1.1 and for every other mass tried so far.)"""
+        if getattr(self, "_inv_div_ok", None) is not None:   # a verdict set from outside: no launch, whatever the mass
+            return self._inv_div_ok
+        total_mass = np.float32(self.physics.masspole + self.physics.masscart)
+        verdicts = self.__dict__.setdefault("_inv_div_verdicts", {})
+        key = total_mass.tobytes()
+        if key not in verdicts:
             import torch
 
             fm = self.cuda_function_manager
             fm.initialize_functions(["HipCartPoleVerifyInvariantDivide"])
-            ok = torch.ones(1, dtype=torch.int32, device=torch.device("cuda", torch.cuda.current_device()))
-            total_mass = np.float32(self.physics.masspole + self.physics.masscart)
-            fm.get_function("HipCartPoleVerifyInvariantDivide")(total_mass, np.float32(1.0) / total_mass, ok,
+            ok = torch.ones(1, dtype=torch.int32, device=torch.device("cuda", int(fm._device_id)))
+            with np.errstate(all="ignore"):   # (a reciprocal may be subnormal or overflow: the kernel is told what the host formed)
+                recip = np.float32(1.0) / total_mass
+            fm.get_function("HipCartPoleVerifyInvariantDivide")(total_mass, recip, ok,
                                                                 block=(256, 1, 1), grid=(4096, 1), shared=0)
-            self._inv_div_ok = int(ok.item())
-        return self._inv_div_ok
+            verdicts[key] = int(ok.item())
+        return verdicts[key]
