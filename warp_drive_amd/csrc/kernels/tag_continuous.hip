@@ -185,7 +185,9 @@ __global__ void HipTagContinuousVerifyInvariantDivide(float kMaxSpeed, float kGr
 static_assert(WD_TC_SHAPE_N <= 128, "the shape-specialised entries use the 7-bit-id search of replicas up to 128 agents");
 #if defined(WD_TC_ROLLOUT)
 // -DWD_TC_ROLLOUT: a unit of its own with ONE entry, `HipTagContinuousRollout_K<k>_N<n>A<a>`: the Tick entry's arguments
-// plus the number of ticks; every block takes its replica through that many ticks (tc_fast_rollout, tc_fast.h).  A separate
+// plus the number of ticks; every block takes its replica through that many ticks (tc_fast_rollout, tc_fast.h).  After the
+// launch memory holds what that many launches of the Tick entry leave; inside it a trip stores every output of its tick, but
+// the state its threads carry in registers only on the last trip and on the trip an episode ends on.  A separate
 // object, so that the one-tick entries below (and the records keyed to their object) never move with it.
 static_assert(WD_TC_SHAPE_N > 64 && WD_TC_SHAPE_THREADS == 128, "one replica per 128-thread block");
 __global__ void __launch_bounds__(512, 4) WD_TC_SHAPE_NAME(HipTagContinuousRollout_K)(WD_TC_PARAMS WD_TC_FUSE_PARAMS

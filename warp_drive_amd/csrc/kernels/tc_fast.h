@@ -14,6 +14,29 @@
 
 namespace {
 
+// What the multi-tick entry keeps out of memory until a CLOSING trip (the last of a launch, or the one a replica's episode
+// ends on): position, speed, heading, acceleration, the edge penalty, the RNG epoch word; from lane 0 the time step and the
+// runner count.  `s` is the thread's carry AFTER the move (TcCarry::in), `epoch` the word the next trip starts from.
+// One replica per block (`env0`, SN agents): every array is addressed off the replica's row on the scalar side, and the
+// agent's place in it is ONE 32-bit byte offset shared by all seven (the form of tc_store_id_row, tc_rows.h).
+template <int SN>
+__device__ __forceinline__ void tc_store_carried(const TcArgs &a, const TcFuse &fz, const TcIn &s, float edge_pen,
+                                                 uint32_t epoch, int env0, int ag, int nrun) {
+  const long row0 = (long)env0 * SN;
+  const unsigned off = 4u * (unsigned)ag;
+  *(float *)((char *)(a.loc_x + row0) + off) = s.x;
+  *(float *)((char *)(a.loc_y + row0) + off) = s.y;
+  *(float *)((char *)(a.speed + row0) + off) = s.speed;
+  *(float *)((char *)(a.direction + row0) + off) = s.dir;
+  *(float *)((char *)(a.acceleration + row0) + off) = s.acc;
+  *(float *)((char *)(a.edge_pen_arr + row0) + off) = edge_pen;
+  *(uint32_t *)((char *)(fz.rng_state + WD_RNG_HEADER + row0) + off) = epoch;
+  if (ag == 0) {
+    a.timestep[env0] = s.tstep;
+    a.num_runners[env0] = nrun;
+  }
+}
+
 // EXACTK: K == KMAX, known at compile time (row offsets become immediates, the K-dependent selects fold away)
 // LOOP: called as the body of the multi-tick entry (tc_fast_rollout below) for trip `tick` of a launch; the replica-independent tables
 // are built on trip 0 and stay (`n_taggers` carries their length); the thread's own state arrives in `cy` and leaves in it
@@ -88,7 +111,7 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   TcIn in;
   bool reloaded = false;  // LOOP: block-uniform
   if constexpr (LOOP) {
-    // The steady-state trip loads nothing but the slabs: the state is what this thread stored on the trip before.  Trip 0
+    // The steady-state trip loads nothing but the slabs: the state is what this thread computed on the trip before.  Trip 0
     // of a launch and the trip after a restore read it from memory (all of it: which arrays a restore rewrites is the
     // host's choice), and wait for it, BEFORE the slabs are issued.
     in = cy->in;
@@ -150,7 +173,7 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   WD_TC_PROBE(2);
   __syncthreads();  // tables are published; every wavefront is done with the slabs
   WD_TC_PROBE(3);
-  // (LOOP: the state arrays the move stores to, from a view taken behind the barrier)
+  // (LOOP: obs_rows_cleared, from a view taken behind the barrier; the state arrays are stored on a closing trip only)
   typename TcPhaseArgs<LOOP>::type pv_move = tc_phase<LOOP>(a, fz);
   // packed index of this lane's agent among the agents in the game, and their number
   int my_c = ag, n_live = N;
@@ -194,9 +217,9 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
   const int sg = in.sg;
   const bool is_runner = active && (in.type == 0) && (sg != 0);  // member of self.runners
   if (active) {
-    const TcMoved m = tc_move<LOOP>(tc_phase_a(pv_move), tb, in, sampled, gi, tab_in_lds, LOOP ? cy : nullptr, LOOP ? lc : nullptr);
+    const TcMoved m = tc_move<LOOP, !LOOP>(tc_phase_a(pv_move), tb, in, sampled, gi, tab_in_lds, LOOP ? cy : nullptr, LOOP ? lc : nullptr);
     edge_pen = m.edge_pen; my_x = m.x; my_y = m.y;
-    if constexpr (LOOP) {  // what the next trip would read back
+    if constexpr (LOOP) {  // what the next trip would read back, and what a closing trip stores
       cy->in.x = m.x; cy->in.y = m.y;
       cy->in.cleared = (sg == 0) ? 1 : 0;
     }
@@ -248,7 +271,7 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
     l.tagcnt[li] = 0;
     if (ag == 0) {
       const int t = in.tstep + 1;  // :800
-      tc_phase_a(pv_move).timestep[env] = t;
+      if constexpr (!LOOP) tc_phase_a(pv_move).timestep[env] = t;  // (LOOP: on a closing trip, from the carry)
       tb.tstep[el] = t;
       // float(t) / episode_length, :474 (LOOP: by the reciprocal, proved for t = 1 .. T by the same verifier)
       if constexpr (LOOP) tb.tfrac[el] = (float)tc_div_const((double)t, (double)a.T, lc->r_T);
@@ -786,7 +809,26 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
 
   // ------------------------------------------------------------ rewards / done
   typename TcPhaseArgs<LOOP>::type pv_fin = tc_phase<LOOP>(a, fz);  // (LOOP: rewards, still_in_the_game, num_runners, done, behind the barrier)
-  if (active) tc_finish_agent(tc_phase_a(pv_fin), tb, el, ag, gi, env, sg, is_runner, tagged, l.tagcnt[li], edge_pen, in.step_reward, FUSED);
+  if (active) tc_finish_agent(tc_phase_a(pv_fin), tb, el, ag, gi, env, sg, is_runner, tagged, l.tagcnt[li], edge_pen, in.step_reward, FUSED, !LOOP);
+  if constexpr (LOOP) {
+    // CLOSING TRIP: the last trip of the launch, or the trip the replica's episode ends on (the predicate of
+    // tc_finish_agent; tb.tstep and tb.nrun are final behind the barrier above, so it is block-uniform).  Nothing can read
+    // the carried state from memory before one -- the next trip overwrites it, the host cannot look inside a launch -- so
+    // only here does it go to memory: what the one-tick kernel stores on this trip.  In front of the `doneflag` barrier: the
+    // restore's drain and barrier separate these stores from tc_reset_finished, which may rewrite the same rows, and the
+    // trip after a restore (or the next launch) reloads every one of them.
+    // (both words read, no short circuit: one wait for the pair; their index is a zero the compiler cannot see through --
+    // a constant LDS address would be formed in front of the loop and parked in a lane; the launch's length comes from the
+    // phase's view, so that nothing of it stays in a register across the trip either)
+    int first = 0;
+    asm volatile("" : "+v"(first));
+    const int ended = ((tb.tstep[first] >= tc_phase_a(pv_fin).T) | (tb.nrun[first] == 0)) ? 1 : 0;
+    if ((tick + 1 == pv_fin.n_ticks) | (__builtin_amdgcn_readfirstlane(ended) != 0)) {
+      static_assert(!LOOP || SN > 0, "one replica of SN agents per block");
+      const TcPhase pv_close(a, fz);  // (a view of its own: cold)
+      if (active) tc_store_carried<SN>(pv_close.a, pv_close.fz, cy->in, edge_pen, in.epoch + 1u, env0, ag, tb.nrun[0]);
+    }
+  }
   if (FUSED) {
     __syncthreads();  // doneflag
     bool any = false;
@@ -823,10 +865,16 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
 // `ticks` ticks of the block's replicas in ONE launch (one replica per block; the fused, sampling tick).  The replicas of a
 // launch are independent, so nothing but the kernel boundary made replica r's tick t + 1 wait for replica s's tick t: here
 // every block runs on at its own pace and the blocks of a CU drift out of phase (one block's fetch and row flush under
-// another's search).  Every trip computes and STORES what the one-tick kernel stores, and fetches both slabs again (the
-// probabilities change every tick).  What a trip does not do is read back the state its own threads stored on the trip
-// before: sg, heading, acceleration, speed, position, RNG epoch, the cleared flag and the time step travel in registers
-// (TcCarry; the runner count stays in tb.nrun), the Philox key is read once per launch.  A steady-state trip is: done = 0,
+// another's search).  Every trip computes the whole tick, fetches both slabs again (the probabilities change every tick) and
+// STORES what a caller of a tick reads: observations, neighbour ids, sampled actions, rewards, done flags, and the
+// change-only still_in_the_game and obs_rows_cleared words.  What a trip does not do is read back the state its own threads
+// computed on the trip before: sg, heading, acceleration, speed, position, RNG epoch, the cleared flag and the time step
+// travel in registers (TcCarry; the runner count stays in tb.nrun), the Philox key is read once per launch.  Nor does it
+// store that state where nobody can read it: the five state arrays, the edge penalty, epoch + 1, the time step and the
+// runner count go to memory on CLOSING trips only -- the last trip of the launch and the trip the replica's episode ends on
+// (tc_store_carried, in the rewards phase), with the values the one-tick kernel stores on that trip.  Any other trip's
+// values would be overwritten by the next trip before the launch ends, and the host cannot look inside a launch; the trip
+// after a restore reloads all of it, arrays the reset table leaves out included.  A steady-state trip is: done = 0,
 // slab issue, Philox in the shadow of the fetch, slab wait, both inverse-CDF scans, move ... -- no other load, and no
 // store, LDS access or second vmcnt wait between the slab issue and the slab wait.  The state is read from memory on trip 0
 // of a launch (the host may have written anything in between) and on the trip after a restore (tc_reset_finished,
@@ -840,8 +888,8 @@ __device__ __forceinline__ int tc_fast_impl(const TcArgs &a, const TcFuse &fz, u
 //   * the probability slabs alias the work area: the next trip's global_load_lds may only go out once every wavefront
 //     is done with this trip's staging buffers and tables.
 // (Replacing the trip-end vmcnt(0) by the lgkmcnt(0) the LDS reuse needs was measured in round 21: correct -- every address
-// is stored by the same wavefront on every trip, same-wavefront stores to one address complete in program order, the
-// restore keeps its drains -- but no faster, docs/rounds/r21.md; the drain stays.)
+// is stored by the same wavefront on every trip it is stored on, same-wavefront stores to one address complete in program
+// order, the restore keeps its drains -- but no faster, docs/rounds/r21.md; the drain stays.)
 // No barrier across blocks, no communication between them.
 template <int KMAX, bool EXACTK, int IDB, int SN, int SA, int ST>
 __device__ __forceinline__ void tc_fast_rollout(const TcArgs &a, const TcFuse &fz, unsigned char *smem, int n_acc,

@@ -107,6 +107,7 @@ __device__ __forceinline__ TcKernargView tc_kernarg_view() {
 struct TcPhase {
   TcArgs a;
   TcFuse fz;
+  int n_ticks;  // the trips of this launch (read by the rewards phase alone: the last one is a closing trip, tc_fast.h)
   __device__ __forceinline__ TcPhase(const TcArgs &base, const TcFuse &fbase) {
     const TcKernargView k = tc_kernarg_view();
     {
@@ -119,6 +120,7 @@ struct TcPhase {
       this->a = a;
       this->fz = fz;
       (void)kNumAccelerationActions; (void)kNumTurnActions;
+      this->n_ticks = k->kNumTicks;
     }
     // what is cheap to keep in registers: the launch constants the arithmetic uses (and the sizes the entry folded to
     // constants).  `runner_exits` is NOT among them: kept, it lives as two 64-bit masks that do not fit either.

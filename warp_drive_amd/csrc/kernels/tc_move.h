@@ -9,7 +9,7 @@
 namespace {
 
 // ---- move: float32 kinematics exactly as numpy evaluates update_state (:339-401); stores the new
-// state, returns the post-move position, the edge penalty and the observation features.
+// state (unless STORE == false), returns the post-move position, the edge penalty and the observation features.
 // numpy's float32 remainder by 2 pi (npy_divmodf: fmodf, then the divisor's sign) for the only dividends a heading ever
 // produces -- an angle of [0, 2 pi) plus one turn: |a| < 4 pi.  fmodf is EXACT by definition, and for |a| < 2 b it is a or
 // a -+ b, the subtraction exact (Sterbenz: b <= |a| < 2 b): five branch-free instructions instead of the library's long
@@ -31,7 +31,9 @@ struct TcMoved {
 // `cy` (the multi-tick entry only): the stored heading, acceleration and speed also go to the thread's carry
 // CDIV (the multi-tick entry only, with `lc`): the five divisions by launch constants that end the move are products with
 // the reciprocals of `lc` plus one residual correction (tc_div_const, tc_divide.h)
-template <bool CDIV = false>
+// STORE == false (the multi-tick entry only): the six state stores are left to the caller, which makes them on a closing
+// trip alone (tc_store_carried, tc_fast.h) -- position and edge penalty leave in the result, the rest through `cy`
+template <bool CDIV = false, bool STORE = true>
 __device__ __forceinline__ TcMoved tc_move(const TcArgs &a, const TcTables &tb, const TcIn &in, int2 act, int gi,
                                            bool tab_in_lds, TcCarry *cy = nullptr, const TcLoopConsts *lc = nullptr) {
   const float two_pi = 6.2831854820251465f;            // float32(2*pi), :356
@@ -61,12 +63,14 @@ __device__ __forceinline__ TcMoved tc_move(const TcArgs &a, const TcTables &tb, 
   py = fminf(fmaxf(py, 0.0f), L);
   TcMoved m;
   m.edge_pen = a.edge_hit_penalty * (crossed ? 1.0f : 0.0f);                  // :394
-  a.loc_x[gi] = px;
-  a.loc_y[gi] = py;
-  a.speed[gi] = v;
-  a.direction[gi] = dir;
-  a.acceleration[gi] = acc;
-  a.edge_pen_arr[gi] = m.edge_pen;
+  if constexpr (STORE) {
+    a.loc_x[gi] = px;
+    a.loc_y[gi] = py;
+    a.speed[gi] = v;
+    a.direction[gi] = dir;
+    a.acceleration[gi] = acc;
+    a.edge_pen_arr[gi] = m.edge_pen;
+  }
   m.x = px;
   m.y = py;
   if (cy != nullptr) { cy->in.dir = dir; cy->in.acc = acc; cy->in.speed = v; }

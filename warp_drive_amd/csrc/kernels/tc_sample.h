@@ -53,7 +53,7 @@ __device__ __forceinline__ int2 tc_sample_heads(const TcArgs &a, const TcFuse &f
 // Multi-tick entry only (two slabs side by side, no tc_one_slab path: replicas of at most 128 agents, asserted at the
 // call site).  The caller has issued both slabs and NOTHING else since; between that and the wait there is only register work: the ten Philox rounds, on the epoch the thread carries
 // and the key the launch read once, run in the shadow of the fetch.  No load, no store (its acknowledgement would be
-// waited for in order with the slabs' data) and no LDS access lies in between.  The epoch word goes out with the actions.
+// waited for in order with the slabs' data) and no LDS access lies in between.  The actions go out behind the wait.
 // SA: the size of both heads as a constant (n_acc == n_turn == SA, set by the entry): SA entries read and scanned per
 // head, not WD_SLAB_CH of which the last are masked off.
 template <int SA>
@@ -73,7 +73,7 @@ __device__ __forceinline__ int2 tc_sample_heads_carried(const TcArgs &a, const T
   // its own wavefront
   __builtin_amdgcn_s_waitcnt(WD_WAIT_VMCNT0);
   __builtin_amdgcn_wave_barrier();
-  // where the actions and the epoch word go: a view of the kernel arguments taken behind the wait (tc_kernarg.h); its
+  // where the actions go: a view of the kernel arguments taken behind the wait (tc_kernarg.h); its
   // scalar loads return under the two scans
   const TcFuse fz = TcPhase(a, fz_).fz;
   int2 sampled = make_int2(0, 0);
@@ -85,7 +85,8 @@ __device__ __forceinline__ int2 tc_sample_heads_carried(const TcArgs &a, const T
     asm volatile("" : "+v"(turn_row));
     sampled.y = wd_slab_sample<SA>((const float *)((const char *)slab_acc + turn_row), wd_u01_open_closed(rnd.y));
     ((int2 *)fz.actions_out)[gi] = sampled;
-    fz.rng_state[WD_RNG_HEADER + gi] = epoch + 1u;
+    // (the epoch word is NOT stored here: the thread carries it, and memory gets epoch + 1 on a closing trip,
+    // tc_store_carried in tc_fast.h)
   }
   return sampled;
 }

@@ -70,9 +70,11 @@ __device__ __forceinline__ bool tc_find_tag(const TcArgs &a, const TcTables &tb,
 }
 
 // ---- rewards / done of one agent (:655-678, :880-883); call after the barrier that follows the tags
+// store_nrun == false (the multi-tick entry only): the runner count stays in tb.nrun and goes to memory on a closing trip
+// alone (tc_store_carried, tc_fast.h)
 __device__ __forceinline__ void tc_finish_agent(const TcArgs &a, const TcTables &tb, int el, int ag, int gi, int env,
                                                 int sg, bool is_runner, bool tagged, int tagcnt, float edge_pen,
-                                                float step_reward, bool fused) {
+                                                float step_reward, bool fused, bool store_nrun = true) {
   float rew = 0.0f;
   if (sg) { rew += edge_pen; rew += step_reward; }              // :655-658
   if (tagged) rew += a.tag_penalty;                             // :664
@@ -83,7 +85,7 @@ __device__ __forceinline__ void tc_finish_agent(const TcArgs &a, const TcTables 
   if (tagged && a.runner_exits) a.sig_arr[gi] = 0;              // :669
   if (ag == 0) {
     const int nr = tb.nrun[el];
-    a.num_runners[env] = nr;
+    if (store_nrun) a.num_runners[env] = nr;
     const bool fin = (tb.tstep[el] >= a.T || nr == 0);          // :880-883
     if (fin) a.done[env] = 1;
     if (fused) tb.doneflag[el] = fin ? 1 : 0;
