@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Trainer's A2C update on its two paths -- "framework" (framework GEMMs, FusedObjective, autograd, clip_grad_norm_,
-torch.optim.Adam, the repack) and "kernels" (`trainer.fused_update: "all"`: five launches,
-training/pg_update_kernels.py) -- in ONE process on the one-launch rollout, at seven shapes: Cartpole E = 100 000 with
+"""Trainer's A2C update on its paths -- "framework" (framework GEMMs, FusedObjective, autograd, clip_grad_norm_,
+torch.optim.Adam, the repack), "kernels" (`trainer.fused_update: "all"`: five launches,
+training/pg_update_kernels.py) and, for Cartpole and Acrobot, "matrix" (the same with
+`trainer.fused_update_gradients: "matrix"`: the gradient launch on the float32 matrix cores) -- in ONE process on the one-launch rollout, at seven shapes: Cartpole E = 100 000 with
 T = 10 (the shipped shape) and T = 50, single_acrobot as shipped (E = 100, T = 500), the learning test's Acrobot
 E = 1000, T = 50, and TagGridWorld (training/pg_update_gridworld_kernels.py: five launches PER trained policy) at
 tag_gridworld.yaml's E = 1000, T = 100 with [32, 32] and with [64, 64] policies, both trained, and at the learning test's
@@ -12,9 +13,11 @@ iteration is rollout, synchronise, device event, `_update_model_params(it, False
 inside a repeat.  One JSON line per (shape, path): the median of every repeat, and the median / min / max over the
 repeats, of the update and of the whole iteration (rollout + update, host clock between two synchronisations); for the
 kernels path also the device time of each of the five launches.  A last line per shape says whether the slowest repeat
-of the kernels path is faster than the fastest repeat of the framework path.
+of the kernels path is faster than the fastest repeat of the framework path, and the same for the matrix path against
+both others.
 
     python scripts/pg_update_timing.py [--iterations 200] [--warmup 20] [--repeats 5] [--shapes 0,1,2,3,4,5,6]
+                                       [--matrix-blocks-per-cu H=N,...]
 """
 import argparse
 import json
@@ -34,12 +37,15 @@ SHAPES = (("cartpole", 100000, 10), ("cartpole", 100000, 50), ("acrobot", 100, 5
           ("tag_gridworld", 600, 100, 32, ("tagger",), 20))
 
 
-def build(env, E, T, fused, results_dir, width=None, trained=("shared",), grid_length=None):
+def build(env, E, T, path, results_dir, width=None, trained=("shared",), grid_length=None):
     from warp_drive_amd.training.scripts.train import setup_trainer
 
     trainer = {"num_envs": E, "train_batch_size": E * T, "num_episodes": 10 ** 6, "seed": 1, "fused_rollout_policy": "all"}
+    fused = path != "framework"
     if fused:
         trainer["fused_update"] = "all"
+    if path == "matrix":
+        trainer["fused_update_gradients"] = "matrix"
     ov = {"trainer": trainer, "saving": {"metrics_log_freq": 10 ** 9, "model_params_save_freq": 0}}
     name = f"single_{env}"
     if env == "tag_gridworld":
@@ -52,6 +58,7 @@ def build(env, E, T, fused, results_dir, width=None, trained=("shared",), grid_l
     tr = setup_trainer(name, ov, results_dir=results_dir, verbose=False)
     assert tr._batch_rollout is not None
     assert all(tr.update_path[p] == ("kernels" if fused else "framework") for p in trained), tr.update_path
+    assert not fused or env == "tag_gridworld" or tr.update_gradients_path == {"shared": "matrix" if path == "matrix" else "lanes"}
     return tr
 
 
@@ -112,13 +119,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--shapes", default=",".join(str(i) for i in range(len(SHAPES))))
+    ap.add_argument("--matrix-blocks-per-cu", default="", help="H=N,...: blocks of the matrix entry per compute unit, to compare")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this measures the device: no GPU, no number"
-    paths = ("framework", "kernels")
+    from warp_drive_amd.training import pg_update_kernels as pguk
+
+    for item in filter(None, args.matrix_blocks_per_cu.split(",")):
+        pguk.MATRIX_BLOCKS_PER_CU[int(item.split("=")[0])] = int(item.split("=")[1])
     for env, E, T, *more in [SHAPES[int(i)] for i in args.shapes.split(",")]:
         trained = more[1] if more else ("shared",)
+        paths = ("framework", "kernels") + (() if more else ("matrix",))
         with tempfile.TemporaryDirectory() as tmp:
-            trainers = {p: build(env, E, T, p == "kernels", os.path.join(tmp, p), *more) for p in paths}
+            trainers = {p: build(env, E, T, p, os.path.join(tmp, p), *more) for p in paths}
             update = {p: [] for p in paths}
             whole = {p: [] for p in paths}
             it = 0
@@ -137,7 +149,9 @@ def main():
                               "iteration": summary(whole[p])}
                 if more:
                     records[p].update({"hidden": more[0], "trained": {pol: rows[pol] for pol in trained}})
-                if p == "kernels":
+                if p == "matrix":
+                    records[p]["blocks_per_cu"] = dict(pguk.MATRIX_BLOCKS_PER_CU)
+                if p != "framework":
                     launches = {pol: per_launch(trainers[p], 50, pol) for pol in trained}
                     records[p]["launch_us"] = launches if more else launches["shared"]
                 print(json.dumps(records[p]), flush=True)
@@ -145,6 +159,13 @@ def main():
             print(json.dumps({"env": env, "envs": E, "ticks": T, **({"hidden": more[0]} if more else {}), "kernels_slowest_repeat_us": k["max_us"],
                               "framework_fastest_repeat_us": f["min_us"], "kernels_faster": k["max_us"] < f["min_us"],
                               "ratio_of_medians": round(f["median_us"] / k["median_us"], 2)}), flush=True)
+            if "matrix" in records:
+                mx = records["matrix"]["update"]
+                print(json.dumps({"env": env, "envs": E, "ticks": T, "matrix_slowest_repeat_us": mx["max_us"],
+                                  "matrix_every_repeat_below_framework": all(a < f["min_us"] for a in mx["repeat_medians_us"]),
+                                  "matrix_not_slower_than_lanes": mx["median_us"] <= k["median_us"],
+                                  "framework_over_matrix": round(f["median_us"] / mx["median_us"], 2),
+                                  "lanes_over_matrix": round(k["median_us"] / mx["median_us"], 2)}), flush=True)
             for tr in trainers.values():
                 tr.graceful_close()
 

@@ -77,6 +77,10 @@ UNITS = {
     # Trainer's A2C / PPO update for the in-kernel policies (trainer.fused_update: "all"): values, gradients, reduce,
     # clip + Adam + the packed policy's refill
     "wd_kernels_pg.hsaco": ("pg_update.hip", []),
+    # its gradient launch with the three H x H products per row on the float32 matrix cores
+    # (trainer.fused_update_gradients: "matrix"); KERNEL_FLAGS, and no packed float32 operations at all: nothing here gains
+    # from them (see -fno-slp-vectorize below)
+    "wd_kernels_pg_mx.hsaco": ("pg_update_matrix.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]),
     # the same update for the two policies of the one-launch TagGridWorld rollout (21 inputs, five actions, n agents)
     "wd_kernels_pg_gw.hsaco": ("pg_update_gridworld.hip", []),
     "wd_kernels_test.hsaco": ("wd_test_kernels.hip", []),

@@ -7,7 +7,9 @@ wd_kernels_pg.hsaco; the returns entry is wd_kernels_update.hsaco's):
     HipPgReduce               partials -> flat gradient, per-tensor sums of squares, the four sums of the objective
     HipPgApply                clip, Adam, refill of the rollout's packed policy
 
-`trainer.fused_update: "all"` selects it (opt-in; training/trainer.py).  `admitted_shape` says which policies it serves;
+`trainer.fused_update: "all"` selects it (opt-in; training/trainer.py).  `trainer.fused_update_gradients: "matrix"` then
+launches HipPgGradientsMx_H<H>_O<O> (csrc/kernels/pg_update_matrix.hip, wd_kernels_pg_mx.hsaco) in the third place: the
+same arguments and partials, the three H x H products per row on the float32 matrix cores.  `admitted_shape` says which policies it serves;
 `PgUpdateKernels` holds the launch wrappers, their geometry fixed from E, T, H, O, A and the compute-unit count;
 `FlatPolicy` makes the parameters of a FullyConnected views of one flat float32 buffer in the kernels' layout, so the
 kernels update the module in place and the module remains the source of truth.
@@ -32,6 +34,11 @@ REDUCE_BLOCKS = TENSORS + 1   # eight parameter tensors + the four sums
 SUMS = 4                   # sum logp * adv, sum entropy, sum (v - ret)^2, sum adv
 APPLY_THREADS = 256
 LDS_LIMIT = 160 * 1024
+GRADIENTS_ENTRIES = ("lanes", "matrix")   # HipPgGradients (one row per lane) | HipPgGradientsMx (the matrix cores)
+MATRIX_THREADS = 256       # __launch_bounds__ of HipPgGradientsMx: four wavefronts of 32 rows, the same 128-row tile
+MATRIX_LD = 36             # row stride of the arrays a wavefront stages ([unit][32 rows])
+MATRIX_MAX_OBS = 6
+MATRIX_BLOCKS_PER_CU = {32: 2, 64: 1}   # what registers and LDS let a compute unit hold (docs/rounds/r47.md)
 RETURNS_ENTRY = "HipDiscountedReturns"
 _NULL = np.uint64(0)
 
@@ -69,14 +76,31 @@ def gradients_lds_bytes(H, O):
     return values_lds_bytes(H, O) + 4 * (2 * H * LD + O * LD + (MAX_ACTIONS + 1) * LD + SUMS * LD)
 
 
-def kernel_names(H, O):
+def gradients_matrix_lds_bytes(H, O):
+    """PgmLds<H, O>::TOTAL of pg_update_matrix.hip: the network (eight head rows, W1 with its rows padded by 8), per
+    wavefront two staged arrays [H][36] and the staged inputs [6][32] and deltas [9][32]"""
+    net = _pad4(H * O + H + H + MAX_ACTIONS * H + MAX_ACTIONS + H + 1) + H * (H + 8)
+    return 4 * (net + (MATRIX_THREADS // 64) * (2 * H * MATRIX_LD + (MATRIX_MAX_OBS + MAX_ACTIONS + 1) * 32))
+
+
+def gradients_entry_name(H, O, gradients_entry="lanes"):
+    assert gradients_entry in GRADIENTS_ENTRIES, gradients_entry
+    return f"HipPgGradients{'Mx' if gradients_entry == 'matrix' else ''}_H{H}_O{O}"
+
+
+def kernel_names(H, O, gradients_entry="lanes"):
     """the five launches, in order"""
-    return [f"HipPgValues_H{H}_O{O}", RETURNS_ENTRY, f"HipPgGradients_H{H}_O{O}", "HipPgReduce", "HipPgApply"]
+    return [f"HipPgValues_H{H}_O{O}", RETURNS_ENTRY, gradients_entry_name(H, O, gradients_entry), "HipPgReduce", "HipPgApply"]
 
 
 def all_kernel_names():
     """every entry of wd_kernels_pg.hsaco"""
     return sorted({n for H in HIDDEN for O in OBS_SIZES for n in kernel_names(H, O)} - {RETURNS_ENTRY})
+
+
+def matrix_kernel_names():
+    """every entry of wd_kernels_pg_mx.hsaco"""
+    return sorted(gradients_entry_name(H, O, "matrix") for H in HIDDEN for O in OBS_SIZES)
 
 
 def _admitted_tail(fc_dims, obs_size, obs_sizes, obs_takes, dtype, normalize_return, normalize_advantage, neg_pos_env_ratio,
@@ -164,10 +188,11 @@ class _PgUpdateLaunches:
     n, the two LDS sizes, the packed size and `_shape_args`.  Blocks and grids: the gradient kernel's block is its tile
     (TILE threads) and its grid one block per tile up to one per compute unit (the rest are grid-stride trips); the value
     kernel takes the largest block of 64 / 128 / 256 threads that still gives every compute unit one; Apply has one thread
-    per float of the larger of the network and the packed policy."""
+    per float of the larger of the network and the packed policy.  `gradients_block` / `blocks_per_cu`: another gradient
+    entry's block size and how many of its blocks a compute unit holds (the tile stays TILE rows)."""
 
     def _setup(self, function_manager, names, batch_shape, H, O, A, values_lds, gradients_lds, packed_floats, device,
-               compute_units):
+               compute_units, gradients_block=TILE, blocks_per_cu=1):
         self.T, self.E = int(batch_shape[0]), int(batch_shape[1])
         self.n = int(batch_shape[2]) if len(batch_shape) == 3 else 1
         assert self.E >= 1 and self.T >= 1 and self.n >= 1, batch_shape
@@ -192,7 +217,8 @@ class _PgUpdateLaunches:
         self.values_lds = values_lds
         self.returns_grid = -(-(self.E * self.n) // RETURNS_THREADS)
         self.tiles = -(-self.rows // TILE)
-        self.gradients_grid = max(1, min(self.tiles, self.compute_units))
+        self.gradients_block = int(gradients_block)
+        self.gradients_grid = max(1, min(self.tiles, self.compute_units * int(blocks_per_cu)))
         self.gradients_lds = gradients_lds
         self.apply_grid = -(-max(self.P, self.packed_floats) // APPLY_THREADS)
         assert max(self.values_lds, self.gradients_lds) <= LDS_LIMIT
@@ -262,7 +288,7 @@ class _PgUpdateLaunches:
         assert partials.dtype == torch.float32
         self.fn_gradients(obs, actions, advantages, returns, theta, np.int64(self.rows), *self._shape_args(True),
                           np.float32(1.0 / self.rows), np.float32(ent_coeff), np.float32(vf_coeff), partials,
-                          block=(TILE, 1, 1), grid=(int(partials.shape[0]), 1), shared=self.gradients_lds)
+                          block=(self.gradients_block, 1, 1), grid=(int(partials.shape[0]), 1), shared=self.gradients_lds)
         return partials
 
     def reduce(self, partials=None, grads=None, sumsq=None, sums=None):
@@ -327,12 +353,18 @@ class _PgUpdateLaunches:
 
 
 class PgUpdateKernels(_PgUpdateLaunches):
-    """The five launches for one (E, T, H, O, A): one agent per replica, every entry takes (H, O, A)."""
+    """The five launches for one (E, T, H, O, A): one agent per replica, every entry takes (H, O, A).
+    gradients_entry "matrix": the third launch is HipPgGradientsMx, its block, grid, LDS bytes and partials sized for it."""
 
-    def __init__(self, function_manager, E, T, H, O, A, device, compute_units=None):
+    def __init__(self, function_manager, E, T, H, O, A, device, compute_units=None, gradients_entry="lanes"):
         assert H in HIDDEN and O in OBS_SIZES and 1 <= A <= MAX_ACTIONS, (H, O, A)
-        self._setup(function_manager, kernel_names(H, O), (T, E), H, O, A, values_lds_bytes(H, O), gradients_lds_bytes(H, O),
-                    packed_floats(H, O, A), device, compute_units)
+        assert gradients_entry in GRADIENTS_ENTRIES, gradients_entry
+        self.gradients_entry = gradients_entry
+        matrix = gradients_entry == "matrix"
+        self._setup(function_manager, kernel_names(H, O, gradients_entry), (T, E), H, O, A, values_lds_bytes(H, O),
+                    gradients_matrix_lds_bytes(H, O) if matrix else gradients_lds_bytes(H, O), packed_floats(H, O, A), device,
+                    compute_units, gradients_block=MATRIX_THREADS if matrix else TILE,
+                    blocks_per_cu=MATRIX_BLOCKS_PER_CU[H] if matrix else 1)
 
     def _shape_args(self, per_row):
         return np.int32(self.H), np.int32(self.O), np.int32(self.A)

@@ -94,6 +94,9 @@ class Trainer:
         # (refused here, before anything touches the device)
         if isinstance(config["trainer"].get("fused_update", True), str) and config["trainer"]["fused_update"] != "all":
             raise ValueError(f"trainer.fused_update: True, False or \"all\", not {config['trainer']['fused_update']!r}")
+        if config["trainer"].get("fused_update_gradients", "lanes") not in pguk.GRADIENTS_ENTRIES:
+            raise ValueError(f"trainer.fused_update_gradients: \"lanes\" or \"matrix\", not "
+                             f"{config['trainer']['fused_update_gradients']!r}")
         E = env_wrapper.n_envs
         if policy_tag_to_agent_id_map is None:
             policy_tag_to_agent_id_map = {"shared": list(range(env_wrapper.n_agents))}
@@ -102,6 +105,9 @@ class Trainer:
         # {policy: "kernels" | "framework"}: which update a policy takes (`_setup_pg_update` decides)
         self.update_path = {pol: "framework" for pol in self.policies}
         self._pg_flat, self._pg_adam, self._pg_kernels, self._pg_stale_forward = {}, {}, {}, set()
+        # {policy: "lanes" | "matrix"} of the policies whose update is pg_update_kernels.PgUpdateKernels' five launches: the
+        # gradient entry they launch (`trainer.fused_update_gradients`)
+        self.update_gradients_path = {}
         assert set(self.policies) == set(config["policy"]), "every policy needs a config entry"
         tcfg = config["trainer"]
         self.num_envs = E
@@ -390,7 +396,10 @@ class Trainer:
         training/pg_update_custom_kernels.py::admitted_custom_shape and to the env object's `update_kernels_refusal` -- a
         custom environment whose code object has the update entries of include/wd_env_update.h, which then builds the
         launches itself (`update_kernels`).  Any other policy logs the reason once and stays on today's path;
-        `update_path` says which, per policy (it may be mixed)."""
+        `update_path` says which, per policy (it may be mixed).  `trainer.fused_update_gradients: "matrix"` (default
+        "lanes") gives a policy the FIRST rule admits the gradient launch on the float32 matrix cores
+        (csrc/kernels/pg_update_matrix.hip); the gridworld and custom-environment launches are what they were;
+        `update_gradients_path` says which entry such a policy launches."""
         if tcfg.get("fused_update", True) != "all" or self.device.type != "cuda":
             return
         for pol in self.policies:
@@ -446,8 +455,10 @@ class Trainer:
                 self._pg_kernels[pol] = pggk.PgGridworldUpdateKernels(env_wrapper.cuda_function_manager, self.num_envs,
                                                                       self.batch_len, len(ids), flat.H, self.device)
             else:
+                entry = tcfg.get("fused_update_gradients", "lanes")
                 self._pg_kernels[pol] = pguk.PgUpdateKernels(env_wrapper.cuda_function_manager, self.num_envs, self.batch_len,
-                                                             flat.H, flat.O, flat.A, self.device)
+                                                             flat.H, flat.O, flat.A, self.device, gradients_entry=entry)
+                self.update_gradients_path[pol] = entry
             self.update_path[pol] = "kernels"
 
     # --------------------------------------------------------------------------- rollout
