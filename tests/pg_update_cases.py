@@ -5,6 +5,9 @@
     tiles on 3 blocks), grids with 1 to 3 surplus blocks, both widths, O in {2, 4, 6}, A in {1, 2, 3, 8}, gamma 1 and 0.99,
     entropy coefficients 0 and 0.1, value coefficients 0.01 and 0.1, A2C and PPO, four done patterns, and one case whose
     head weights are scaled until the logit gaps exceed 110 (`gap`).
+  * `WAVE_CASES`, `GRID_CASES`, `DEPTH_CASES`, `out_of_range_actions`: beside `CASES`, for both gradient entries -- the
+    matrix entry's wavefront edges, the grid the wrapper picks on the device, the trip count of 5 M rows, and actions
+    outside 0 .. A - 1 (tests/test_pg_update_depth_host.py, tests/test_gpu_pg_update_depth.py).
   * the inputs of a case (`inputs`): the network has hidden units whose pre-activation is exactly 0 on every row (a zero
     row of weights and a zero bias, with non-zero weights leaving the unit: relu'(0) = 1 would show) and the usual negative
     pre-activations.
@@ -49,6 +52,76 @@ CASES = (
     _case(64, 5, 0.99, 64, 4, 3, 0.1, 0.1, "value 2", gap=True, seed=11),               # logit gaps above 110
     _case(65, 10, 1.0, 32, 6, 1, 0.1, 0.01, "last row", seed=12),                       # one action: no policy gradient at all
 )
+
+
+# Beside CASES (whose sets tests/test_pg_update_host.py pins): what the matrix entry and the trainer's launches add.
+# WAVE_CASES: the matrix entry works in wavefronts of 32 rows, four to a 128-row tile.  A last tile of 32 rows (a wavefront
+# exactly full), 33 (one row into the next wavefront), 96 (the last wavefront exactly dead), 97 (one row in wavefront 3).
+WAVE_CASES = (
+    _case(16, 2, 0.99, 32, 2, 3, 0.1, 0.1, "last row", seed=21),                        # 32 rows
+    _case(11, 3, 1.0, 64, 4, 8, 0.0, 0.01, "one mid-batch", "PPO", seed=22),            # 33 rows
+    _case(32, 3, 0.99, 32, 6, 1, 0.1, 0.01, "value 2", seed=23),                        # 96 rows
+    _case(15, 15, 0.99, 64, 2, 2, 0.1, 0.1, "none", "PPO", seed=24),                    # 225 rows = 128 + 97
+)
+# GRID_CASES: 65 984 rows = 516 tiles, the last of 64 rows: more tiles than `blocks per compute unit * compute units` on a
+# device of 256 compute units (256 blocks; 512 for the matrix entry at H = 32), so the wrapper's own cap decides the grid
+# and HipPgReduce sums 256 or 512 partials.  grid None here means: whatever the wrapper chooses.
+GRID_CASES = (
+    _case(1031, 64, 0.99, 32, 4, 2, 0.1, 0.1, "value 2", "PPO", seed=30),
+    _case(1031, 64, 0.99, 64, 6, 3, 0.1, 0.01, "value 2", seed=29),
+)
+# DEPTH_CASES: 20 385 rows = 160 tiles, the last of 33 rows, launched with compute_units = 1: ONE block makes 160 trips
+# (lanes, matrix at H = 64), two blocks 80 trips each (matrix at H = 32, two blocks per compute unit).  The recommended
+# workload, 5 000 000 rows = 39 063 tiles on 256 compute units, makes ceil(39 063 / 256) = 153 trips per block, and
+# ceil(39 063 / 512) = 77 for the matrix entry at H = 32: these cases accumulate at or above that depth.
+DEPTH_CASES = (
+    _case(4077, 5, 0.99, 32, 4, 2, 0.1, 0.1, "value 2", seed=25),
+    _case(4077, 5, 0.99, 64, 6, 3, 0.1, 0.01, "value 2", "PPO", seed=27),
+)
+# The seeds of the grid and depth cases are, per case, the first from 25 up (21 .. 24 are the wave cases') not yet taken for
+# which no pre-activation of either hidden layer, the units that are exactly 0 aside, lies within RELU_MARGIN of 0 in
+# float64.  A float32 evaluation decides relu's branch of such a row by its rounding, and ONE row on the other branch moves
+# a gradient by a row's share, 1 / rows of an O(1) number: 1e-5 at these sizes, a thousand times the bound's floor, in the
+# kernels and in the framework's float32 run alike.  (At 2570 rows `CASES` meets such a row with a chance of a few per cent;
+# at 65 984 rows and 128 units most seeds hold one.)  2^-22 is half an ulp of a float32 partial sum below 4.
+RELU_MARGIN = 2.0 ** -22
+OUT_OF_RANGE_VALUES = (-1, None, 2 ** 31 - 1, -2 ** 31)   # None: A, the first action past the range
+OUT_OF_RANGE_CASES = (CASES[3], CASES[1])                 # A = 8 on 325 rows (ent 0), A = 2 on 126 rows
+
+
+def out_of_range_rows(case):
+    """the rows (sorted, a seeded tenth of them, at least four) whose action `out_of_range_actions` replaces"""
+    rows = case.T * case.E
+    rng = np.random.default_rng(3000 + case.seed)
+    return np.sort(rng.choice(rows, max(len(OUT_OF_RANGE_VALUES), rows // 10), replace=False))
+
+
+def out_of_range_actions(case, inp):
+    """a copy of `inp` in which a seeded tenth of the rows has its action replaced by -1, A, 2^31 - 1 or -2^31 in turn (all
+    four present).  The kernels and `yardstick` define such a row: no one-hot term, logp of the clamped action."""
+    out = {k: v.copy() for k, v in inp.items()}
+    where = out_of_range_rows(case)
+    values = np.array([case.A if v is None else v for v in OUT_OF_RANGE_VALUES], np.int64)
+    flat = out["actions"].reshape(-1)
+    flat[where] = values[np.arange(where.size) % values.size].astype(np.int32)
+    assert out["actions"].dtype == np.int32 and np.shares_memory(flat, out["actions"])
+    return out
+
+
+def clipped_actions(case, inp):
+    """a copy of `inp` with every action clamped into 0 .. A - 1 (what the framework may be handed)"""
+    out = {k: v.copy() for k, v in inp.items()}
+    out["actions"] = np.clip(out["actions"], 0, case.A - 1).astype(np.int32)
+    return out
+
+
+def float32_error_of(want, want_in_range, yard_in_range, keys):
+    """The float32 run's error on the CLIPPED actions, carried over to `want` (the yardstick on the out-of-range ones):
+    want + (yard_in_range - want_in_range) per key.  Judged against `want` it gives err_f32 = |yard_in_range - want_in_range|,
+    the error a float32 computation of the same size and magnitude makes -- while the framework's result itself differs
+    from `want` by the out-of-range rows' one-hot, which as err_f32 would excuse exactly the defect looked for."""
+    return {k: np.asarray(want[k], f64) + (np.asarray(yard_in_range[k], f64).reshape(np.shape(want[k]))
+                                           - np.asarray(want_in_range[k], f64).reshape(np.shape(want[k]))) for k in keys}
 
 
 def case_tiles(case):

@@ -47,10 +47,10 @@ def references():
     return out
 
 
-def _kernels(fm, case):
+def _kernels(fm, case, compute_units=None, entry="lanes"):
     from warp_drive_amd.training.pg_update_kernels import PgUpdateKernels
 
-    return PgUpdateKernels(fm, case.E, case.T, case.H, case.O, case.A, DEV)
+    return PgUpdateKernels(fm, case.E, case.T, case.H, case.O, case.A, DEV, compute_units=compute_units, gradients_entry=entry)
 
 
 def _counts():
@@ -111,6 +111,8 @@ def _judge(tag, got, want, yard, keys, worst_only=False):
         worst = max(ratios, key=ratios.get)
         ratios = {f"worst of {len(ratios)}: {worst}": ratios[worst]}
     print(f"{tag}: err / err_f32 " + ", ".join(f"{k} {v:.2f}" for k, v in ratios.items()))
+    for k, err, err_f32, scale in failures:
+        print(f"{tag}: OUTSIDE the bound: {k} err {err:.3e} 4*err_f32 {4 * err_f32:.3e} floor {2e-6 * scale:.3e}")
     assert not failures, (tag, failures)
 
 
@@ -127,14 +129,11 @@ def _inputs_as_they_were(d, inp):
 
 
 # ================================================================================================ 1 + 2. values, returns
-@pytest.mark.parametrize("case", pc.CASES, ids=lambda c: c.name)
-def test_values_and_returns(fm, references, case):
-    """values under the bound against float64 -- at the wrapper's geometry, and bit-identical at one block of 64 threads
-    (grid-stride trips) and with surplus blocks; the returns the existing entry forms from them equal
-    losses.discounted_returns on the kernel's own values bit for bit, the advantages are returns - values"""
+def values_and_returns(fm, case, inp, want):
+    """the body of `test_values_and_returns` for one case, its inputs and the float64 yardstick from them (shared with
+    tests/test_gpu_pg_update_depth.py)"""
     from warp_drive_amd.training.losses import discounted_returns
 
-    inp, want = references[case.name]
     k, d = _kernels(fm, case), _device_inputs(inp)
     T, E = case.T, case.E
     results = []
@@ -165,23 +164,41 @@ def test_values_and_returns(fm, references, case):
     _inputs_as_they_were(d, inp)
 
 
-# ============================================================================================ 3 + 4. gradients, reduce
 @pytest.mark.parametrize("case", pc.CASES, ids=lambda c: c.name)
-def test_gradients_after_reduce(fm, references, case):
-    """from the kernel's own values, returns and advantages: the eight gradients and the four sums under the bound against
-    float64, the per-tensor sums of squares against those of the kernel's own gradients; blocks without rows write zeros;
-    nothing outside the written regions changes; a second run gives the same bytes"""
+def test_values_and_returns(fm, references, case):
+    """values under the bound against float64 -- at the wrapper's geometry, and bit-identical at one block of 64 threads
+    (grid-stride trips) and with surplus blocks; the returns the existing entry forms from them equal
+    losses.discounted_returns on the kernel's own values bit for bit, the advantages are returns - values"""
+    inp, want = references[case.name]
+    values_and_returns(fm, case, inp, want)
+
+
+# ============================================================================================ 3 + 4. gradients, reduce
+def gradients_after_reduce(fm, case, inp, entry="lanes", compute_units=None, actions=None):
+    """The body of `test_gradients_after_reduce` and of tests/test_gpu_pg_update_matrix.py's twin for one gradient entry
+    ("lanes" | "matrix").  compute_units None: the grid is the case's (`pc.case_grid`); given: the kernels are built for
+    that many compute units and the grid is the wrapper's own.  actions: a replacement of inp["actions"], possibly out of
+    range -- `want` is the yardstick on it, while err_f32 comes from the framework on the same inputs with the actions
+    CLIPPED into range (torch is never handed an out-of-range action), measured against the yardstick on those clipped
+    actions: the error of a float32 computation of the same size and magnitude (`pc.float32_error_of`).  Returns what the
+    launches left and how it was judged."""
     from warp_drive_amd.training import pg_update_kernels as pguk
 
-    inp, _ = references[case.name]
-    k, d = _kernels(fm, case), _device_inputs(inp)
+    if actions is not None:
+        inp = dict(inp, actions=np.ascontiguousarray(actions, np.int32).reshape(inp["actions"].shape))
+    in_range = pc.clipped_actions(case, inp)
+    launch = "HipPgGradientsMx" if entry == "matrix" else "HipPgGradients"
+    prefix = "matrix " if entry == "matrix" else ""
+    k, d = _kernels(fm, case, compute_units=compute_units, entry=entry), _device_inputs(inp)
     values = k.compute_values(d["obs"], d["theta"]).clone()
     returns, adv = k.discounted_returns(d["rewards"], d["done"], case.gamma, values=values)
     returns, adv = returns.clone(), adv.clone()
     v_host = values.cpu().numpy()
     want = pc.yardstick(case, inp, values=v_host)
-    yard = pc.framework(case, inp, torch.float32, DEV, values=v_host)
-    grid = pc.case_grid(case)
+    yard = pc.framework(case, in_range, torch.float32, DEV, values=v_host)
+    if actions is not None:
+        yard = pc.float32_error_of(want, pc.yardstick(case, in_range, values=v_host), yard, pc.TENSOR_NAMES + pc.SUM_NAMES)
+    grid = pc.case_grid(case) if compute_units is None else k.gradients_grid
     P = k.P
     runs = []
     for _ in range(2):
@@ -194,7 +211,7 @@ def test_gradients_after_reduce(fm, references, case):
                     returns=_fenced(returns.cpu().numpy()), partials=partials)
         k.reduce(partials=partials, grads=grads, sumsq=sumsq, sums=sums)
         torch.cuda.synchronize()
-        assert _launched_since(before) == {"HipPgGradients": 1, "HipPgReduce": 1}
+        assert _launched_since(before) == {launch: 1, "HipPgReduce": 1}   # (and never the other gradient entry)
         for whole, view in ((whole_p, partials), (whole_g, grads), (whole_s, sumsq), (whole_l, sums)):
             assert _untouched(whole, view), case.name
         runs.append((partials, grads, sumsq, sums))
@@ -202,21 +219,32 @@ def test_gradients_after_reduce(fm, references, case):
         assert _same_bytes(a, b), case.name
     partials, grads, sumsq, sums = runs[0]
     assert bool(torch.isfinite(partials).all())
-    assert grid == k.tiles or case.grid
+    assert grid == k.tiles or case.grid or compute_units is not None
     if grid > k.tiles:
         assert not partials[k.tiles:].any(), "a block without rows writes zeros"
     g_host = grads.cpu().numpy()
     bounds = pc.tensor_bounds(case.H, case.O, case.A)
     got = {name: g_host[lo:hi] for name, (lo, hi) in zip(pc.TENSOR_NAMES, bounds)}
     got.update({name: sums[i].item() for i, name in enumerate(pc.SUM_NAMES)})
-    _judge(f"gradients {case.name}", got, want, yard, pc.TENSOR_NAMES + pc.SUM_NAMES)
     ss_got = {n: sumsq[i].item() for i, n in enumerate(pc.TENSOR_NAMES)}
     ss_want = {n: float(np.sum(g_host[lo:hi].astype(f64) ** 2)) for n, (lo, hi) in zip(pc.TENSOR_NAMES, bounds)}
     ss_yard = {n: float((grads[lo:hi] * grads[lo:hi]).sum()) for n, (lo, hi) in zip(pc.TENSOR_NAMES, bounds)}
-    _judge(f"sums of squares {case.name}", ss_got, ss_want, ss_yard, pc.TENSOR_NAMES)
+    out = {"k": k, "grid": grid, "partials": partials, "values": v_host, "got": got, "want": want, "yard": yard,
+           "ss": (ss_got, ss_want, ss_yard)}
+    _judge(f"{prefix}gradients {case.name}", got, want, yard, pc.TENSOR_NAMES + pc.SUM_NAMES)
+    _judge(f"{prefix}sums of squares {case.name}", ss_got, ss_want, ss_yard, pc.TENSOR_NAMES)
     assert abs(k.gradient_norm(sumsq) - np.sqrt(sum(ss_want.values()))) <= 1e-5 * max(k.gradient_norm(sumsq), 1e-30)
     assert pguk.TILE == pc.TILE
     _inputs_as_they_were(d, inp)
+    return out
+
+
+@pytest.mark.parametrize("case", pc.CASES, ids=lambda c: c.name)
+def test_gradients_after_reduce(fm, references, case):
+    """from the kernel's own values, returns and advantages: the eight gradients and the four sums under the bound against
+    float64, the per-tensor sums of squares against those of the kernel's own gradients; blocks without rows write zeros;
+    nothing outside the written regions changes; a second run gives the same bytes"""
+    gradients_after_reduce(fm, case, references[case.name][0], "lanes")
 
 
 def test_an_entry_launched_for_another_shape_touches_nothing(fm):

@@ -5,8 +5,8 @@ import pytest
 import torch
 
 from tests import pg_update_cases as pc
-from tests.test_gpu_pg_update import (DEV, ENVS, _counts, _device_inputs, _fenced, _inputs_as_they_were, _judge,  # noqa: F401
-                                      _launched_since, _same_bytes, _sentinel, _trainer, _untouched, fm, references)
+from tests.test_gpu_pg_update import (DEV, ENVS, _counts, _device_inputs, _launched_since, _same_bytes, _sentinel,  # noqa: F401
+                                      _trainer, fm, gradients_after_reduce, references)
 
 pytestmark = pytest.mark.gpu
 f32, f64 = np.float32, np.float64
@@ -24,41 +24,7 @@ def test_matrix_gradients_after_reduce(fm, references, case):
     """from the kernels' own values, returns and advantages: HipPgGradientsMx, then the existing HipPgReduce -- the eight
     gradients and the four sums under the bound against float64, the sums of squares against those of the kernel's own
     gradients; surplus blocks write zeros; fences intact; inputs unchanged; a second run gives the same bytes"""
-    inp, _ = references[case.name]
-    k, d = _kernels(fm, case), _device_inputs(inp)
-    values = k.compute_values(d["obs"], d["theta"]).clone()
-    returns, adv = (t.clone() for t in k.discounted_returns(d["rewards"], d["done"], case.gamma, values=values))
-    v_host = values.cpu().numpy()
-    want = pc.yardstick(case, inp, values=v_host)
-    yard = pc.framework(case, inp, torch.float32, DEV, values=v_host)
-    grid, P = pc.case_grid(case), k.P
-    runs = []
-    for _ in range(2):
-        outs = [_sentinel(shape) for shape in ((grid, P + 4), (P,), (8,), (4,))]
-        partials, grads, sumsq, sums = (view for _, view in outs)
-        before = _counts()
-        k.gradients(d["obs"], d["actions"], d["theta"], case.ent, case.vf, advantages=_fenced(adv.cpu().numpy()),
-                    returns=_fenced(returns.cpu().numpy()), partials=partials)
-        k.reduce(partials=partials, grads=grads, sumsq=sumsq, sums=sums)
-        torch.cuda.synchronize()
-        assert _launched_since(before) == {"HipPgGradientsMx": 1, "HipPgReduce": 1}   # and no HipPgGradients
-        assert all(_untouched(whole, view) for whole, view in outs), case.name
-        runs.append((partials, grads, sumsq, sums))
-    assert all(_same_bytes(a, b) for a, b in zip(*runs)), case.name
-    partials, grads, sumsq, sums = runs[0]
-    assert bool(torch.isfinite(partials).all()) and (grid == k.tiles or case.grid)
-    if grid > k.tiles:
-        assert not partials[k.tiles:].any(), "a block without rows writes zeros"
-    g_host = grads.cpu().numpy()
-    bounds = pc.tensor_bounds(case.H, case.O, case.A)
-    got = {name: g_host[lo:hi] for name, (lo, hi) in zip(pc.TENSOR_NAMES, bounds)}
-    got.update({name: sums[i].item() for i, name in enumerate(pc.SUM_NAMES)})
-    _judge(f"matrix gradients {case.name}", got, want, yard, pc.TENSOR_NAMES + pc.SUM_NAMES)
-    ss_got = {n: sumsq[i].item() for i, n in enumerate(pc.TENSOR_NAMES)}
-    ss_want = {n: float(np.sum(g_host[lo:hi].astype(f64) ** 2)) for n, (lo, hi) in zip(pc.TENSOR_NAMES, bounds)}
-    ss_yard = {n: float((grads[lo:hi] * grads[lo:hi]).sum()) for n, (lo, hi) in zip(pc.TENSOR_NAMES, bounds)}
-    _judge(f"matrix sums of squares {case.name}", ss_got, ss_want, ss_yard, pc.TENSOR_NAMES)
-    _inputs_as_they_were(d, inp)
+    gradients_after_reduce(fm, case, references[case.name][0], "matrix")
 
 
 def test_a_matrix_entry_launched_for_another_shape_touches_nothing(fm):

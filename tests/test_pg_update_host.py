@@ -251,6 +251,11 @@ def test_cases_cover_what_the_issue_lists():
 @pytest.mark.parametrize("case", pc.CASES, ids=lambda c: c.name)
 def test_inputs_hold_what_the_cases_promise(case, references):
     inp, want, _, _ = references[case.name]
+    check_inputs(case, inp, want)
+
+
+def check_inputs(case, inp, want):
+    """(shared with tests/test_pg_update_depth_host.py)"""
     net = {k: v.astype(f64) for k, v in pc.unflatten(inp["theta"], case.H, case.O, case.A).items()}
     z, _, (_, z1, _, z2, _) = pc.forward64(net, inp["obs"].astype(f64).reshape(-1, case.O))
     assert (z1 < 0).any() and (z2 < 0).any() and (z1 > 0).any() and (z2 > 0).any()
@@ -280,7 +285,10 @@ def test_inputs_hold_what_the_cases_promise(case, references):
 def test_written_out_float64_pass_agrees_with_float64_autograd(case, references):
     """training/losses.py's A2C and PPO objects, end to end, and the same objective on GIVEN values (what the GPU file
     hands the gradient stage)"""
-    inp, want, auto64, auto32 = references[case.name]
+    check_float64_agreement(case, *references[case.name])
+
+
+def check_float64_agreement(case, inp, want, auto64, auto32):
     given = auto32["values"].astype(f32)
     for w, a in ((want, auto64), (pc.yardstick(case, inp, values=given), pc.framework(case, inp, torch.float64, values=given))):
         for key in RESULT_KEYS:
@@ -293,9 +301,13 @@ def test_written_out_float64_pass_agrees_with_float64_autograd(case, references)
 
 @pytest.mark.parametrize("case", pc.CASES, ids=lambda c: c.name)
 def test_returns_model_is_discounted_returns_bit_for_bit(case, references):
+    inp, _, _, auto32 = references[case.name]
+    check_returns_model(case, inp, auto32)
+
+
+def check_returns_model(case, inp, auto32):
     from warp_drive_amd.training.losses import discounted_returns
 
-    inp, _, _, auto32 = references[case.name]
     v = auto32["values"].astype(f32)
     want = discounted_returns(torch.from_numpy(inp["rewards"])[..., None], torch.from_numpy(inp["done"]),
                               torch.from_numpy(v)[..., None], case.gamma)

@@ -127,6 +127,25 @@ __device__ __forceinline__ void pg_acc_heads(PgAcc<H, O> &g, const float *S1, co
   }
 }
 
+// acc += trip, field by field.  A trip's 128 rows are summed from +0 into `trip` and added here ONCE: an accumulator that
+// lives for the launch is then a chain of 128 + trips additions, not 128 * trips (at 160 trips the direct chain left the
+// bias gradients and the four sums outside the float32 bound: docs/rounds/r48.md)
+template <int H, int O>
+__device__ __forceinline__ void pg_fold_trip(PgAcc<H, O> &acc, const PgAcc<H, O> &trip) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < PgAcc<H, O>::JB; ++b) acc.w1[a][b] += trip.w1[a][b];
+#pragma unroll
+  for (int c = 0; c < PgAcc<H, O>::KB; ++c) acc.w0[c] += trip.w0[c];
+#pragma unroll
+  for (int c = 0; c < PgAcc<H, O>::OB; ++c) acc.wo[c] += trip.wo[c];
+  acc.b0 += trip.b0;
+  acc.b1 += trip.b1;
+  acc.bo += trip.bo;
+  acc.sum += trip.sum;
+}
+
 // the block's partial, in the FLAT layout (A logits): P floats, then the four sums.  (Stays here for its head part.)
 template <int H, int O>
 __device__ __forceinline__ void pg_write_partial(const PgAcc<H, O> &g, float *out, int A) {
@@ -184,6 +203,8 @@ __device__ __forceinline__ void pg_gradients_impl(const float *__restrict__ obs,
   for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const long g = tile * PG_TILE + tid;
     const bool live = g < rows;
+    PgAcc<H, O> trip;
+    trip.clear();
     float x[O];
 #pragma unroll
     for (int k = 0; k < O; ++k) x[k] = 0.0f;
@@ -264,7 +285,7 @@ __device__ __forceinline__ void pg_gradients_impl(const float *__restrict__ obs,
       for (int k = 0; k < O; ++k) S2[k * PG_LD + tid] = x[k];
     }
     __syncthreads();
-    pg_acc_heads<H, O>(acc, S1, SD, SS, A);
+    pg_acc_heads<H, O>(trip, S1, SD, SS, A);
     __syncthreads();
     {
       // d2[i] = relu'(h2[i]) * (sum_j dz[j] Wp[j][i] + dv Wv[i]), j ascending from +0, the value last (the deltas read
@@ -297,7 +318,7 @@ __device__ __forceinline__ void pg_gradients_impl(const float *__restrict__ obs,
       upd_stage<H, PG_LD>(S1, tid, d2);
     }
     __syncthreads();
-    upd_acc_w1<H, PG_TILE, PG_LD>(acc, S0, S1);
+    upd_acc_w1<H, PG_TILE, PG_LD>(trip, S0, S1);
     {
       float d1[H];
       upd_layer1_backward<H, PG_LD>(w + L::W1, S1 + tid, m1, d1);
@@ -305,7 +326,8 @@ __device__ __forceinline__ void pg_gradients_impl(const float *__restrict__ obs,
       upd_stage<H, PG_LD>(S1, tid, d1);
     }
     __syncthreads();
-    upd_acc_w0<H, PG_TILE, PG_LD, O>(acc, S1, S2);
+    upd_acc_w0<H, PG_TILE, PG_LD, O>(trip, S1, S2);
+    pg_fold_trip<H, O>(acc, trip);
     __syncthreads();
   }
   pg_write_partial<H, O>(acc, partials + (long)blockIdx.x * (upd_pg_net_floats(H, O, A) + 4), A);
