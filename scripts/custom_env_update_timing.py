@@ -1,18 +1,20 @@
 #!/usr/bin/env python3
-"""The A2C / PPO update of a custom environment as kernels (include/wd_env_update.h) against the framework's update, on
-examples/rendezvous_update/ at N = 100 agents and a batch of 20 ticks: E = 2000 replicas (4 M rows) and E = 200 (400 k
-rows), per hidden width three plans in ONE process, all on the one-launch rollout:
+"""The A2C / PPO update of a custom environment as kernels (include/wd_env_update.h, include/wd_env_update_matrix.h) against
+the framework's update, on examples/rendezvous_update_matrix/ at N = 100 agents and a batch of 20 ticks: E = 2000 replicas
+(4 M rows) and E = 200 (400 k rows), per hidden width three plans in ONE process, all on the one-launch rollout:
 
     "framework"    `trainer.fused_update` unset: the update in framework ops -- the parent commit's path, the yardstick
-    "kernels x1"   `trainer.fused_update: "all"`: five launches, the gradient launch on ONE block per compute unit
-    "kernels x2"   the same with TWO blocks per compute unit (PgCustomUpdateKernels' `blocks_per_cu`)
+    "lanes"        `trainer.fused_update: "all"`: five launches, the gradient launch one batch row per lane on the wrapper's
+                   default grid (docs/rounds/r39.md: two blocks per compute unit at width 32, one at width 64)
+    "matrix"       the same with `trainer.fused_update_gradients: "matrix"`: the gradient launch on the matrix cores
 
 Method (scripts/custom_env_rollout_timing.py's): device events around `--updates` calls of `Trainer._update_model_params`
 (non-logging) on a rolled-out batch, after `--warmup` calls, six windows per plan, the plans alternating inside every round
 so that each sees the same drift of the clocks.  One JSON line per plan with every window (ms per update) and the time of
 a whole training iteration (rollout + update, host time between two synchronisations), then one line per shape and width
 that says, for each kernel plan, whether EVERY window of it lies below EVERY window of the framework's, and whether every
-window of "kernels x2" lies below every window of "kernels x1".  Nothing gates on the times.
+window of "matrix" lies below every window of "lanes".  The gradient launch alone (`--updates` launches per window, the
+two entries alternating) is in the kernel plans' lines.  Nothing gates on the times.
 
     python scripts/custom_env_update_timing.py [--envs 2000 200] [--agents 100] [--batch 20] [--updates 20] [--warmup 3]
 """
@@ -30,14 +32,14 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-PLANS = ("framework", "kernels x1", "kernels x2")
-BLOCKS_PER_CU = {"kernels x1": 1, "kernels x2": 2}
+PLANS = ("framework", "lanes", "matrix")
 POLICY = "shared"
 
 
 def update_example():
     spec = importlib.util.spec_from_file_location(
-        "rendezvous_update_example", os.path.join(ROOT, "examples", "rendezvous_update", "rendezvous_update.py"))
+        "rendezvous_update_matrix_example",
+        os.path.join(ROOT, "examples", "rendezvous_update_matrix", "rendezvous_update_matrix.py"))
     module = importlib.util.module_from_spec(spec)
     sys.modules[spec.name] = module
     spec.loader.exec_module(module)
@@ -50,15 +52,15 @@ def build(plan, width, envs, args, module, results_dir):
     from warp_drive_amd.utils.env_registrar import EnvironmentRegistrar
 
     registrar = EnvironmentRegistrar()
-    registrar.add(env_backend=["cpu", "hip"], cuda_env_src_path=module.SOURCE)(module.RendezvousUpdate)
+    registrar.add(env_backend=["cpu", "hip"], cuda_env_src_path=module.SOURCE)(module.RendezvousUpdateMatrix)
     env_config = dict(num_agents=args.agents, grid_length=10, episode_length=20, seed=1, wall_penalty=0.125,
                       spread_limit=-1)
-    w = EnvWrapper(env_name="RendezvousUpdate", env_config=env_config, num_envs=envs, env_backend="hip",
+    w = EnvWrapper(env_name="RendezvousUpdateMatrix", env_config=env_config, num_envs=envs, env_backend="hip",
                    env_registrar=registrar)
     trainer_config = {"num_envs": envs, "train_batch_size": envs * args.batch, "num_episodes": 10 ** 7, "seed": 7,
                       "fused_rollout_policy": "all"}
     if plan != "framework":
-        trainer_config["fused_update"] = "all"
+        trainer_config.update(fused_update="all", fused_update_gradients=plan)
     config = {"name": "rendezvous_update", "trainer": trainer_config,
               "policy": {POLICY: {"to_train": True, "algorithm": "A2C", "lr": 0.001, "vf_loss_coeff": 1, "gamma": 0.98,
                                   "entropy_coeff": 0.05, "clip_grad_norm": True, "max_grad_norm": 3,
@@ -73,10 +75,21 @@ def build(plan, width, envs, args, module, results_dir):
     want = "framework" if plan == "framework" else "kernels"
     assert trainer.update_path == {POLICY: want}, (plan, trainer.update_path)
     if plan != "framework":
-        k = trainer._pg_kernels[POLICY]
-        trainer._pg_kernels[POLICY] = w.env.update_kernels(envs, args.batch, args.agents, k.H, k.O, k.A, trainer.device,
-                                                           blocks_per_cu=BLOCKS_PER_CU[plan])
+        assert trainer.update_gradients_path == {POLICY: plan}, (plan, trainer.update_gradients_path)
     return trainer
+
+
+def gradient_window(trainer, launches):
+    """ms per gradient launch alone, on the batch and the values the last update left"""
+    k, b = trainer._pg_kernels[POLICY], trainer.batch[POLICY]
+    theta, T = trainer._pg_flat[POLICY].flat, trainer.batch_len
+    a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(launches):
+        k.gradients(b["obs"][:T], b["actions"][:T], theta, 0.05, 1.0)
+    e.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(e) / launches
 
 
 def run_updates(trainer, n):
@@ -128,6 +141,11 @@ def main():
                         run_updates(built[plan], args.warmup)
                         torch.cuda.synchronize()
                         times[plan].append(window(built[plan], args.updates))
+                alone = {plan: [] for plan in PLANS[1:]}
+                for _ in range(args.windows):
+                    for plan in PLANS[1:]:
+                        gradient_window(built[plan], args.warmup)
+                        alone[plan].append(gradient_window(built[plan], args.updates))
                 whole = {plan: iteration_ms(built[plan], args.iterations) for plan in PLANS}
                 rows = envs * args.agents * args.batch
                 for plan in PLANS:
@@ -139,17 +157,21 @@ def main():
                                       "updates_per_window": args.updates, "warmup_updates": args.warmup,
                                       "windows_ms_per_update": [round(v, 3) for v in ms],
                                       "median_ms_per_update": round(float(np.median(ms)), 3), "min_ms_per_update": round(min(ms), 3),
-                                      "max_ms_per_update": round(max(ms), 3), "iteration_ms": round(whole[plan], 2)}), flush=True)
+                                      "max_ms_per_update": round(max(ms), 3), "iteration_ms": round(whole[plan], 2),
+                                      "gradient_launch_windows_ms": [round(v, 3) for v in alone.get(plan, [])]}), flush=True)
                 med = {plan: float(np.median(times[plan])) for plan in PLANS}
                 below = lambda a, b: max(times[a]) < min(times[b])   # noqa: E731
                 print(json.dumps({"width": width, "envs": envs, "rows": rows,
-                                  "every_x1_window_below_every_framework_window": below("kernels x1", "framework"),
-                                  "every_x2_window_below_every_framework_window": below("kernels x2", "framework"),
-                                  "every_x2_window_below_every_x1_window": below("kernels x2", "kernels x1"),
-                                  "framework_over_x1": round(med["framework"] / med["kernels x1"], 2),
-                                  "framework_over_x2": round(med["framework"] / med["kernels x2"], 2),
-                                  "iteration_framework_over_x1": round(whole["framework"] / whole["kernels x1"], 2),
-                                  "iteration_framework_over_x2": round(whole["framework"] / whole["kernels x2"], 2)}),
+                                  "every_lanes_window_below_every_framework_window": below("lanes", "framework"),
+                                  "every_matrix_window_below_every_framework_window": below("matrix", "framework"),
+                                  "every_matrix_window_below_every_lanes_window": below("matrix", "lanes"),
+                                  "framework_over_lanes": round(med["framework"] / med["lanes"], 2),
+                                  "framework_over_matrix": round(med["framework"] / med["matrix"], 2),
+                                  "lanes_over_matrix": round(med["lanes"] / med["matrix"], 2),
+                                  "gradient_launch_lanes_over_matrix": round(
+                                      float(np.median(alone["lanes"]) / np.median(alone["matrix"])), 2),
+                                  "iteration_framework_over_lanes": round(whole["framework"] / whole["lanes"], 2),
+                                  "iteration_framework_over_matrix": round(whole["framework"] / whole["matrix"], 2)}),
                       flush=True)
                 for trainer in built.values():
                     trainer.graceful_close()

@@ -31,18 +31,15 @@
 // rows writes zeros; rows past `rows` are never read and contribute exactly zero; relu'(0) = 0.
 //
 // Dynamic LDS: PgmLds<H, O>::TOTAL floats (training/pg_update_kernels.py::gradients_matrix_lds_bytes).
-#include "pg_update_common.h"
+#include "pg_update_matrix_common.h"   // PGM_LD, pgm_f16, the lane's unit list, the staged arrays
 
 #define PGM_THREADS 256
 #define PGM_WAVES 4
 #define PGM_TILE 128              // rows per block tile
-#define PGM_LD 36                 // staged arrays are [unit][PGM_LD]: 32 rows, rows of 16-byte multiples
 #define PGM_MAX_ACTIONS 8
 #define PGM_OUTPUTS (PGM_MAX_ACTIONS + 1)   // the logits' deltas (those below A are real), then the value's
 #define PGM_MAX_OBS 6
 #define PGM_ROW_SUMS (PGM_OUTPUTS + 4)      // per row slot: the nine deltas (dbp, dbv), then the four sums
-
-typedef float pgm_f16 __attribute__((ext_vector_type(16)));
 
 // LDS, in floats: the network (Wp as eight rows, so everything behind it sits at a fixed 16-byte aligned offset; W1
 // last, its rows padded), then per wavefront two staged arrays [H][PGM_LD], then per wavefront the staged inputs [6][32]
@@ -61,57 +58,6 @@ struct PgmLds {
   static_assert(upd_pad4(upd_pg_net_floats(H, O, PGM_MAX_ACTIONS) + 4) + PGM_WAVES * 32 * PGM_ROW_SUMS <=
                 PGM_WAVES * WAVE_STAGE, "the staging area holds the block's partial");
 };
-
-// unit s of the list of lane half hf: tile s / 16, register v = s % 16 of the accumulator layout
-__device__ __forceinline__ constexpr int pgm_unit(int s, int hf) {
-  return 32 * (s / 16) + 8 * ((s % 16) / 4) + 4 * hf + s % 4;
-}
-
-// lower half's number + upper half's, on both halves
-__device__ __forceinline__ float pgm_add_halves(float mine, int hf) {
-  const float other = __shfl_xor(mine, 32);
-  return (hf ? other : mine) + (hf ? mine : other);
-}
-
-template <int NU>
-__device__ __forceinline__ uint32_t pgm_positive_mask(const float (&h)[NU]) {
-  uint32_t m = 0;
-#pragma unroll
-  for (int s = 0; s < NU; ++s) m |= (h[s] > 0.0f) ? (1u << s) : 0u;
-  return m;
-}
-
-// the lane's units of its row, unit-major: S[unit][row]
-template <int NU>
-__device__ __forceinline__ void pgm_stage(float *S, int r, int hf, const float (&h)[NU]) {
-#pragma unroll
-  for (int s = 0; s < NU; ++s) S[(pgm_unit(s, 0) + 4 * hf) * PGM_LD + r] = h[s];
-}
-
-// unit 32 t + m of the staged array, rows 16 hf .. 16 hf + 15
-template <int TO>
-__device__ __forceinline__ void pgm_unit_rows(const float *S, int m, int hf, float4 (&out)[TO][4]) {
-#pragma unroll
-  for (int t = 0; t < TO; ++t)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) out[t][q] = *(const float4 *)(S + (32 * t + m) * PGM_LD + 16 * hf + 4 * q);
-}
-
-// acc += sum over the sixteen rows, ascending, of a[row] * b[row]
-__device__ __forceinline__ float pgm_dot16(float acc, const float4 (&a)[4], const float4 (&b)[4]) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    acc = fmaf(a[q].x, b[q].x, acc); acc = fmaf(a[q].y, b[q].y, acc);
-    acc = fmaf(a[q].z, b[q].z, acc); acc = fmaf(a[q].w, b[q].w, acc);
-  }
-  return acc;
-}
-
-__device__ __forceinline__ float pgm_sum16(float acc, const float4 (&a)[4]) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) { acc += a[q].x; acc += a[q].y; acc += a[q].z; acc += a[q].w; }
-  return acc;
-}
 
 template <int H, int O>
 __device__ __forceinline__ void pgm_gradients_impl(const float *__restrict__ obs, const int *__restrict__ actions,

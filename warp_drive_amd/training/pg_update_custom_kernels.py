@@ -5,6 +5,8 @@ is wd_kernels_update.hsaco's):
     Hip<Name>PgValues_H<H>      values [T, E, n] of the recorded rows (n agents per replica)
     HipDiscountedReturns        the existing entry on `values` (n agents, w = 1, v_col = 0): returns and advantages [T, E, n]
     Hip<Name>PgGradients_H<H>   forward, the objective's gradient, backward: one partial of the eight tensors per block
+                                (gradients_entry "matrix": Hip<Name>PgGradientsMx_H<H>, WD_PG_UPDATE_MX_ENTRIES of
+                                include/wd_env_update_matrix.h -- the same arguments and partials, on the matrix cores)
     Hip<Name>PgReduce           partials -> flat gradient, per-tensor sums of squares, the four sums of the objective
     Hip<Name>PgApply            clip, Adam, refill of the rollout's packed policy (pack_rollout_policy: a prefix of the flat
                                 parameters)
@@ -17,8 +19,9 @@ warp_drive_amd/utils/custom_tick.py::FusedUpdateMixin asks it for an env class a
 import numpy as np
 import torch
 
-from warp_drive_amd.training.pg_update_kernels import (HIDDEN, LD, LDS_LIMIT, MAX_ACTIONS, RETURNS_ENTRY, SUMS,
-                                                       _admitted_tail, _pad4, _PgUpdateLaunches, packed_floats)
+from warp_drive_amd.training.pg_update_kernels import (GRADIENTS_ENTRIES, HIDDEN, LD, LDS_LIMIT, MATRIX_BLOCKS_PER_CU, MATRIX_LD,
+                                                       MATRIX_THREADS, MAX_ACTIONS, RETURNS_ENTRY, SUMS, TILE, _admitted_tail,
+                                                       _pad4, _PgUpdateLaunches, packed_floats)
 
 MAX_OBS = 32               # WD_UPD_MAX_OBS of include/wd_env_update.h
 MAX_BLOCKS_PER_CU = 2      # blocks of the gradient launch per compute unit, where two are resident (default_blocks_per_cu)
@@ -34,6 +37,15 @@ def gradients_lds_bytes(H, F):
     return values_lds_bytes(H, F) + 4 * LD * (2 * H + F + (MAX_ACTIONS + 1) + SUMS)
 
 
+def gradients_matrix_lds_bytes(H, F):
+    """wd_pg_gradients_mx_lds_floats of include/wd_env_update_matrix.h: the network (W0 k-major on F rounded up to even,
+    its inputs H or H + 32 floats apart; eight head rows; W1 with its rows padded by 8, at width 64 a transposed copy too),
+    per wavefront two staged arrays [H][36], the observation tile [F2][36] and the deltas [9][32]"""
+    F2, ldk = (F + 1) & ~1, H if H % 64 == 32 else H + 32
+    net = _pad4(F2 * ldk + H + H + MAX_ACTIONS * H + MAX_ACTIONS + H + 1) + (2 if H == 64 else 1) * H * (H + 8)
+    return 4 * (net + (MATRIX_THREADS // 64) * (2 * H * MATRIX_LD + F2 * MATRIX_LD + (MAX_ACTIONS + 1) * 32))
+
+
 def default_blocks_per_cu(H, F):
     """blocks of the gradient launch per compute unit: two where the LDS of a compute unit holds two of them (every
     width-32 shape), else one (every width-64 shape).  docs/rounds/r39.md: at width 32 every window of two blocks lay below
@@ -42,14 +54,22 @@ def default_blocks_per_cu(H, F):
     return max(1, min(MAX_BLOCKS_PER_CU, LDS_LIMIT // gradients_lds_bytes(H, F)))
 
 
-def kernel_names(prefix, H):
-    """the five launches, in order; `prefix`: "Hip<Name>Pg" """
-    return [f"{prefix}Values_H{H}", RETURNS_ENTRY, f"{prefix}Gradients_H{H}", f"{prefix}Reduce", f"{prefix}Apply"]
+def kernel_names(prefix, H, gradients_entry="lanes"):
+    """the five launches, in order; `prefix`: "Hip<Name>Pg"; gradients_entry "matrix": the third is the Mx entry of
+    include/wd_env_update_matrix.h"""
+    assert gradients_entry in GRADIENTS_ENTRIES, gradients_entry
+    mx = "Mx" if gradients_entry == "matrix" else ""
+    return [f"{prefix}Values_H{H}", RETURNS_ENTRY, f"{prefix}Gradients{mx}_H{H}", f"{prefix}Reduce", f"{prefix}Apply"]
 
 
 def all_kernel_names(prefix):
     """the six entries WD_PG_UPDATE_ENTRIES defines"""
     return sorted({n for H in HIDDEN for n in kernel_names(prefix, H)} - {RETURNS_ENTRY})
+
+
+def matrix_kernel_names(prefix):
+    """the two entries WD_PG_UPDATE_MX_ENTRIES defines"""
+    return [kernel_names(prefix, H, "matrix")[2] for H in HIDDEN]
 
 
 def admitted_custom_shape(one_launch_rollout, rollout_packing, n_policies, n_agents, head_sizes, fc_dims, obs_size, dtype,
@@ -81,16 +101,23 @@ def admitted_custom_shape(one_launch_rollout, rollout_packing, n_policies, n_age
 class PgCustomUpdateKernels(_PgUpdateLaunches):
     """The five launches for the policy of (E, T, n, H, F, A) on the entries `entry_prefix`Values_H<H> ...: rows =
     T * E * n; the Values and Gradients entries take A, Reduce and Apply take (H, A).  blocks_per_cu: the gradient
-    launch's grid is one block per tile up to this many per compute unit (None: default_blocks_per_cu)."""
+    launch's grid is one block per tile up to this many per compute unit (None: default_blocks_per_cu).
+    gradients_entry "matrix": the third launch is `entry_prefix`GradientsMx_H<H> of include/wd_env_update_matrix.h -- a
+    block of 256 threads on the same 128-row tile, its own LDS bytes, MATRIX_BLOCKS_PER_CU blocks per compute unit."""
 
-    def __init__(self, function_manager, entry_prefix, E, T, n, H, F, A, device, compute_units=None, blocks_per_cu=None):
+    def __init__(self, function_manager, entry_prefix, E, T, n, H, F, A, device, compute_units=None, blocks_per_cu=None,
+                 gradients_entry="lanes"):
         assert H in HIDDEN and 1 <= F <= MAX_OBS and 1 <= A <= MAX_ACTIONS, (H, F, A)
-        self._setup(function_manager, kernel_names(entry_prefix, H), (T, E, n), H, F, A, values_lds_bytes(H, F),
-                    gradients_lds_bytes(H, F), packed_floats(H, F, A), device, compute_units)
-        self.blocks_per_cu = default_blocks_per_cu(H, F) if blocks_per_cu is None else int(blocks_per_cu)
+        assert gradients_entry in GRADIENTS_ENTRIES, gradients_entry
+        self.gradients_entry = gradients_entry
+        matrix = gradients_entry == "matrix"
+        if blocks_per_cu is None:
+            blocks_per_cu = MATRIX_BLOCKS_PER_CU[H] if matrix else default_blocks_per_cu(H, F)
+        self.blocks_per_cu = int(blocks_per_cu)
         assert self.blocks_per_cu >= 1
-        self.gradients_grid = max(1, min(self.tiles, self.blocks_per_cu * self.compute_units))
-        self.partials = torch.zeros((self.gradients_grid, self.P + SUMS), dtype=torch.float32, device=self.device)
+        self._setup(function_manager, kernel_names(entry_prefix, H, gradients_entry), (T, E, n), H, F, A, values_lds_bytes(H, F),
+                    gradients_matrix_lds_bytes(H, F) if matrix else gradients_lds_bytes(H, F), packed_floats(H, F, A), device,
+                    compute_units, gradients_block=MATRIX_THREADS if matrix else TILE, blocks_per_cu=self.blocks_per_cu)
 
     def _shape_args(self, per_row):
         return (np.int32(self.A),) if per_row else (np.int32(self.H), np.int32(self.A))

@@ -398,8 +398,10 @@ class Trainer:
         launches itself (`update_kernels`).  Any other policy logs the reason once and stays on today's path;
         `update_path` says which, per policy (it may be mixed).  `trainer.fused_update_gradients: "matrix"` (default
         "lanes") gives a policy the FIRST rule admits the gradient launch on the float32 matrix cores
-        (csrc/kernels/pg_update_matrix.hip); the gridworld and custom-environment launches are what they were;
-        `update_gradients_path` says which entry such a policy launches."""
+        (csrc/kernels/pg_update_matrix.hip), and asks a custom environment that has the update entries for its ...PgGradientsMx
+        entries (include/wd_env_update_matrix.h) as well: an env without them says why in one log line and keeps its "lanes"
+        entries; the gridworld launches are what they were; `update_gradients_path` says which entry a policy of the
+        first or of the custom rule launches ("lanes" without the key)."""
         if tcfg.get("fused_update", True) != "all" or self.device.type != "cuda":
             return
         for pol in self.policies:
@@ -439,8 +441,22 @@ class Trainer:
                     len(self.policies), len(ids), self.head_sizes, pcfg["model"]["fc_dims"], obs_size, dtype,
                     bool(pcfg["normalize_return"]), bool(pcfg["normalize_advantage"]), self.neg_pos_env_ratio, self.world,
                     pcfg["algorithm"])
+                custom_entry = "lanes"
                 if custom:
-                    custom, why = offers(int(pcfg["model"]["fc_dims"][0]), obs_size, int(self.head_sizes[0]))
+                    shape = (int(pcfg["model"]["fc_dims"][0]), obs_size, int(self.head_sizes[0]))
+                    custom, why = offers(*shape)
+                    if custom and tcfg.get("fused_update_gradients", "lanes") == "matrix":
+                        # an env that has the update entries is asked for its matrix-core gradient entries as well; without
+                        # them (or with an `update_kernels_refusal` that takes no `gradients_entry`) it keeps "lanes"
+                        try:
+                            matrix, why_not = offers(*shape, gradients_entry="matrix")
+                        except TypeError:
+                            matrix, why_not = False, "the env's update_kernels_refusal takes no gradients_entry"
+                        if matrix:
+                            custom_entry = "matrix"
+                        elif self.rank == 0:
+                            logging.info(f"trainer.fused_update_gradients \"matrix\", policy '{pol}': {why_not}; its gradient "
+                                         "launch is the env's \"lanes\" entry")
             if not ok and not gridworld and not custom:
                 if self.rank == 0:
                     pguk.log_refusal(pol, why)
@@ -449,8 +465,10 @@ class Trainer:
             self._pg_flat[pol] = flat
             self._pg_adam[pol] = {"step": 0, "exp_avg": torch.zeros_like(flat.flat), "exp_avg_sq": torch.zeros_like(flat.flat)}
             if custom:
-                self._pg_kernels[pol] = env_wrapper.env.update_kernels(self.num_envs, self.batch_len, len(ids), flat.H, flat.O,
-                                                                       flat.A, self.device)
+                self._pg_kernels[pol] = env_wrapper.env.update_kernels(
+                    self.num_envs, self.batch_len, len(ids), flat.H, flat.O, flat.A, self.device,
+                    **({"gradients_entry": "matrix"} if custom_entry == "matrix" else {}))
+                self.update_gradients_path[pol] = custom_entry
             elif gridworld:
                 self._pg_kernels[pol] = pggk.PgGridworldUpdateKernels(env_wrapper.cuda_function_manager, self.num_envs,
                                                                       self.batch_len, len(ids), flat.H, self.device)

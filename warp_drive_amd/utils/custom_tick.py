@@ -246,9 +246,10 @@ class FusedUpdateMixin(FusedRolloutMixin):
     UPDATE_KERNEL_PREFIX = None
     UPDATE_OBS_SIZE = None
 
-    def update_kernels_refusal(self, width, obs_size, n_actions):
+    def update_kernels_refusal(self, width, obs_size, n_actions, gradients_entry="lanes"):
         """(True, "") when this env's code object has update entries for a policy of hidden width `width` on `obs_size`
-        observation floats with `n_actions` actions, else (False, why)"""
+        observation floats with `n_actions` actions, else (False, why); gradients_entry "matrix": and the two
+        ...PgGradientsMx_H* entries of include/wd_env_update_matrix.h"""
         from warp_drive_amd.training import pg_update_custom_kernels as pgck
 
         who = type(self).__name__
@@ -263,20 +264,27 @@ class FusedUpdateMixin(FusedRolloutMixin):
         if int(obs_size) != int(self.UPDATE_OBS_SIZE):
             return False, (f"observation size {int(obs_size)}: the update entries of {who} were compiled for "
                            f"{int(self.UPDATE_OBS_SIZE)}")
-        for name in pgck.all_kernel_names(self.UPDATE_KERNEL_PREFIX):
+        if gradients_entry not in pgck.GRADIENTS_ENTRIES:
+            return False, f"gradients_entry {gradients_entry!r}: one of {list(pgck.GRADIENTS_ENTRIES)}"
+        names = pgck.all_kernel_names(self.UPDATE_KERNEL_PREFIX)
+        if gradients_entry == "matrix":
+            names = names + pgck.matrix_kernel_names(self.UPDATE_KERNEL_PREFIX)
+        for name in names:
             if not self.cuda_function_manager.has_function(name):
                 return False, f"the entry {name}, which the env's code object does not have"
         return True, ""
 
-    def update_kernels(self, num_envs, batch_len, n_agents, width, obs_size, n_actions, device, **options):
+    def update_kernels(self, num_envs, batch_len, n_agents, width, obs_size, n_actions, device, gradients_entry="lanes",
+                       **options):
         """the five launches (training/pg_update_custom_kernels.py::PgCustomUpdateKernels) on this env's entries"""
         from warp_drive_amd.training import pg_update_custom_kernels as pgck
 
-        ok, why = self.update_kernels_refusal(width, obs_size, n_actions)
+        ok, why = self.update_kernels_refusal(width, obs_size, n_actions, gradients_entry)
         if not ok:
             raise UnsupportedRolloutShape(f"{type(self).__name__}: {why}")
         return pgck.PgCustomUpdateKernels(self.cuda_function_manager, self.UPDATE_KERNEL_PREFIX, num_envs, batch_len,
-                                          n_agents, width, obs_size, n_actions, device, **options)
+                                          n_agents, width, obs_size, n_actions, device, gradients_entry=gradients_entry,
+                                          **options)
 
 
 # ------------------------------------------------------------------------------------------------------------------
