@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Trainer's A2C update on its paths -- "framework" (framework GEMMs, FusedObjective, autograd, clip_grad_norm_,
 torch.optim.Adam, the repack), "kernels" (`trainer.fused_update: "all"`: five launches,
-training/pg_update_kernels.py) and, for Cartpole and Acrobot, "matrix" (the same with
-`trainer.fused_update_gradients: "matrix"`: the gradient launch on the float32 matrix cores) -- in ONE process on the one-launch rollout, at seven shapes: Cartpole E = 100 000 with
+training/pg_update_kernels.py) and "matrix" (the same with `trainer.fused_update_gradients: "matrix"`: the gradient
+launch on the float32 matrix cores) -- in ONE process on the one-launch rollout, at seven shapes: Cartpole E = 100 000 with
 T = 10 (the shipped shape) and T = 50, single_acrobot as shipped (E = 100, T = 500), the learning test's Acrobot
 E = 1000, T = 50, and TagGridWorld (training/pg_update_gridworld_kernels.py: five launches PER trained policy) at
 tag_gridworld.yaml's E = 1000, T = 100 with [32, 32] and with [64, 64] policies, both trained, and at the learning test's
@@ -12,9 +12,9 @@ Per shape: two trainers, same seed.  Per repeat and path: `--warmup` iterations,
 iteration is rollout, synchronise, device event, `_update_model_params(it, False)`, device event.  The paths alternate
 inside a repeat.  One JSON line per (shape, path): the median of every repeat, and the median / min / max over the
 repeats, of the update and of the whole iteration (rollout + update, host clock between two synchronisations); for the
-kernels path also the device time of each of the five launches.  A last line per shape says whether the slowest repeat
-of the kernels path is faster than the fastest repeat of the framework path, and the same for the matrix path against
-both others.
+kernels and matrix paths also the device time of each of the five launches (per trained policy on TagGridWorld).  A last
+line per shape says whether the slowest repeat of the kernels path is faster than the fastest repeat of the framework
+path, and the same for the matrix path against both others.
 
     python scripts/pg_update_timing.py [--iterations 200] [--warmup 20] [--repeats 5] [--shapes 0,1,2,3,4,5,6]
                                        [--matrix-blocks-per-cu H=N,...]
@@ -58,7 +58,7 @@ def build(env, E, T, path, results_dir, width=None, trained=("shared",), grid_le
     tr = setup_trainer(name, ov, results_dir=results_dir, verbose=False)
     assert tr._batch_rollout is not None
     assert all(tr.update_path[p] == ("kernels" if fused else "framework") for p in trained), tr.update_path
-    assert not fused or env == "tag_gridworld" or tr.update_gradients_path == {"shared": "matrix" if path == "matrix" else "lanes"}
+    assert not fused or tr.update_gradients_path == {p: "matrix" if path == "matrix" else "lanes" for p in trained}
     return tr
 
 
@@ -128,7 +128,7 @@ def main():
         pguk.MATRIX_BLOCKS_PER_CU[int(item.split("=")[0])] = int(item.split("=")[1])
     for env, E, T, *more in [SHAPES[int(i)] for i in args.shapes.split(",")]:
         trained = more[1] if more else ("shared",)
-        paths = ("framework", "kernels") + (() if more else ("matrix",))
+        paths = ("framework", "kernels", "matrix")
         with tempfile.TemporaryDirectory() as tmp:
             trainers = {p: build(env, E, T, p, os.path.join(tmp, p), *more) for p in paths}
             update = {p: [] for p in paths}
@@ -161,7 +161,9 @@ def main():
                               "ratio_of_medians": round(f["median_us"] / k["median_us"], 2)}), flush=True)
             if "matrix" in records:
                 mx = records["matrix"]["update"]
-                print(json.dumps({"env": env, "envs": E, "ticks": T, "matrix_slowest_repeat_us": mx["max_us"],
+                print(json.dumps({"env": env, "envs": E, "ticks": T, **({"hidden": more[0]} if more else {}),
+                                  "matrix_slowest_repeat_us": mx["max_us"], "lanes_fastest_repeat_us": k["min_us"],
+                                  "matrix_faster_than_lanes": mx["max_us"] < k["min_us"],
                                   "matrix_every_repeat_below_framework": all(a < f["min_us"] for a in mx["repeat_medians_us"]),
                                   "matrix_not_slower_than_lanes": mx["median_us"] <= k["median_us"],
                                   "framework_over_matrix": round(f["median_us"] / mx["median_us"], 2),

@@ -83,6 +83,10 @@ UNITS = {
     "wd_kernels_pg_mx.hsaco": ("pg_update_matrix.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]),
     # the same update for the two policies of the one-launch TagGridWorld rollout (21 inputs, five actions, n agents)
     "wd_kernels_pg_gw.hsaco": ("pg_update_gridworld.hip", []),
+    # ... and its gradient launch on the float32 matrix cores (21 inputs, five actions as compile-time constants), with the
+    # flags of wd_kernels_pg_mx.hsaco
+    "wd_kernels_pg_gw_mx.hsaco": ("pg_update_gridworld_matrix.hip", ["-Xclang", "-target-feature", "-Xclang",
+                                                                      "-packed-fp32-ops"]),
     "wd_kernels_test.hsaco": ("wd_test_kernels.hip", []),
 }
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")

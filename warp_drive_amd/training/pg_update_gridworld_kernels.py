@@ -10,11 +10,16 @@
 A row is (t, replica, agent of the policy): rows = T * E * n, and the objective's means are over all of them.  The network
 is the module's -- W0 [H][21], b0, W1 [H][H], b1, Wp [5][H], bp, Wv [1][H], bv, float32 -- flat in that order (`FlatPolicy`
 of training/pg_update_kernels.py, as it is); the packed policy is NOT a prefix of it (W0's rows are 24 floats apart there)
-and the Apply launch writes every float of it.  `admitted_gridworld_shape` says which policies this serves."""
+and the Apply launch writes every float of it.  `admitted_gridworld_shape` says which policies this serves.
+
+`trainer.fused_update_gradients: "matrix"` launches HipPgGwGradientsMatrix_H<H> (csrc/kernels/pg_update_gridworld_matrix.hip,
+wd_kernels_pg_gw_mx.hsaco) in the third place: the same arguments and partials, the three layers' products and the two
+weight gradients on the float32 matrix cores."""
 import numpy as np
 
-from warp_drive_amd.training.pg_update_kernels import (LD, RETURNS_ENTRY, SUMS, _admitted_tail, _pad4, _PgUpdateLaunches,
-                                                       net_floats)
+from warp_drive_amd.training.pg_update_kernels import (GRADIENTS_ENTRIES, LD, MATRIX_BLOCKS_PER_CU, MATRIX_LD,
+                                                       MATRIX_THREADS, RETURNS_ENTRY, SUMS, TILE, _admitted_tail, _pad4,
+                                                       _PgUpdateLaunches, net_floats)
 
 HIDDEN = (32, 64)          # widths the code object has entries for
 OBS = 21                   # observation floats of a TagGridWorld row at 5 agents (full observations)
@@ -22,6 +27,7 @@ ACTIONS = 5
 IN_STRIDE = 24             # floats per row of W0 in LDS and in the packed policy (tag_gridworld_n5_common.h: GW5_IN_STRIDE)
 BIAS_SLOTS = 8             # the value head's LDS copy starts behind eight bias slots: a 16-byte boundary
 CODE_OBJECT = "wd_kernels_pg_gw.hsaco"
+MATRIX_CODE_OBJECT = "wd_kernels_pg_gw_mx.hsaco"   # HipPgGwGradientsMatrix_H<H> alone
 
 
 def gw_net_floats(H):
@@ -46,14 +52,30 @@ def gradients_lds_bytes(H):
     return values_lds_bytes(H) + 4 * LD * (2 * H + OBS + (ACTIONS + 1) + SUMS)
 
 
-def kernel_names(H):
+def gradients_matrix_lds_bytes(H):
+    """gwm_lds_floats(H) of pg_update_gridworld_matrix.hip: the network (W0 k-major [22][32 or 96], b0, b1, Wp, eight bias
+    slots, Wv, bv; W1 and its transpose with rows padded by 8), per wavefront two staged arrays [H][36], the observation
+    tile [22][36] and the deltas [6][32]"""
+    obs2, ldk = OBS + 1, H if H % 64 == 32 else H + 32
+    net = _pad4(obs2 * ldk + H + H + ACTIONS * H + BIAS_SLOTS + H + 1) + 2 * H * (H + 8)
+    return 4 * (net + (MATRIX_THREADS // 64) * (2 * H * MATRIX_LD + obs2 * MATRIX_LD + (ACTIONS + 1) * 32))
+
+
+def kernel_names(H, gradients_entry="lanes"):
     """the five launches, in order"""
-    return [f"HipPgGwValues_H{H}", RETURNS_ENTRY, f"HipPgGwGradients_H{H}", "HipPgGwReduce", "HipPgGwApply"]
+    assert gradients_entry in GRADIENTS_ENTRIES, gradients_entry
+    mx = "Matrix" if gradients_entry == "matrix" else ""
+    return [f"HipPgGwValues_H{H}", RETURNS_ENTRY, f"HipPgGwGradients{mx}_H{H}", "HipPgGwReduce", "HipPgGwApply"]
 
 
 def all_kernel_names():
     """every entry of wd_kernels_pg_gw.hsaco"""
     return sorted({n for H in HIDDEN for n in kernel_names(H)} - {RETURNS_ENTRY})
+
+
+def matrix_kernel_names():
+    """every entry of wd_kernels_pg_gw_mx.hsaco"""
+    return sorted(kernel_names(H, "matrix")[2] for H in HIDDEN)
 
 
 def pack_from_flat(theta, H):
@@ -92,12 +114,18 @@ def admitted_gridworld_shape(one_launch_rollout, gridworld_packing, n_policies, 
 
 class PgGridworldUpdateKernels(_PgUpdateLaunches):
     """The five launches for one policy of (E, T, n, H): rows = T * E * n; the Values and Gradients entries take no shape
-    argument, Reduce and Apply take H."""
+    argument, Reduce and Apply take H.  gradients_entry "matrix": the third launch is HipPgGwGradientsMatrix_H<H>, its block
+    (256 threads on the same 128-row tiles), grid, LDS bytes and partials sized for it."""
 
-    def __init__(self, function_manager, E, T, n, H, device, compute_units=None):
+    def __init__(self, function_manager, E, T, n, H, device, compute_units=None, gradients_entry="lanes"):
         assert H in HIDDEN, H
-        self._setup(function_manager, kernel_names(H), (T, E, n), H, OBS, ACTIONS, values_lds_bytes(H), gradients_lds_bytes(H),
-                    packed_floats(H), device, compute_units)
+        assert gradients_entry in GRADIENTS_ENTRIES, gradients_entry
+        self.gradients_entry = gradients_entry
+        matrix = gradients_entry == "matrix"
+        self._setup(function_manager, kernel_names(H, gradients_entry), (T, E, n), H, OBS, ACTIONS, values_lds_bytes(H),
+                    gradients_matrix_lds_bytes(H) if matrix else gradients_lds_bytes(H), packed_floats(H), device,
+                    compute_units, gradients_block=MATRIX_THREADS if matrix else TILE,
+                    blocks_per_cu=MATRIX_BLOCKS_PER_CU[H] if matrix else 1)
 
     def _shape_args(self, per_row):
         return () if per_row else (np.int32(self.H),)

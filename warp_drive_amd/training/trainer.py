@@ -105,8 +105,8 @@ class Trainer:
         # {policy: "kernels" | "framework"}: which update a policy takes (`_setup_pg_update` decides)
         self.update_path = {pol: "framework" for pol in self.policies}
         self._pg_flat, self._pg_adam, self._pg_kernels, self._pg_stale_forward = {}, {}, {}, set()
-        # {policy: "lanes" | "matrix"} of the policies whose update is pg_update_kernels.PgUpdateKernels' five launches: the
-        # gradient entry they launch (`trainer.fused_update_gradients`)
+        # {policy: "lanes" | "matrix"} of the policies whose update is five kernel launches: the gradient entry they launch
+        # (`trainer.fused_update_gradients`)
         self.update_gradients_path = {}
         assert set(self.policies) == set(config["policy"]), "every policy needs a config entry"
         tcfg = config["trainer"]
@@ -398,10 +398,10 @@ class Trainer:
         launches itself (`update_kernels`).  Any other policy logs the reason once and stays on today's path;
         `update_path` says which, per policy (it may be mixed).  `trainer.fused_update_gradients: "matrix"` (default
         "lanes") gives a policy the FIRST rule admits the gradient launch on the float32 matrix cores
-        (csrc/kernels/pg_update_matrix.hip), and asks a custom environment that has the update entries for its ...PgGradientsMx
+        (csrc/kernels/pg_update_matrix.hip), a gridworld policy HipPgGwGradientsMatrix (csrc/kernels/
+        pg_update_gridworld_matrix.hip), and asks a custom environment that has the update entries for its ...PgGradientsMx
         entries (include/wd_env_update_matrix.h) as well: an env without them says why in one log line and keeps its "lanes"
-        entries; the gridworld launches are what they were; `update_gradients_path` says which entry a policy of the
-        first or of the custom rule launches ("lanes" without the key)."""
+        entries; `update_gradients_path` says which entry a policy launches ("lanes" without the key)."""
         if tcfg.get("fused_update", True) != "all" or self.device.type != "cuda":
             return
         for pol in self.policies:
@@ -470,8 +470,11 @@ class Trainer:
                     **({"gradients_entry": "matrix"} if custom_entry == "matrix" else {}))
                 self.update_gradients_path[pol] = custom_entry
             elif gridworld:
+                entry = tcfg.get("fused_update_gradients", "lanes")
                 self._pg_kernels[pol] = pggk.PgGridworldUpdateKernels(env_wrapper.cuda_function_manager, self.num_envs,
-                                                                      self.batch_len, len(ids), flat.H, self.device)
+                                                                      self.batch_len, len(ids), flat.H, self.device,
+                                                                      gradients_entry=entry)
+                self.update_gradients_path[pol] = entry
             else:
                 entry = tcfg.get("fused_update_gradients", "lanes")
                 self._pg_kernels[pol] = pguk.PgUpdateKernels(env_wrapper.cuda_function_manager, self.num_envs, self.batch_len,
