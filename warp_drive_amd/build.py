@@ -74,6 +74,9 @@ UNITS = {
     "wd_kernels_cc.hsaco": ("classic_control.hip", []),
     # TrainerDDPG's update (trainer.fused_update): next values, gradients, reduce, clip + Adam + soft update
     "wd_kernels_ddpg.hsaco": ("ddpg_update.hip", []),
+    # ... and its gradient launch on the float32 matrix cores (trainer.fused_update_gradients: "matrix"), with the flags
+    # of wd_kernels_pg_mx.hsaco
+    "wd_kernels_ddpg_mx.hsaco": ("ddpg_update_matrix.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]),
     # Trainer's A2C / PPO update for the in-kernel policies (trainer.fused_update: "all"): values, gradients, reduce,
     # clip + Adam + the packed policy's refill
     "wd_kernels_pg.hsaco": ("pg_update.hip", []),

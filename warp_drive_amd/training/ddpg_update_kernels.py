@@ -10,6 +10,10 @@ serves; `DdpgUpdateKernels` holds the launch wrappers, their geometry fixed from
 the parameters of the actor and the critic (and of their targets) views of one flat float32 buffer each, in the kernels'
 layout, so the kernels update the modules in place and the modules remain the source of truth.
 
+`trainer.fused_update_gradients: "matrix"` launches HipDdpgGradientsMatrix_H<H>_O<O> (csrc/kernels/ddpg_update_matrix.hip,
+wd_kernels_ddpg_mx.hsaco) in the second place: the same arguments, returns and partials, a row's passes split over two
+lanes and the eight H x H products of a row tile on the float32 matrix cores.
+
 Layout of one network (two hidden layers of H units on I inputs, one output), the order of its parameters:
 W0 [H][I], b0 [H], W1 [H][H], b1 [H], Wo [H], bo [1]; a flat buffer holds the actor (I = O), then the critic (I = O + 1)."""
 import logging
@@ -27,6 +31,10 @@ REDUCE_BLOCKS = 13         # twelve parameter tensors + the losses
 APPLY_THREADS = 256
 LDS_LIMIT = 160 * 1024
 TENSORS_PER_NETWORK = 6
+MATRIX_CODE_OBJECT = "wd_kernels_ddpg_mx.hsaco"   # HipDdpgGradientsMatrix_H<H>_O<O> alone
+GRADIENTS_ENTRIES = ("lanes", "matrix")            # `trainer.fused_update_gradients`
+MATRIX_THREADS = 256       # block of the matrix entry: four wavefronts on the same TILE rows
+MATRIX_LD = 36             # row stride of the arrays it stages per wavefront (pg_update_matrix_common.h: PGM_LD)
 _NULL = np.uint64(0)
 
 
@@ -62,12 +70,29 @@ def gradients_lds_bytes(H, O):
     return targets_lds_bytes(H, O) + 4 * (2 * H * LD + 4 * LD + 2 * TILE)
 
 
-def kernel_names(H, O):
-    return [f"HipDdpgTargets_H{H}_O{O}", f"HipDdpgGradients_H{H}_O{O}", "HipDdpgReduce", "HipDdpgApply"]
+def gradients_matrix_lds_bytes(H, O):
+    """dgm_lds_floats(H, O) of ddpg_update_matrix.hip: the two networks' small tensors (everything but W1), four copies
+    of W1 (actor, critic, each also transposed) with rows padded by 8, per wavefront two staged arrays [H][36], the staged
+    inputs [O + 1][32] and two deltas [2][32]"""
+    small = _pad4(H * O + 3 * H + 1) + _pad4(H * (O + 1) + 3 * H + 1)
+    return 4 * (small + 4 * H * (H + 8) + (MATRIX_THREADS // 64) * (2 * H * MATRIX_LD + (O + 3) * 32))
+
+
+def kernel_names(H, O, gradients_entry="lanes"):
+    """the four launches, in order"""
+    assert gradients_entry in GRADIENTS_ENTRIES, gradients_entry
+    mx = "Matrix" if gradients_entry == "matrix" else ""
+    return [f"HipDdpgTargets_H{H}_O{O}", f"HipDdpgGradients{mx}_H{H}_O{O}", "HipDdpgReduce", "HipDdpgApply"]
 
 
 def all_kernel_names():
+    """every entry of wd_kernels_ddpg.hsaco"""
     return sorted({n for H in HIDDEN for O in OBS_SIZES for n in kernel_names(H, O)})
+
+
+def matrix_kernel_names():
+    """every entry of wd_kernels_ddpg_mx.hsaco"""
+    return sorted(kernel_names(H, O, "matrix")[1] for H in HIDDEN for O in OBS_SIZES)
 
 
 def admitted_shape(n_policies, n_agents, obs_size, action_dims, actor_fc_dims, critic_fc_dims, normalize_return):
@@ -127,10 +152,14 @@ class FlatNetworks:
 class DdpgUpdateKernels:
     """The four launches for one (E, T, n_step, H, O).  Blocks and grids are fixed here: the gradient kernel's block is its
     tile (TILE threads) and its grid one block per tile up to one per compute unit (the rest are grid-stride trips); the
-    next-value kernel takes the largest block of 64 / 128 / 256 threads that still gives every compute unit one."""
+    next-value kernel takes the largest block of 64 / 128 / 256 threads that still gives every compute unit one.
+    gradients_entry "matrix": the second launch is HipDdpgGradientsMatrix_H<H>_O<O> (csrc/kernels/ddpg_update_matrix.hip) with
+    a block of MATRIX_THREADS and its own LDS bytes, on the same tiles, grid and partials."""
 
-    def __init__(self, function_manager, E, T, n_step, H, O, device, compute_units=None):
+    def __init__(self, function_manager, E, T, n_step, H, O, device, compute_units=None, gradients_entry="lanes"):
         assert H in HIDDEN and O in OBS_SIZES, (H, O)
+        assert gradients_entry in GRADIENTS_ENTRIES, gradients_entry
+        self.gradients_entry = gradients_entry
         assert n_step >= 1 and T >= max(n_step, 2), (T, n_step)
         self.E, self.T, self.n_step, self.H, self.O = int(E), int(T), int(n_step), int(H), int(O)
         self.V = self.T - self.n_step + 1
@@ -140,7 +169,7 @@ class DdpgUpdateKernels:
         self.compute_units = int(compute_units)
         self.PT = total_floats(H, O)
         self.PA = net_floats(H, O)
-        self.names = kernel_names(H, O)
+        self.names = kernel_names(H, O, gradients_entry)
         function_manager.initialize_functions(self.names)
         self.fn_targets, self.fn_gradients, self.fn_reduce, self.fn_apply = (function_manager.get_function(n) for n in self.names)
         # ---- geometry
@@ -154,7 +183,9 @@ class DdpgUpdateKernels:
         self.rows = self.V * self.E
         self.tiles = -(-self.rows // TILE)
         self.gradients_grid = max(1, min(self.tiles, self.compute_units))
-        self.gradients_lds = gradients_lds_bytes(H, O)
+        matrix = gradients_entry == "matrix"
+        self.gradients_block = MATRIX_THREADS if matrix else TILE
+        self.gradients_lds = gradients_matrix_lds_bytes(H, O) if matrix else gradients_lds_bytes(H, O)
         self.apply_grid = -(-self.PT // APPLY_THREADS)
         assert max(self.targets_lds, self.gradients_lds) <= LDS_LIMIT
         # ---- what the launches hand to each other
@@ -197,7 +228,7 @@ class DdpgUpdateKernels:
         assert partials.dim() == 2 and partials.shape[1] == self.PT + 2 and partials.is_contiguous()
         self.fn_gradients(obs, actions, rewards, done, next_values, theta, np.int32(self.T), np.int32(self.E),
                           np.int32(self.n_step), np.float32(gamma), np.float32(action_scale), np.float32(action_bias),
-                          returns_out, partials, block=(TILE, 1, 1), grid=(int(partials.shape[0]), 1),
+                          returns_out, partials, block=(self.gradients_block, 1, 1), grid=(int(partials.shape[0]), 1),
                           shared=self.gradients_lds)
         return partials, returns_out
 

@@ -99,10 +99,13 @@ class TrainerDDPG:
     Apply launch has refilled the packed actor the one-launch rollout skips its framework-side repack for as long as the
     actor's version counters stand.  A logging iteration computes the framework path's metrics under `no_grad` from the networks
     before the step, with the gradient norms from the reduce launch.  Works with either rollout path.  `update_path`
-    says which."""
+    says which.  `trainer.fused_update_gradients: "matrix"` (default "lanes") launches the gradient entry on the float32
+    matrix cores in the second place (csrc/kernels/ddpg_update_matrix.hip; docs/rounds/r51.md says from which batch it
+    pays); `update_gradients_path` says which entry, None on the framework path."""
 
     update_path = "framework"
-    _update_kernels = None   # training/ddpg_update_kernels.py::DdpgUpdateKernels on the "kernels" path
+    update_gradients_path = None   # "lanes" or "matrix" on the "kernels" path (`trainer.fused_update_gradients`)
+    _update_kernels = None  # training/ddpg_update_kernels.py::DdpgUpdateKernels on the "kernels" path
 
     def __init__(self, env_wrapper=None, config=None, policy_tag_to_agent_id_map=None, device_id=0, results_dir=None,
                  verbose=True):
@@ -118,6 +121,9 @@ class TrainerDDPG:
         if isinstance(wants_update_kernels, str) and wants_update_kernels != "all":
             raise ValueError(f"trainer.fused_update: True, False or \"all\", not {wants_update_kernels!r}")
         wants_update_kernels = bool(wants_update_kernels)   # ("all" = true here)
+        if config["trainer"].get("fused_update_gradients", "lanes") not in duk.GRADIENTS_ENTRIES:
+            raise ValueError(f"trainer.fused_update_gradients: \"lanes\" or \"matrix\", not "
+                             f"{config['trainer']['fused_update_gradients']!r}")
         defaults = yaml.safe_load(open(_DEFAULT_CONFIG))
         for key, default in defaults.items():
             if key == "policy":
@@ -218,9 +224,11 @@ class TrainerDDPG:
                 self._adam = {"step": 0, "exp_avg": torch.zeros_like(self._flat.flat),
                               "exp_avg_sq": torch.zeros_like(self._flat.flat)}
                 self._update_kernels = duk.DdpgUpdateKernels(env_wrapper.cuda_function_manager, E, self.batch_len,
-                                                             self.n_step, self._flat.H, obs_size, self.device)
+                                                             self.n_step, self._flat.H, obs_size, self.device,
+                                                             gradients_entry=tcfg.get("fused_update_gradients", "lanes"))
                 self._actor_range = (scale, bias)
                 self.update_path = "kernels"
+                self.update_gradients_path = self._update_kernels.gradients_entry
             else:
                 duk.log_refusal(why)
 
