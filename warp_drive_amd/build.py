@@ -80,6 +80,10 @@ UNITS = {
     # Trainer's A2C / PPO update for the in-kernel policies (trainer.fused_update: "all"): values, gradients, reduce,
     # clip + Adam + the packed policy's refill
     "wd_kernels_pg.hsaco": ("pg_update.hip", []),
+    # normalize_return / normalize_advantage between its returns and gradient launches (trainer.fused_update_normalize):
+    # per-tick moments and the two normalisations on [T][C] arrays, for every user of those launches; the flags of
+    # wd_kernels_pg.hsaco
+    "wd_kernels_pg_norm.hsaco": ("pg_normalize.hip", []),
     # its gradient launch with the three H x H products per row on the float32 matrix cores
     # (trainer.fused_update_gradients: "matrix"); KERNEL_FLAGS, and no packed float32 operations at all: nothing here gains
     # from them (see -fno-slp-vectorize below)

@@ -9,7 +9,10 @@ wd_kernels_pg.hsaco; the returns entry is wd_kernels_update.hsaco's):
 
 `trainer.fused_update: "all"` selects it (opt-in; training/trainer.py).  `trainer.fused_update_gradients: "matrix"` then
 launches HipPgGradientsMx_H<H>_O<O> (csrc/kernels/pg_update_matrix.hip, wd_kernels_pg_mx.hsaco) in the third place: the
-same arguments and partials, the three H x H products per row on the float32 matrix cores.  `admitted_shape` says which policies it serves;
+same arguments and partials, the three H x H products per row on the float32 matrix cores.
+`trainer.fused_update_normalize: true` serves a policy with `normalize_return` / `normalize_advantage` too: two or three
+launches of csrc/kernels/pg_normalize.hip (wd_kernels_pg_norm.hsaco) between the second and the third
+(`_PgUpdateLaunches.normalize`).  `admitted_shape` says which policies it serves;
 `PgUpdateKernels` holds the launch wrappers, their geometry fixed from E, T, H, O, A and the compute-unit count;
 `FlatPolicy` makes the parameters of a FullyConnected views of one flat float32 buffer in the kernels' layout, so the
 kernels update the module in place and the module remains the source of truth.
@@ -40,6 +43,12 @@ MATRIX_LD = 36             # row stride of the arrays a wavefront stages ([unit]
 MATRIX_MAX_OBS = 6
 MATRIX_BLOCKS_PER_CU = {32: 2, 64: 1}   # what registers and LDS let a compute unit hold (docs/rounds/r47.md)
 RETURNS_ENTRY = "HipDiscountedReturns"
+# normalize_return / normalize_advantage between the returns and the gradient launch (csrc/kernels/pg_normalize.hip)
+NORMALIZE_CODE_OBJECT = "wd_kernels_pg_norm.hsaco"
+NORMALIZE_ENTRIES = ("HipPgTickMoments", "HipPgNormalizeReturns", "HipPgNormalizeAdvantages")
+NORMALIZE_THREADS = 256    # their __launch_bounds__: one block per (tick, chunk), 16 columns per lane
+NORMALIZE_CHUNK = 16 * NORMALIZE_THREADS
+NORMALIZE_EPS = 1.0e-10    # losses._EPSILON
 _NULL = np.uint64(0)
 
 
@@ -149,6 +158,15 @@ def admitted_shape(one_launch_rollout, n_policies, n_agents, head_sizes, fc_dims
                           normalize_return, normalize_advantage, neg_pos_env_ratio, world_size, algorithm, one_launch_rollout)
 
 
+def normalize_refusal(n_envs, n_agents):
+    """(True, "") when the normalising launches serve a policy of n_agents agents on n_envs replicas, else (False, why)"""
+    columns = int(n_envs) * int(n_agents)
+    if columns < 2:
+        return False, (f"{columns} column per tick: the unbiased standard deviation of normalize_return / "
+                       "normalize_advantage is NaN there")
+    return True, ""
+
+
 def policy_parameters(model):
     """the eight parameters of a two-hidden-layer, one-head FullyConnected in the kernels' order"""
     layers = [model.fc["0"][0], model.fc["1"][0], model.policy_head[0], model.vf_head]
@@ -221,6 +239,12 @@ class _PgUpdateLaunches:
         self.gradients_grid = max(1, min(self.tiles, self.compute_units * int(blocks_per_cu)))
         self.gradients_lds = gradients_lds
         self.apply_grid = -(-max(self.P, self.packed_floats) // APPLY_THREADS)
+        # (the normalising launches: one block per chunk of a tick's E * n columns; their entries and buffers come with
+        # the first `normalize`)
+        self.columns = self.E * self.n
+        self.normalize_chunks = -(-self.columns // NORMALIZE_CHUNK)
+        self.normalize_grid = self.T * self.normalize_chunks
+        self._function_manager, self._fn_normalize = function_manager, None
         assert max(self.values_lds, self.gradients_lds) <= LDS_LIMIT
         # ---- what the launches hand to each other
         f32 = dict(dtype=torch.float32, device=self.device)
@@ -271,6 +295,51 @@ class _PgUpdateLaunches:
                         np.int32(self.n), returns, advantages, block=(RETURNS_THREADS, 1, 1), grid=(self.returns_grid, 1),
                         shared=0)
         return returns, advantages
+
+    def _normalize_setup(self):
+        """first use: the three entries of wd_kernels_pg_norm.hsaco and what they write (a policy that never normalises
+        pays for neither); partials [T][chunks][2] = (mean, M2) per chunk of a tick"""
+        ok, why = normalize_refusal(self.E, self.n)
+        assert ok, why
+        self._function_manager.initialize_functions(list(NORMALIZE_ENTRIES))
+        self._fn_normalize = tuple(self._function_manager.get_function(n) for n in NORMALIZE_ENTRIES)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.norm_returns, self.norm_advantages = torch.zeros_like(self.returns), torch.zeros_like(self.advantages)
+        self.partials_returns = torch.zeros((self.T, self.normalize_chunks, 2), **f32)
+        self.partials_advantages = torch.zeros((self.T, self.normalize_chunks, 2), **f32)
+
+    def normalize(self, normalize_return, normalize_advantage, returns=None, values=None, advantages=None,
+                  norm_returns=None, norm_advantages=None):
+        """losses._normalise between `discounted_returns` and `gradients`, in A2C.compute_loss_and_metrics' order, as two
+        or three launches of one block per (tick, chunk of 4096 columns):
+            normalize_return:     Moments(returns), NormalizeReturns -> norm_returns, advantages = norm_returns - values
+            normalize_advantage:  Moments(advantages), NormalizeAdvantages -> norm_advantages
+            both:                 Moments(returns), NormalizeReturns (which also leaves the chunk moments of its
+                                  advantages), NormalizeAdvantages
+        Out of place but for `advantages` under normalize_return, which becomes norm_returns - values as in the framework.
+        Returns (advantages, returns) as the gradient launch is to read them."""
+        if not (normalize_return or normalize_advantage):
+            return (self.advantages if advantages is None else advantages), (self.returns if returns is None else returns)
+        if self._fn_normalize is None:
+            self._normalize_setup()
+        fn_moments, fn_returns, fn_advantages = self._fn_normalize
+        returns, values = self.returns if returns is None else returns, self.values if values is None else values
+        advantages = self.advantages if advantages is None else advantages
+        norm_returns = self.norm_returns if norm_returns is None else norm_returns
+        norm_advantages = self.norm_advantages if norm_advantages is None else norm_advantages
+        self._check_flat(returns, values, advantages, norm_returns, norm_advantages, numel=self.rows)
+        shape = (np.int32(self.T), np.int32(self.columns), np.int32(self.normalize_chunks))
+        launch = dict(block=(NORMALIZE_THREADS, 1, 1), grid=(self.normalize_grid, 1), shared=0)
+        eps = np.float32(NORMALIZE_EPS)
+        if normalize_return:
+            fn_moments(returns, *shape, self.partials_returns, **launch)
+            fn_returns(returns, values, self.partials_returns, *shape, eps, norm_returns, advantages,
+                       self.partials_advantages if normalize_advantage else _NULL, **launch)
+        else:
+            fn_moments(advantages, *shape, self.partials_advantages, **launch)
+        if normalize_advantage:
+            fn_advantages(advantages, self.partials_advantages, *shape, eps, norm_advantages, **launch)
+        return (norm_advantages if normalize_advantage else advantages), (norm_returns if normalize_return else returns)
 
     def gradients(self, obs, actions, theta, ent_coeff, vf_coeff, advantages=None, returns=None, partials=None):
         """per-block partials [blocks, P + 4]: the gradient of
@@ -323,24 +392,28 @@ class _PgUpdateLaunches:
         """the 2-norm of the whole gradient before clipping, from the reduce launch (reads the device)"""
         return float(torch.sqrt((self.sumsq if sumsq is None else sumsq).double().sum()))
 
-    def metrics(self, rewards, actions, ent_coeff, vf_coeff, ppo):
+    def metrics(self, rewards, actions, ent_coeff, vf_coeff, ppo, normalize_return=False, normalize_advantage=False):
         """the metric dict of losses.A2C.compute_loss_and_metrics_from_logits from what the launches left behind: values,
         returns, advantages and the four sums (reads the device; call after `reduce`); rewards [T, E, n], actions
-        [T, E, n, 1]"""
+        [T, E, n, 1].  After `normalize(normalize_return, normalize_advantage)` the four sums are those of the normalised
+        pair the gradient launch read, the raw and the normalised means are both reported and the explained variance is
+        formed from the normalised pair, as the framework does."""
         R = float(self.rows)
         s_pg, s_ent, s_vf, s_adv = (float(v) for v in self.sums.double().tolist())
         policy_loss = -(s_adv if ppo else s_pg) / R   # PPO at ratio 1: min(ratio * A, clamp(ratio) * A) = A
         vf_loss, entropy = s_vf / R, s_ent / R
         adv, ret = self.advantages.reshape(self.T, self.E, self.n), self.returns.reshape(self.T, self.E, self.n)
-        var_explained = torch.clamp(1 - adv.var() / (ret.var() + 1.0e-10), min=-1.0)
+        norm_adv = self.norm_advantages.reshape(adv.shape) if normalize_advantage else adv
+        norm_ret = self.norm_returns.reshape(ret.shape) if normalize_return else ret
+        var_explained = torch.clamp(1 - norm_adv.var() / (norm_ret.var() + 1.0e-10), min=-1.0)
         m = {
             "VF loss coefficient": vf_coeff, "Entropy coefficient": ent_coeff,
             "Total loss": float(np.float32(policy_loss + vf_coeff * vf_loss - ent_coeff * entropy)),
             "Policy loss": policy_loss, "Value function loss": vf_loss,
             "Mean rewards": rewards.mean().item(), "Max. rewards": rewards.max().item(),
             "Min. rewards": rewards.min().item(), "Mean value function": self.values.mean().item(),
-            "Mean advantages": adv.mean().item(), "Mean (norm.) advantages": adv.mean().item(),
-            "Mean (discounted) returns": ret.mean().item(), "Mean normalized returns": ret.mean().item(),
+            "Mean advantages": adv.mean().item(), "Mean (norm.) advantages": norm_adv.mean().item(),
+            "Mean (discounted) returns": ret.mean().item(), "Mean normalized returns": norm_ret.mean().item(),
             "Mean entropy": entropy, "Variance explained by the value function": var_explained.item(),
         }
         af = actions.reshape(self.T, self.E, self.n, -1).float()

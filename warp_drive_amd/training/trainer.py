@@ -97,6 +97,9 @@ class Trainer:
         if config["trainer"].get("fused_update_gradients", "lanes") not in pguk.GRADIENTS_ENTRIES:
             raise ValueError(f"trainer.fused_update_gradients: \"lanes\" or \"matrix\", not "
                              f"{config['trainer']['fused_update_gradients']!r}")
+        if not isinstance(config["trainer"].get("fused_update_normalize", False), bool):
+            raise ValueError(f"trainer.fused_update_normalize: True or False, not "
+                             f"{config['trainer']['fused_update_normalize']!r}")
         E = env_wrapper.n_envs
         if policy_tag_to_agent_id_map is None:
             policy_tag_to_agent_id_map = {"shared": list(range(env_wrapper.n_agents))}
@@ -108,6 +111,9 @@ class Trainer:
         # {policy: "lanes" | "matrix"} of the policies whose update is five kernel launches: the gradient entry they launch
         # (`trainer.fused_update_gradients`)
         self.update_gradients_path = {}
+        # {policy: (normalize_return, normalize_advantage)} of the policies on the "kernels" path whose returns / advantages
+        # the normalising launches serve (`trainer.fused_update_normalize`)
+        self._pg_normalize = {}
         assert set(self.policies) == set(config["policy"]), "every policy needs a config entry"
         tcfg = config["trainer"]
         self.num_envs = E
@@ -401,7 +407,11 @@ class Trainer:
         (csrc/kernels/pg_update_matrix.hip), a gridworld policy HipPgGwGradientsMatrix (csrc/kernels/
         pg_update_gridworld_matrix.hip), and asks a custom environment that has the update entries for its ...PgGradientsMx
         entries (include/wd_env_update_matrix.h) as well: an env without them says why in one log line and keeps its "lanes"
-        entries; `update_gradients_path` says which entry a policy launches ("lanes" without the key)."""
+        entries; `update_gradients_path` says which entry a policy launches ("lanes" without the key).
+        `trainer.fused_update_normalize: true` (default false) keeps a policy with `normalize_return` /
+        `normalize_advantage` on these launches: per-tick moments and the normalisations run as two or three more launches
+        between the returns and the gradients (csrc/kernels/pg_normalize.hip; `_PgUpdateLaunches.normalize`), for all three
+        kinds of policy above.  Without the key such a policy is refused as before."""
         if tcfg.get("fused_update", True) != "all" or self.device.type != "cuda":
             return
         for pol in self.policies:
@@ -411,9 +421,12 @@ class Trainer:
             ids = self.policy_map[pol]
             obs_size = flattened_obs_size(env_wrapper.env.observation_space[ids[0]])
             dtype = next(self.models[pol].parameters()).dtype if self._update_dtype is None else self._update_dtype
+            # `trainer.fused_update_normalize`: the admission rules are asked without the two normalisations, which the
+            # launches of csrc/kernels/pg_normalize.hip then serve (`_update_with_pg_kernels`); without the key they refuse
+            normalizes = (bool(pcfg["normalize_return"]), bool(pcfg["normalize_advantage"]))
+            asked = (False, False) if tcfg.get("fused_update_normalize", False) else normalizes
             ok, why = pguk.admitted_shape(self._batch_rollout is not None, len(self.policies), len(ids), self.head_sizes,
-                                          pcfg["model"]["fc_dims"], obs_size, dtype, bool(pcfg["normalize_return"]),
-                                          bool(pcfg["normalize_advantage"]), self.neg_pos_env_ratio, self.world,
+                                          pcfg["model"]["fc_dims"], obs_size, dtype, *asked, self.neg_pos_env_ratio, self.world,
                                           pcfg["algorithm"])
             if ok and self._batch_rollout["pack"] is not pack_rollout_policy:
                 ok, why = False, "the rollout's packed policy is not pack_rollout_policy's layout"
@@ -425,7 +438,7 @@ class Trainer:
                     self._batch_rollout is not None,
                     self._batch_rollout is not None and self._batch_rollout["pack"] is pack_gridworld_policy,
                     len(self.policies), len(ids), self.head_sizes, pcfg["model"]["fc_dims"], obs_size, dtype,
-                    bool(pcfg["normalize_return"]), bool(pcfg["normalize_advantage"]), self.neg_pos_env_ratio, self.world,
+                    *asked, self.neg_pos_env_ratio, self.world,
                     pcfg["algorithm"])
                 if not gridworld and self._batch_rollout is not None and self._batch_rollout["pack"] is pack_gridworld_policy:
                     why = gw_why   # (a gridworld policy is told what the gridworld kernels miss, not that it has 5 agents)
@@ -439,7 +452,7 @@ class Trainer:
                     self._batch_rollout is not None,
                     self._batch_rollout is not None and self._batch_rollout["pack"] is pack_rollout_policy,
                     len(self.policies), len(ids), self.head_sizes, pcfg["model"]["fc_dims"], obs_size, dtype,
-                    bool(pcfg["normalize_return"]), bool(pcfg["normalize_advantage"]), self.neg_pos_env_ratio, self.world,
+                    *asked, self.neg_pos_env_ratio, self.world,
                     pcfg["algorithm"])
                 custom_entry = "lanes"
                 if custom:
@@ -457,10 +470,16 @@ class Trainer:
                         elif self.rank == 0:
                             logging.info(f"trainer.fused_update_gradients \"matrix\", policy '{pol}': {why_not}; its gradient "
                                          "launch is the env's \"lanes\" entry")
+            if (ok or gridworld or custom) and any(normalizes):
+                served, why_not = pguk.normalize_refusal(self.num_envs, len(ids))
+                if not served:
+                    ok, gridworld, custom, why = False, False, False, why_not
             if not ok and not gridworld and not custom:
                 if self.rank == 0:
                     pguk.log_refusal(pol, why)
                 continue
+            if any(normalizes):
+                self._pg_normalize[pol] = normalizes
             flat = pguk.FlatPolicy(self.models[pol])
             self._pg_flat[pol] = flat
             self._pg_adam[pol] = {"step": 0, "exp_avg": torch.zeros_like(flat.flat), "exp_avg_sq": torch.zeros_like(flat.flat)}
@@ -750,9 +769,12 @@ class Trainer:
         ent_c = objective.entropy_coeff_schedule.get_param_value(self.current_timestep[pol])
         k.compute_values(obs, flat.flat)
         k.discounted_returns(rewards, done, objective.discount_factor_gamma)
-        k.gradients(obs, actions, flat.flat, ent_c, vf_c)
+        normalizes = self._pg_normalize.get(pol, (False, False))   # (`trainer.fused_update_normalize`: 2 or 3 launches more)
+        advantages, returns = k.normalize(*normalizes)
+        k.gradients(obs, actions, flat.flat, ent_c, vf_c, advantages=advantages, returns=returns)
         k.reduce()
-        metrics = k.metrics(rewards, actions, vf_coeff=vf_c, ent_coeff=ent_c, ppo=objective.clip_param is not None) if log else None
+        metrics = k.metrics(rewards, actions, vf_coeff=vf_c, ent_coeff=ent_c, ppo=objective.clip_param is not None,
+                            normalize_return=normalizes[0], normalize_advantage=normalizes[1]) if log else None
         adam["step"] += 1
         packed = self._batch_rollout["packed"][pol]
         k.apply(flat.flat, adam["exp_avg"], adam["exp_avg_sq"], adam["step"], pcfg["lr"],
