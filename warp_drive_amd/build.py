@@ -84,6 +84,10 @@ UNITS = {
     # per-tick moments and the two normalisations on [T][C] arrays, for every user of those launches; the flags of
     # wd_kernels_pg.hsaco
     "wd_kernels_pg_norm.hsaco": ("pg_normalize.hip", []),
+    # neg_pos_env_ratio before its values launch (trainer.fused_update_downsample): the positives of `done`, a Philox key
+    # per replica, a radix select of the negatives to keep, and the gather of the kept columns; the flags of
+    # wd_kernels_pg.hsaco
+    "wd_kernels_pg_select.hsaco": ("pg_downsample.hip", []),
     # its gradient launch with the three H x H products per row on the float32 matrix cores
     # (trainer.fused_update_gradients: "matrix"); KERNEL_FLAGS, and no packed float32 operations at all: nothing here gains
     # from them (see -fno-slp-vectorize below)

@@ -13,6 +13,9 @@ same arguments and partials, the three H x H products per row on the float32 mat
 `trainer.fused_update_normalize: true` serves a policy with `normalize_return` / `normalize_advantage` too: two or three
 launches of csrc/kernels/pg_normalize.hip (wd_kernels_pg_norm.hsaco) between the second and the third
 (`_PgUpdateLaunches.normalize`).  `admitted_shape` says which policies it serves;
+`trainer.fused_update_downsample: true` serves `trainer.neg_pos_env_ratio` too: three launches of
+csrc/kernels/pg_downsample.hip (wd_kernels_pg_select.hsaco) before the first, one read-back of three integers, and
+the launches above on the kept columns (`_PgUpdateLaunches.downsample`).
 `PgUpdateKernels` holds the launch wrappers, their geometry fixed from E, T, H, O, A and the compute-unit count;
 `FlatPolicy` makes the parameters of a FullyConnected views of one flat float32 buffer in the kernels' layout, so the
 kernels update the module in place and the module remains the source of truth.
@@ -49,6 +52,14 @@ NORMALIZE_ENTRIES = ("HipPgTickMoments", "HipPgNormalizeReturns", "HipPgNormaliz
 NORMALIZE_THREADS = 256    # their __launch_bounds__: one block per (tick, chunk), 16 columns per lane
 NORMALIZE_CHUNK = 16 * NORMALIZE_THREADS
 NORMALIZE_EPS = 1.0e-10    # losses._EPSILON
+# neg_pos_env_ratio before the values launch (csrc/kernels/pg_downsample.hip)
+DOWNSAMPLE_CODE_OBJECT = "wd_kernels_pg_select.hsaco"
+DOWNSAMPLE_ENTRIES = ("HipPgSelectScan", "HipPgSelectKeep", "HipPgGatherColumns")
+SELECT_SCAN_THREADS = 256  # one lane per replica
+SELECT_KEEP_THREADS = 1024  # HipPgSelectKeep is ONE block of these
+GATHER_THREADS = 256
+GATHER_CHUNK = 256         # kept columns per block of HipPgGatherColumns
+DOWNSAMPLE_STREAM_TAG = 0x646F776E   # "down": counter word 2 of the keys' Philox stream (word 3 is 6)
 _NULL = np.uint64(0)
 
 
@@ -213,6 +224,7 @@ class _PgUpdateLaunches:
                compute_units, gradients_block=TILE, blocks_per_cu=1):
         self.T, self.E = int(batch_shape[0]), int(batch_shape[1])
         self.n = int(batch_shape[2]) if len(batch_shape) == 3 else 1
+        self._batch_dims = len(batch_shape)
         assert self.E >= 1 and self.T >= 1 and self.n >= 1, batch_shape
         self.H, self.O, self.A = int(H), int(O), int(A)
         self.device = torch.device(device)
@@ -225,36 +237,53 @@ class _PgUpdateLaunches:
         function_manager.initialize_functions(self.names)
         (self.fn_values, self.fn_returns, self.fn_gradients, self.fn_reduce,
          self.fn_apply) = (function_manager.get_function(n) for n in self.names)
-        # ---- geometry
+        self.values_lds, self.gradients_lds = values_lds, gradients_lds
+        self.gradients_block, self._blocks_per_cu = int(gradients_block), int(blocks_per_cu)
+        self.apply_grid = -(-max(self.P, self.packed_floats) // APPLY_THREADS)
+        # (the normalising and the down-sampling launches: their entries and buffers come with the first `normalize` /
+        # `downsample`)
+        self._function_manager, self._fn_normalize, self._fn_downsample = function_manager, None, None
+        assert max(self.values_lds, self.gradients_lds) <= LDS_LIMIT
+        self.sampled = None                # (positives, negatives kept) of the last `downsample`
+        self.E_recorded = self.E           # replicas of the recorded batch; `downsample` may leave self.E below it
+        self._geometry(self.E)
+        # ---- what the launches hand to each other, allocated once for the recorded batch; the attributes are views of
+        # the first rows of these (all of them unless `downsample` kept fewer replicas)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self._whole = {name: torch.zeros(self.rows, **f32) for name in ("values", "returns", "advantages")}
+        self._whole["partials"] = torch.zeros((self.gradients_grid, self.P + SUMS), **f32)
+        self._views()
+        self.grads = torch.zeros(self.P, **f32)
+        self.sumsq = torch.zeros(TENSORS, **f32)
+        self.sums = torch.zeros(SUMS, **f32)
+
+    def _geometry(self, E):
+        """blocks and grids of every launch for a batch of T ticks of E replicas (the class docstring's rules)"""
+        self.E = int(E)
         self.rows = self.T * self.E * self.n
         block = VALUES_MAX_THREADS
         while block > 64 and -(-self.rows // block) < self.compute_units:
             block //= 2
         self.values_block = block
         self.values_grid = max(1, min(-(-self.rows // block), 8 * self.compute_units))
-        self.values_lds = values_lds
         self.returns_grid = -(-(self.E * self.n) // RETURNS_THREADS)
         self.tiles = -(-self.rows // TILE)
-        self.gradients_block = int(gradients_block)
-        self.gradients_grid = max(1, min(self.tiles, self.compute_units * int(blocks_per_cu)))
-        self.gradients_lds = gradients_lds
-        self.apply_grid = -(-max(self.P, self.packed_floats) // APPLY_THREADS)
-        # (the normalising launches: one block per chunk of a tick's E * n columns; their entries and buffers come with
-        # the first `normalize`)
+        self.gradients_grid = max(1, min(self.tiles, self.compute_units * self._blocks_per_cu))
+        # (the normalising launches: one block per chunk of a tick's E * n columns)
         self.columns = self.E * self.n
         self.normalize_chunks = -(-self.columns // NORMALIZE_CHUNK)
         self.normalize_grid = self.T * self.normalize_chunks
-        self._function_manager, self._fn_normalize = function_manager, None
-        assert max(self.values_lds, self.gradients_lds) <= LDS_LIMIT
-        # ---- what the launches hand to each other
-        f32 = dict(dtype=torch.float32, device=self.device)
-        self.values = torch.zeros(batch_shape, **f32)
-        self.returns = torch.zeros(batch_shape, **f32)
-        self.advantages = torch.zeros(batch_shape, **f32)
-        self.partials = torch.zeros((self.gradients_grid, self.P + SUMS), **f32)
-        self.grads = torch.zeros(self.P, **f32)
-        self.sumsq = torch.zeros(TENSORS, **f32)
-        self.sums = torch.zeros(SUMS, **f32)
+
+    def _views(self):
+        """the buffers of the current geometry: the first T * E * n floats of each whole one, in the batch's shape"""
+        shape = (self.T, self.E) if self._batch_dims == 2 else (self.T, self.E, self.n)
+        for name, whole in self._whole.items():
+            if name == "partials":
+                self.partials = whole[:self.gradients_grid]
+            elif name == "partials_returns" or name == "partials_advantages":
+                setattr(self, name, whole[:self.T * self.normalize_chunks * 2].view(self.T, self.normalize_chunks, 2))
+            else:
+                setattr(self, name, whole[:self.rows].view(shape))
 
     # ------------------------------------------------------------------------------------------------ the launches
     def _check_batch(self, t, tail, dtype=torch.float32, rows=None):
@@ -296,6 +325,97 @@ class _PgUpdateLaunches:
                         shared=0)
         return returns, advantages
 
+    # ---------------------------------------------------------------------------------------- neg_pos_env_ratio
+    def _downsample_setup(self):
+        """first use: the three entries of wd_kernels_pg_select.hsaco and what they write, sized once for the recorded
+        batch (a trainer without neg_pos_env_ratio pays for neither)"""
+        if self._fn_downsample is not None:
+            return
+        self._function_manager.initialize_functions(list(DOWNSAMPLE_ENTRIES))
+        self._fn_downsample = tuple(self._function_manager.get_function(n) for n in DOWNSAMPLE_ENTRIES)
+        E, rows = self.E_recorded, self.T * self.E_recorded * self.n
+        i32 = dict(dtype=torch.int32, device=self.device)
+        self.select_blocks = -(-E // SELECT_SCAN_THREADS)
+        self.positive, self.keys, self.keep_ids = (torch.zeros(E, **i32) for _ in range(3))   # (keys: uint32 bits)
+        self.block_counts, self.counts = torch.zeros(self.select_blocks, **i32), torch.zeros(3, **i32)
+        self._kept = {"obs": torch.zeros(rows * self.O, dtype=torch.float32, device=self.device),
+                      "actions": torch.zeros(rows, **i32),
+                      "rewards": torch.zeros(rows, dtype=torch.float32, device=self.device),
+                      "done": torch.zeros(self.T * E, **i32)}
+
+    def select_scan(self, done, epoch, seed_words, positive=None, keys=None, block_counts=None):
+        """positive [E] = done == 2 at any tick, keys [E] = word 0 of Philox counter (e, epoch, DOWNSAMPLE_STREAM_TAG, 6)
+        under `seed_words`, one positive count per block of 256 replicas; done [T, E] of the recorded batch"""
+        self._downsample_setup()
+        E = self.E_recorded
+        self._check_batch(done, 1, torch.int32, rows=self.T * E)
+        positive, keys = self.positive if positive is None else positive, self.keys if keys is None else keys
+        block_counts = self.block_counts if block_counts is None else block_counts
+        assert positive.numel() == keys.numel() == E and block_counts.numel() == self.select_blocks
+        self._fn_downsample[0](done, np.int32(self.T), np.int32(E), np.uint32(int(epoch) & 0xFFFFFFFF),
+                               np.uint32(DOWNSAMPLE_STREAM_TAG), np.uint32(int(seed_words[0]) & 0xFFFFFFFF),
+                               np.uint32(int(seed_words[1]) & 0xFFFFFFFF), positive, keys, block_counts,
+                               block=(SELECT_SCAN_THREADS, 1, 1), grid=(self.select_blocks, 1), shared=0)
+
+    def select_keep(self, ratio, positive=None, keys=None, block_counts=None, keep_ids=None, counts=None):
+        """keep_ids [K] ascending and counts = (K, positives, negatives kept) by losses._sample_positive_negative_env_ids'
+        rule: every replica when there is no positive or pos + int(pos * ratio) >= E, else the positives and the
+        int(pos * ratio) negatives with the smallest (key, replica id)"""
+        self._downsample_setup()
+        positive, keys = self.positive if positive is None else positive, self.keys if keys is None else keys
+        block_counts = self.block_counts if block_counts is None else block_counts
+        keep_ids, counts = self.keep_ids if keep_ids is None else keep_ids, self.counts if counts is None else counts
+        E = self.E_recorded
+        assert positive.numel() == keys.numel() == E and keep_ids.numel() >= E and counts.numel() == 3
+        assert all(t.dtype == torch.int32 and t.is_contiguous() for t in (positive, keys, block_counts, keep_ids, counts))
+        self._fn_downsample[1](keys, positive, block_counts, np.int32(block_counts.numel()), np.int32(E), np.float64(ratio),
+                               keep_ids, counts, block=(SELECT_KEEP_THREADS, 1, 1), grid=(1, 1), shared=0)
+
+    def gather_columns(self, K, pairs, keep_ids=None):
+        """dst [T][K][w] = src [T][E][keep_ids][w] for up to four (src, dst) pairs of 4-byte elements in ONE launch; the
+        width w of a pair is src's elements per (tick, replica)"""
+        self._downsample_setup()
+        keep_ids, E, K = self.keep_ids if keep_ids is None else keep_ids, self.E_recorded, int(K)
+        assert 1 <= K <= E and keep_ids.numel() >= K and 1 <= len(pairs) <= 4
+        args = []
+        for src, dst in pairs:
+            w = src.numel() // (self.T * E)
+            assert src.numel() == self.T * E * w and dst.numel() == self.T * K * w and w >= 1, (tuple(src.shape), K)
+            assert src.element_size() == dst.element_size() == 4 and src.is_contiguous() and dst.is_contiguous()
+            args += [src, dst, np.int32(w)]
+        args += [_NULL, _NULL, np.int32(0)] * (4 - len(pairs))
+        self._fn_downsample[2](keep_ids, np.int32(K), np.int32(self.T), np.int32(E), *args, block=(GATHER_THREADS, 1, 1),
+                               grid=(self.T * -(-K // GATHER_CHUNK), 1), shared=0)
+
+    def downsample(self, done, ratio, epoch, obs, actions, rewards, seed_words=(0, 0)):
+        """`trainer.neg_pos_env_ratio` before `compute_values`: scan, keep, ONE read-back of (K, positives, negatives
+        kept), and -- when K < E -- the gather of the kept columns of the four batch arrays, after which every later launch
+        has the geometry of a (T, K) batch and the buffers are views of the first T * K * n rows of the whole ones (no
+        allocation).  Returns (obs, actions, rewards, done) as the later launches are to read them: the arguments
+        themselves when every replica is kept.  `epoch`: the update's number (the keys of two updates differ)."""
+        self._downsample_setup()
+        if self.E != self.E_recorded:
+            self._geometry(self.E_recorded)
+            self._views()
+        self._check_batch(obs, self.O)
+        self._check_batch(actions, 1, torch.int32)
+        self._check_batch(rewards, 1)
+        self.select_scan(done, epoch, seed_words)
+        self.select_keep(ratio)
+        K, positives, negatives = self.counts.tolist()
+        self.sampled = (positives, negatives)
+        assert 1 <= K <= self.E_recorded and positives + negatives == K, (K, positives, negatives)
+        if K == self.E_recorded:
+            return obs, actions, rewards, done
+        T, n = self.T, self.n
+        kept = {"obs": self._kept["obs"][:T * K * n * self.O].view(T, K, n, self.O),
+                "actions": self._kept["actions"][:T * K * n].view(T, K, n, 1),
+                "rewards": self._kept["rewards"][:T * K * n].view(T, K, n), "done": self._kept["done"][:T * K].view(T, K)}
+        self.gather_columns(K, [(obs, kept["obs"]), (actions, kept["actions"]), (rewards, kept["rewards"]), (done, kept["done"])])
+        self._geometry(K)
+        self._views()
+        return kept["obs"], kept["actions"], kept["rewards"], kept["done"]
+
     def _normalize_setup(self):
         """first use: the three entries of wd_kernels_pg_norm.hsaco and what they write (a policy that never normalises
         pays for neither); partials [T][chunks][2] = (mean, M2) per chunk of a tick"""
@@ -304,9 +424,12 @@ class _PgUpdateLaunches:
         self._function_manager.initialize_functions(list(NORMALIZE_ENTRIES))
         self._fn_normalize = tuple(self._function_manager.get_function(n) for n in NORMALIZE_ENTRIES)
         f32 = dict(dtype=torch.float32, device=self.device)
-        self.norm_returns, self.norm_advantages = torch.zeros_like(self.returns), torch.zeros_like(self.advantages)
-        self.partials_returns = torch.zeros((self.T, self.normalize_chunks, 2), **f32)
-        self.partials_advantages = torch.zeros((self.T, self.normalize_chunks, 2), **f32)
+        rows, chunks = self.T * self.E_recorded * self.n, -(-self.E_recorded * self.n // NORMALIZE_CHUNK)
+        for name in ("norm_returns", "norm_advantages"):
+            self._whole[name] = torch.zeros(rows, **f32)
+        for name in ("partials_returns", "partials_advantages"):
+            self._whole[name] = torch.zeros(self.T * chunks * 2, **f32)
+        self._views()
 
     def normalize(self, normalize_return, normalize_advantage, returns=None, values=None, advantages=None,
                   norm_returns=None, norm_advantages=None):
@@ -397,7 +520,8 @@ class _PgUpdateLaunches:
         returns, advantages and the four sums (reads the device; call after `reduce`); rewards [T, E, n], actions
         [T, E, n, 1].  After `normalize(normalize_return, normalize_advantage)` the four sums are those of the normalised
         pair the gradient launch read, the raw and the normalised means are both reported and the explained variance is
-        formed from the normalised pair, as the framework does."""
+        formed from the normalised pair, as the framework does.  After `downsample` the arrays are those it returned and
+        its two counts are reported under the framework's names."""
         R = float(self.rows)
         s_pg, s_ent, s_vf, s_adv = (float(v) for v in self.sums.double().tolist())
         policy_loss = -(s_adv if ppo else s_pg) / R   # PPO at ratio 1: min(ratio * A, clamp(ratio) * A) = A
@@ -416,6 +540,8 @@ class _PgUpdateLaunches:
             "Mean (discounted) returns": ret.mean().item(), "Mean normalized returns": norm_ret.mean().item(),
             "Mean entropy": entropy, "Variance explained by the value function": var_explained.item(),
         }
+        if self.sampled is not None:   # (after `downsample`: the framework's two counts)
+            m["Num of Positive Sampled Envs"], m["Num of Negative Sampled Envs"] = self.sampled
         af = actions.reshape(self.T, self.E, self.n, -1).float()
         over_agents, over_time, over_envs = (af.std(dim=d).mean(dim=(0, 1)) for d in (2, 0, 1))
         for h in range(af.shape[-1]):

@@ -100,6 +100,9 @@ class Trainer:
         if not isinstance(config["trainer"].get("fused_update_normalize", False), bool):
             raise ValueError(f"trainer.fused_update_normalize: True or False, not "
                              f"{config['trainer']['fused_update_normalize']!r}")
+        if not isinstance(config["trainer"].get("fused_update_downsample", False), bool):
+            raise ValueError(f"trainer.fused_update_downsample: True or False, not "
+                             f"{config['trainer']['fused_update_downsample']!r}")
         E = env_wrapper.n_envs
         if policy_tag_to_agent_id_map is None:
             policy_tag_to_agent_id_map = {"shared": list(range(env_wrapper.n_agents))}
@@ -114,6 +117,9 @@ class Trainer:
         # {policy: (normalize_return, normalize_advantage)} of the policies on the "kernels" path whose returns / advantages
         # the normalising launches serve (`trainer.fused_update_normalize`)
         self._pg_normalize = {}
+        # the policies on the "kernels" path whose replicas the down-sampling launches choose
+        # (`trainer.fused_update_downsample` with `trainer.neg_pos_env_ratio` > 0)
+        self._pg_downsample = set()
         assert set(self.policies) == set(config["policy"]), "every policy needs a config entry"
         tcfg = config["trainer"]
         self.num_envs = E
@@ -136,6 +142,8 @@ class Trainer:
             env_wrapper.init_reset_pool(wdd.rank_seed(tcfg.get("seed", 0) or 0, self.rank))
         self.sampler = HIPSampler(env_wrapper.cuda_function_manager)
         self.sampler.init_random(seed=wdd.rank_seed(tcfg.get("seed", 0) or 0, self.rank) + 1)
+        # (the two words init_random leaves in the RNG state's header: the key of every Philox stream of this trainer)
+        self._seed_words = ((wdd.rank_seed(tcfg.get("seed", 0) or 0, self.rank) + 1) & 0x7FFFFFFF, 0x5BD1E995)
         create_and_push_data_placeholders(env_wrapper=env_wrapper, action_sampler=self.sampler,
                                           policy_tag_to_agent_id_map=self.policy_map,
                                           training_batch_size_per_env=self.batch_len,
@@ -411,7 +419,11 @@ class Trainer:
         `trainer.fused_update_normalize: true` (default false) keeps a policy with `normalize_return` /
         `normalize_advantage` on these launches: per-tick moments and the normalisations run as two or three more launches
         between the returns and the gradients (csrc/kernels/pg_normalize.hip; `_PgUpdateLaunches.normalize`), for all three
-        kinds of policy above.  Without the key such a policy is refused as before."""
+        kinds of policy above.  Without the key such a policy is refused as before.
+        `trainer.fused_update_downsample: true` (default false) does the same for `trainer.neg_pos_env_ratio` > 0: the
+        replicas are chosen and their columns gathered by three launches before the values launch
+        (csrc/kernels/pg_downsample.hip; `_PgUpdateLaunches.downsample`), for the first two kinds of policy; a custom
+        environment's policy stays refused.  Without the key the ratio is refused as before."""
         if tcfg.get("fused_update", True) != "all" or self.device.type != "cuda":
             return
         for pol in self.policies:
@@ -425,8 +437,12 @@ class Trainer:
             # launches of csrc/kernels/pg_normalize.hip then serve (`_update_with_pg_kernels`); without the key they refuse
             normalizes = (bool(pcfg["normalize_return"]), bool(pcfg["normalize_advantage"]))
             asked = (False, False) if tcfg.get("fused_update_normalize", False) else normalizes
+            # `trainer.fused_update_downsample`: likewise the first two rules are asked without neg_pos_env_ratio, which
+            # the launches of csrc/kernels/pg_downsample.hip then serve; the custom-environment rule keeps its refusal
+            downsamples = bool(tcfg.get("fused_update_downsample", False)) and self.neg_pos_env_ratio > 0
+            ratio_asked = -1 if downsamples else self.neg_pos_env_ratio
             ok, why = pguk.admitted_shape(self._batch_rollout is not None, len(self.policies), len(ids), self.head_sizes,
-                                          pcfg["model"]["fc_dims"], obs_size, dtype, *asked, self.neg_pos_env_ratio, self.world,
+                                          pcfg["model"]["fc_dims"], obs_size, dtype, *asked, ratio_asked, self.world,
                                           pcfg["algorithm"])
             if ok and self._batch_rollout["pack"] is not pack_rollout_policy:
                 ok, why = False, "the rollout's packed policy is not pack_rollout_policy's layout"
@@ -438,7 +454,7 @@ class Trainer:
                     self._batch_rollout is not None,
                     self._batch_rollout is not None and self._batch_rollout["pack"] is pack_gridworld_policy,
                     len(self.policies), len(ids), self.head_sizes, pcfg["model"]["fc_dims"], obs_size, dtype,
-                    *asked, self.neg_pos_env_ratio, self.world,
+                    *asked, ratio_asked, self.world,
                     pcfg["algorithm"])
                 if not gridworld and self._batch_rollout is not None and self._batch_rollout["pack"] is pack_gridworld_policy:
                     why = gw_why   # (a gridworld policy is told what the gridworld kernels miss, not that it has 5 agents)
@@ -480,6 +496,8 @@ class Trainer:
                 continue
             if any(normalizes):
                 self._pg_normalize[pol] = normalizes
+            if downsamples and not custom:
+                self._pg_downsample.add(pol)
             flat = pguk.FlatPolicy(self.models[pol])
             self._pg_flat[pol] = flat
             self._pg_adam[pol] = {"step": 0, "exp_avg": torch.zeros_like(flat.flat), "exp_avg_sq": torch.zeros_like(flat.flat)}
@@ -760,13 +778,17 @@ class Trainer:
 
     def _update_with_pg_kernels(self, pol, log):
         """one policy's gradient and optimizer step as five launches (`_setup_pg_update`); returns its metric dict on a
-        logging iteration -- formed from what the launches left on the device -- and reads nothing back otherwise"""
+        logging iteration -- formed from what the launches left on the device -- and reads nothing back otherwise (but the
+        three counts of `downsample` under `trainer.fused_update_downsample`)"""
         pcfg, k, flat, adam = self.config["policy"][pol], self._pg_kernels[pol], self._pg_flat[pol], self._pg_adam[pol]
         assert flat.bound(), "a parameter's .data was re-assigned"
         T, batch, objective = self.batch_len, self.batch[pol], self.trainers[pol]
         obs, actions, rewards, done = batch["obs"][:T], batch["actions"][:T], batch["rewards"][:T], self.done_batch[:T]
         vf_c = objective.vf_loss_coeff_schedule.get_param_value(self.current_timestep[pol])
         ent_c = objective.entropy_coeff_schedule.get_param_value(self.current_timestep[pol])
+        if pol in self._pg_downsample:   # (`trainer.fused_update_downsample`: 3 launches and the one read-back of 3 integers)
+            obs, actions, rewards, done = k.downsample(done, self.neg_pos_env_ratio, adam["step"], obs, actions, rewards,
+                                                       seed_words=self._seed_words)
         k.compute_values(obs, flat.flat)
         k.discounted_returns(rewards, done, objective.discount_factor_gamma)
         normalizes = self._pg_normalize.get(pol, (False, False))   # (`trainer.fused_update_normalize`: 2 or 3 launches more)
