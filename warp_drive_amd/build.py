@@ -88,6 +88,9 @@ UNITS = {
     # per replica, a radix select of the negatives to keep, and the gather of the kept columns; the flags of
     # wd_kernels_pg.hsaco
     "wd_kernels_pg_select.hsaco": ("pg_downsample.hip", []),
+    # GAE(lambda) in its returns launch's position (the policy key `gae_lambda`): the advantage recurrence as a scan of
+    # affine maps over time, S wavefronts per tile of 64 columns; the flags of wd_kernels_pg.hsaco
+    "wd_kernels_pg_gae.hsaco": ("pg_gae.hip", []),
     # its gradient launch with the three H x H products per row on the float32 matrix cores
     # (trainer.fused_update_gradients: "matrix"); KERNEL_FLAGS, and no packed float32 operations at all: nothing here gains
     # from them (see -fno-slp-vectorize below)

@@ -25,6 +25,21 @@ def discounted_returns(rewards, done_flags, values_detached, gamma):
     return returns
 
 
+def gae_returns(rewards, done_flags, values_detached, gamma, gae_lambda):
+    """A + V with the GAE(lambda) advantages A under this project's end-of-batch rule:
+        A_T = done (r_T - V_T) ;  A_t = delta_t + gamma lambda (1 - done_t) A_{t+1},
+        delta_t = r_t + gamma (1 - done_t) V_{t+1} - V_t
+    (R_T = A_T + V_T is discounted_returns' last row; lambda = 1: A_t + V_t = r_t + (1 - done_t) gamma R_{t+1}, its
+    recursion: the whole of `discounted_returns`)"""
+    done = (done_flags > 0).to(rewards.dtype)[..., None]  # [T, E, 1]
+    advantages = torch.zeros_like(rewards)
+    advantages[-1] = done[-1] * (rewards[-1] - values_detached[-1])
+    for t in range(rewards.shape[0] - 2, -1, -1):
+        delta = rewards[t] + (1 - done[t]) * gamma * values_detached[t + 1] - values_detached[t]
+        advantages[t] = delta + (1 - done[t]) * (gamma * gae_lambda) * advantages[t + 1]
+    return advantages + values_detached
+
+
 def _normalise(x):
     return (x - x.mean(dim=(1, 2), keepdim=True)) / (x.std(dim=(1, 2), keepdim=True) + _EPSILON)
 
@@ -33,9 +48,11 @@ class A2C:
     clip_param = None  # PPO sets it
 
     def __init__(self, discount_factor_gamma=1.0, normalize_advantage=False, normalize_return=False,
-                 vf_loss_coeff=0.01, entropy_coeff=0.01):
+                 vf_loss_coeff=0.01, entropy_coeff=0.01, gae_lambda=None):
         assert 0 <= discount_factor_gamma <= 1
+        assert gae_lambda is None or 0 <= gae_lambda <= 1
         self.discount_factor_gamma = discount_factor_gamma
+        self.gae_lambda = gae_lambda   # None: advantages = discounted returns - values; else GAE(lambda), `_returns`
         self.normalize_advantage = normalize_advantage
         self.normalize_return = normalize_return
         self.vf_loss_coeff_schedule = ParamScheduler(vf_loss_coeff)
@@ -43,6 +60,11 @@ class A2C:
 
     def _policy_loss(self, log_prob, advantages):
         return (-log_prob * advantages).mean()
+
+    def _returns(self, rewards, done_flags, values_detached):
+        if self.gae_lambda is None:
+            return discounted_returns(rewards, done_flags, values_detached, self.discount_factor_gamma)
+        return gae_returns(rewards, done_flags, values_detached, self.discount_factor_gamma, self.gae_lambda)
 
     @staticmethod
     def _sample_positive_negative_env_ids(done_flags_batch, negative_positive_ratio):
@@ -75,7 +97,7 @@ class A2C:
                 done_flags_batch, value_functions_batch = done_flags_batch[:, keep], value_functions_batch[:, keep]
                 action_probabilities_batch = [p[:, keep] for p in action_probabilities_batch]
         values_detached = value_functions_batch.detach()
-        returns = discounted_returns(rewards_batch, done_flags_batch, values_detached, self.discount_factor_gamma)
+        returns = self._returns(rewards_batch, done_flags_batch, values_detached)
         norm_returns = _normalise(returns) if self.normalize_return else returns
         vf_loss = nn.functional.mse_loss(value_functions_batch, norm_returns)
         advantages = norm_returns - values_detached
@@ -129,11 +151,11 @@ class A2C:
                              "the framework objective is compute_loss_and_metrics")
         values_detached = out[..., -1].detach()
         out_d = out.detach()
-        if kernels.supports_discounted_returns(rewards_batch, done_flags_batch, out_d):
+        if self.gae_lambda is None and kernels.supports_discounted_returns(rewards_batch, done_flags_batch, out_d):
             # (one kernel instead of a Python loop over T of four small ones: launch-bound, ~1.3 ms per policy)
             returns, advantages = kernels.discounted_returns(rewards_batch, done_flags_batch, out_d, self.discount_factor_gamma)
         else:
-            returns = discounted_returns(rewards_batch, done_flags_batch, values_detached, self.discount_factor_gamma)
+            returns = self._returns(rewards_batch, done_flags_batch, values_detached)
             advantages = None
         norm_returns = _normalise(returns) if self.normalize_return else returns
         if advantages is None or self.normalize_return:

@@ -16,6 +16,8 @@ launches of csrc/kernels/pg_normalize.hip (wd_kernels_pg_norm.hsaco) between the
 `trainer.fused_update_downsample: true` serves `trainer.neg_pos_env_ratio` too: three launches of
 csrc/kernels/pg_downsample.hip (wd_kernels_pg_select.hsaco) before the first, one read-back of three integers, and
 the launches above on the kept columns (`_PgUpdateLaunches.downsample`).
+A policy with `gae_lambda` launches HipPgGaeReturns (csrc/kernels/pg_gae.hip, wd_kernels_pg_gae.hsaco) in the second place:
+GAE(lambda) advantages as a scan over time, returns = advantages + values (`_PgUpdateLaunches.gae_returns`).
 `PgUpdateKernels` holds the launch wrappers, their geometry fixed from E, T, H, O, A and the compute-unit count;
 `FlatPolicy` makes the parameters of a FullyConnected views of one flat float32 buffer in the kernels' layout, so the
 kernels update the module in place and the module remains the source of truth.
@@ -60,6 +62,13 @@ SELECT_KEEP_THREADS = 1024  # HipPgSelectKeep is ONE block of these
 GATHER_THREADS = 256
 GATHER_CHUNK = 256         # kept columns per block of HipPgGatherColumns
 DOWNSAMPLE_STREAM_TAG = 0x646F776E   # "down": counter word 2 of the keys' Philox stream (word 3 is 6)
+# GAE(lambda) in the returns launch's position (csrc/kernels/pg_gae.hip; the policy key `gae_lambda`)
+GAE_CODE_OBJECT = "wd_kernels_pg_gae.hsaco"
+GAE_ENTRY = "HipPgGaeReturns"
+GAE_TILE = 64              # columns of a block: one per lane
+GAE_WAVEFRONTS = (1, 2, 4, 8, 16)   # S, the wavefronts of a block: each owns ceil(T / S) consecutive ticks
+GAE_MIN_ROWS = 8           # a segment shorter than this is not worth a wavefront
+GAE_FULL_DEVICE = 4        # tiles per compute unit (one wavefront per SIMD) from which time is not split
 _NULL = np.uint64(0)
 
 
@@ -121,6 +130,29 @@ def all_kernel_names():
 def matrix_kernel_names():
     """every entry of wd_kernels_pg_mx.hsaco"""
     return sorted(gradients_entry_name(H, O, "matrix") for H in HIDDEN for O in OBS_SIZES)
+
+
+def gae_kernel_names():
+    """every entry of wd_kernels_pg_gae.hsaco"""
+    return [GAE_ENTRY]
+
+
+def gae_wavefronts(columns, T, compute_units):
+    """S of HipPgGaeReturns for a [T][columns] batch: 1 when the ceil(columns / 64) one-wavefront blocks already give
+    every SIMD of the device a wavefront (GAE_FULL_DEVICE tiles per compute unit) or T is short; else the largest S of
+    GAE_WAVEFRONTS that leaves every wavefront at least GAE_MIN_ROWS ticks (T // S >= GAE_MIN_ROWS)."""
+    columns, T, compute_units = int(columns), int(T), int(compute_units)
+    assert columns >= 1 and T >= 1 and compute_units >= 1, (columns, T, compute_units)
+    if -(-columns // GAE_TILE) >= GAE_FULL_DEVICE * compute_units:
+        return 1
+    return max(S for S in GAE_WAVEFRONTS if S == 1 or T // S >= GAE_MIN_ROWS)
+
+
+def gae_lambda_refusal(value):
+    """"" when `value` is a policy's `gae_lambda` -- None or a number in [0, 1] -- else what is wrong with it"""
+    if value is None or (isinstance(value, (int, float)) and not isinstance(value, bool) and 0 <= value <= 1):
+        return ""
+    return f"None or a number in [0, 1], not {value!r}"
 
 
 def _admitted_tail(fc_dims, obs_size, obs_sizes, obs_takes, dtype, normalize_return, normalize_advantage, neg_pos_env_ratio,
@@ -240,9 +272,9 @@ class _PgUpdateLaunches:
         self.values_lds, self.gradients_lds = values_lds, gradients_lds
         self.gradients_block, self._blocks_per_cu = int(gradients_block), int(blocks_per_cu)
         self.apply_grid = -(-max(self.P, self.packed_floats) // APPLY_THREADS)
-        # (the normalising and the down-sampling launches: their entries and buffers come with the first `normalize` /
-        # `downsample`)
-        self._function_manager, self._fn_normalize, self._fn_downsample = function_manager, None, None
+        # (the normalising, the down-sampling and the GAE launches: their entries and buffers come with the first
+        # `normalize` / `downsample` / `gae_returns`)
+        self._function_manager, self._fn_normalize, self._fn_downsample, self._fn_gae = function_manager, None, None, None
         assert max(self.values_lds, self.gradients_lds) <= LDS_LIMIT
         self.sampled = None                # (positives, negatives kept) of the last `downsample`
         self.E_recorded = self.E           # replicas of the recorded batch; `downsample` may leave self.E below it
@@ -323,6 +355,26 @@ class _PgUpdateLaunches:
         self.fn_returns(rewards, done, values, np.int32(1), np.int32(0), np.float32(gamma), np.int32(self.T), np.int32(self.E),
                         np.int32(self.n), returns, advantages, block=(RETURNS_THREADS, 1, 1), grid=(self.returns_grid, 1),
                         shared=0)
+        return returns, advantages
+
+    def gae_returns(self, rewards, done, gamma, gae_lambda, values=None, returns=None, advantages=None, wavefronts=None):
+        """(returns, returns - values) [T, E(, n)] with returns = A + values, A the GAE(lambda) advantages of
+        losses.gae_returns, from HipPgGaeReturns in `discounted_returns`' position; done [T, E] is the replica's.  A block
+        is 64 columns x `wavefronts` segments of ticks (None: `gae_wavefronts` of the current geometry)."""
+        values = self.values if values is None else values
+        returns = self.returns if returns is None else returns
+        advantages = self.advantages if advantages is None else advantages
+        self._check_batch(rewards, 1)
+        self._check_batch(done, 1, torch.int32, rows=self.T * self.E)
+        self._check_flat(values, returns, advantages, numel=self.rows)
+        if self._fn_gae is None:
+            self._function_manager.initialize_functions([GAE_ENTRY])
+            self._fn_gae = self._function_manager.get_function(GAE_ENTRY)
+        S = gae_wavefronts(self.columns, self.T, self.compute_units) if wavefronts is None else int(wavefronts)
+        assert S in GAE_WAVEFRONTS, S
+        self._fn_gae(rewards, done, values, np.float32(gamma), np.float32(gae_lambda), np.int32(self.T), np.int32(self.E),
+                     np.int32(self.n), returns, advantages, block=(GAE_TILE * S, 1, 1),
+                     grid=(-(-self.columns // GAE_TILE), 1), shared=8 * GAE_TILE * S if S > 1 else 0)
         return returns, advantages
 
     # ---------------------------------------------------------------------------------------- neg_pos_env_ratio

@@ -103,6 +103,9 @@ class Trainer:
         if not isinstance(config["trainer"].get("fused_update_downsample", False), bool):
             raise ValueError(f"trainer.fused_update_downsample: True or False, not "
                              f"{config['trainer']['fused_update_downsample']!r}")
+        for pol, pcfg in config["policy"].items():
+            if pguk.gae_lambda_refusal(pcfg.get("gae_lambda")):
+                raise ValueError(f"policy.{pol}.gae_lambda: {pguk.gae_lambda_refusal(pcfg.get('gae_lambda'))}")
         E = env_wrapper.n_envs
         if policy_tag_to_agent_id_map is None:
             policy_tag_to_agent_id_map = {"shared": list(range(env_wrapper.n_agents))}
@@ -182,7 +185,7 @@ class Trainer:
             self.optimizers[pol] = torch.optim.Adam(model.parameters(), lr=pcfg["lr"])
             common = dict(discount_factor_gamma=pcfg["gamma"], normalize_advantage=pcfg["normalize_advantage"],
                           normalize_return=pcfg["normalize_return"], vf_loss_coeff=pcfg["vf_loss_coeff"],
-                          entropy_coeff=pcfg["entropy_coeff"])
+                          entropy_coeff=pcfg["entropy_coeff"], gae_lambda=pcfg.get("gae_lambda"))
             algo = pcfg["algorithm"].upper()
             if algo == "A2C":
                 self.trainers[pol] = A2C(**common)
@@ -423,7 +426,10 @@ class Trainer:
         `trainer.fused_update_downsample: true` (default false) does the same for `trainer.neg_pos_env_ratio` > 0: the
         replicas are chosen and their columns gathered by three launches before the values launch
         (csrc/kernels/pg_downsample.hip; `_PgUpdateLaunches.downsample`), for the first two kinds of policy; a custom
-        environment's policy stays refused.  Without the key the ratio is refused as before."""
+        environment's policy stays refused.  Without the key the ratio is refused as before.
+        A policy with the key `gae_lambda` (a number in [0, 1]; absent or None: nothing changes) is admitted like any other
+        and launches HipPgGaeReturns (csrc/kernels/pg_gae.hip; `_PgUpdateLaunches.gae_returns`) in the returns launch's
+        place, for all three kinds of policy."""
         if tcfg.get("fused_update", True) != "all" or self.device.type != "cuda":
             return
         for pol in self.policies:
@@ -790,7 +796,10 @@ class Trainer:
             obs, actions, rewards, done = k.downsample(done, self.neg_pos_env_ratio, adam["step"], obs, actions, rewards,
                                                        seed_words=self._seed_words)
         k.compute_values(obs, flat.flat)
-        k.discounted_returns(rewards, done, objective.discount_factor_gamma)
+        if objective.gae_lambda is None:
+            k.discounted_returns(rewards, done, objective.discount_factor_gamma)
+        else:   # (the policy key `gae_lambda`: HipPgGaeReturns in the returns launch's position, the same two buffers)
+            k.gae_returns(rewards, done, objective.discount_factor_gamma, objective.gae_lambda)
         normalizes = self._pg_normalize.get(pol, (False, False))   # (`trainer.fused_update_normalize`: 2 or 3 launches more)
         advantages, returns = k.normalize(*normalizes)
         k.gradients(obs, actions, flat.flat, ent_c, vf_c, advantages=advantages, returns=returns)
